@@ -23,7 +23,12 @@ N = 250 cloud points (the reference's downsample=true default; --full-cloud: all
 frames), p32 (configs[0]'s shape, 32 x 10), p4096 (configs[3], 4096 x 40), subswarm8
 (configs[4]: 1024 particles per rank x 30; run with --gpus 8).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--full]
+       A plain run sets up, warms up, times the K steps and prints the result line.
+       --full adds everything else to that line: per-frame and per-kernel device times,
+       the roofline, the tracking error, the extra passes (extra_passes) and the same-run
+       CPU baseline (--no-cpu-baseline leaves that one out).
+       --dump-outputs DIR writes the last timed step's {bestp, cost} as DIR/*.npy.
        --gpus N > 1 without a torch.distributed environment re-launches itself under
        `python -m torch.distributed.run --nproc-per-node N` (a child process started
        before anything touches the GPU) and exits with its return code.
@@ -124,6 +129,15 @@ def parse():
                     help="test mode: each rank saves its state after every frame of the first "
                          "pass (synchronising per frame) and rank 0 the first raw frame and x0, "
                          "as .npy under this directory")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the timed path returned for its "
+                         "last step, the tracker state {bestp[26], cost}, as DIR/bestp.npy and "
+                         "DIR/cost.npy (float64); the same arguments give the same inputs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the diagnostic passes (per-frame and "
+                         "per-kernel device times, roofline, tracking error, the extra passes of "
+                         "extra_passes) and the CPU baseline, and report them in the result line; "
+                         "a plain run only times the steps")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.exchange_form is None:
@@ -153,6 +167,15 @@ def parse():
     return a
 
 
+def refine_info(ctx, lib):
+    """The refine form the context runs (hpe_set_refine_exact), named for the result line."""
+    exact = int(lib.hpe_get_refine_exact(ctx.h))
+    return {"refine_form": ("chain: the reference's DH chain on every evaluation" if exact else
+                            "hand-frame: spheres Rg q + u from centres built once per call, FK "
+                            "within 1e-12 cm of the chain (DESIGN.md §2)"),
+            "refine_kernel": "k_refine, one workgroup"}
+
+
 # ------------------------------------------------------------------------- extra passes
 def extra_passes(args, ctx, lib, state, state0, raw, n_frames, P, refine, ds, world, rank, local):
     """Diagnostic passes over the timed frames, after the timed region (never in `value`):
@@ -173,11 +196,7 @@ def extra_passes(args, ctx, lib, state, state0, raw, n_frames, P, refine, ds, wo
     import torch.distributed as dist
 
     exact0 = int(lib.hpe_get_refine_exact(ctx.h))
-    out = {"refine_form": ("chain: the reference's DH chain on every evaluation" if exact0 else
-                           "hand-frame: spheres Rg q + u from centres built once per call, FK "
-                           "within 1e-12 cm of the chain (DESIGN.md §2)"),
-           "refine_kernel": "k_refine, one workgroup",
-           "refine_exact_ms_per_step": None, "per_frame_graph_ms_per_step": None,
+    out = {"refine_exact_ms_per_step": None, "per_frame_graph_ms_per_step": None,
            "scaling_baseline_ms_per_step": None, "exchange_off_ms_per_step": None,
            "note": ("diagnostic passes after the timed region over the same frames (second of two "
                     "runs each): refine_exact = reference-order refine; per_frame_graph = one "
@@ -239,6 +258,151 @@ def extra_passes(args, ctx, lib, state, state0, raw, n_frames, P, refine, ds, wo
     state.copy_(state0)
     torch.cuda.synchronize()
     return out
+
+
+# ------------------------------------------------------------------------- --full passes
+def diagnostic_passes(args, hand, state, state0, raw, poses, ext, step, run_sequence, ranks,
+                      sub_info, P, refine, ds, world, rank, local):
+    """--full: the passes after the timed region, over the timed frames again from state0
+    (never in `value`): per-frame device time, per-kernel durations with the tracking error,
+    then extra_passes.  Fills ranks / sub_info's exchange_us; returns (prof, rev, errs, extra)."""
+    import numpy as np
+    import torch
+    import hpe
+
+    ctx, lib = hand.ctx, hand.ctx.lib
+    K, n_frames = args.frames_per_graph, args.warmup + args.steps
+    # per-frame device time: the same frames again with one event pair per frame on the
+    # tracker stream (not in the timed region: each timing event adds a marker, ~5 us)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(args.steps)]
+    state.copy_(state0)
+    torch.cuda.synchronize()
+    if not args.resident and not K:
+        ctx.pipeline_begin(raw[args.warmup], True, ds)
+    if K:  # one event pair around the whole sequence
+        ev[0][0].record(ext)
+        run_sequence(args.warmup, args.steps)
+        ev[0][1].record(ext)
+    ex = []  # the per-frame exchange (N > 1): event pairs around it on the tracker stream
+    for k, f in enumerate(range(args.warmup, n_frames if not K else 0)):
+        ev[k][0].record(ext)
+        step(f, ex if world > 1 else None)
+        ev[k][1].record(ext)
+    ctx.check(lib.hpe_sync(ctx.h))
+    torch.cuda.synchronize()
+    frame_us = ([a.elapsed_time(b) * 1e3 for a, b in ev] if not K else
+                [ev[0][0].elapsed_time(ev[0][1]) * 1e3 / args.steps])
+    ex_us = [x if isinstance(x, float) else x[0].elapsed_time(x[1]) * 1e3 for x in ex]
+    if ranks is not None and ex_us:
+        ranks["exchange_us"] = {
+            "mean": float(np.mean(ex_us)), "median": float(np.median(ex_us)),
+            "max": float(np.max(ex_us)), "frames": len(ex_us),
+            "note": ("rank 0: events around the all-gather + pick on the tracker stream (the "
+                     "wait for the other ranks included), second pass" if args.backend == "nccl"
+                     else "rank 0: host wall time of the gloo exchange, second pass")}
+    # per-kernel durations: the same frames once more with every dispatch bracketed by
+    # hipExtLaunchKernel start/stop events on the tracker stream the kernels run on
+    # (direct launches; kernels are identical)
+    ctx.check(lib.hpe_profile_enable(ctx.h, 1))
+    rev = C.c_uint64(0)
+    ctx.check(lib.hpe_refine_eval_count(ctx.h, C.byref(rev), 1))  # reset
+    state.copy_(state0)
+    torch.cuda.synchronize()
+    if not args.resident:
+        ctx.pipeline_begin(raw[args.warmup], True, ds)
+    errs = []  # gnd_truth_err (costfunc.cpp:476-507) of each frame's bestp vs the true pose
+    for f in range(args.warmup, n_frames):
+        step(f)
+        ctx.check(lib.hpe_sync(ctx.h))
+        torch.cuda.synchronize()
+        if poses is None:
+            continue
+        bp = state[:26].cpu().numpy()
+        hand.build_hand_model(bp)
+        est = hand.hand_joints.copy()
+        hand.build_hand_model(poses[f])
+        gt = hand.hand_joints * 10.0
+        gt[:, 1:3] *= -1
+        errs.append(hpe.gnd_truth_err(est, gt.ravel()))
+    ctx.check(lib.hpe_sync(ctx.h))
+    ctx.check(lib.hpe_refine_eval_count(ctx.h, C.byref(rev), 1))
+    prof = {}
+    for name, kid in (("k_pso_gen", 0), ("k_refine", 1), ("k_pso_init", 2), ("k_pso_final", 3),
+                      ("k_preprocess", 4), ("exchange", hpe._lib.PROF_EXCHANGE)):
+        nl = C.c_int32(0); tot = C.c_double(0); mn = C.c_double(0); mx = C.c_double(0)
+        ctx.check(lib.hpe_profile_read_kernel(ctx.h, kid, C.byref(nl), C.byref(tot),
+                                              C.byref(mn), C.byref(mx)))
+        prof[name] = {"launches": nl.value, "avg_us": tot.value / max(nl.value, 1) * 1e3,
+                      "min_us": mn.value * 1e3, "max_us": mx.value * 1e3,
+                      "total_ms": tot.value}
+    ctx.check(lib.hpe_profile_enable(ctx.h, 0))
+    if args.lib_exchange:  # event pairs around the library's all-gather + pick, per frame
+        xs = {"mean": prof["exchange"]["avg_us"], "min": prof["exchange"]["min_us"],
+              "max": prof["exchange"]["max_us"], "frames": prof["exchange"]["launches"],
+              "note": ("rank 0: hipEvents around the library's RCCL all-gather + k_pick_best on "
+                       "the tracker stream (the wait for the other ranks included), in the "
+                       "direct-launch profiling pass; inside the timed graphs the same nodes run "
+                       "without the events")}
+        if ranks is not None:
+            ranks["exchange_us"] = xs
+        sub_info["exchange_us"] = xs
+    extra = extra_passes(args, ctx, lib, state, state0, raw, n_frames, P, refine, ds, world, rank,
+                         local)
+    prof["frame_graph"] = {"launches": len(frame_us), "avg_us": sum(frame_us) / len(frame_us),
+                           "min_us": min(frame_us), "max_us": max(frame_us),
+                           "median_us": float(np.median(frame_us)),
+                           "per_frame_us": [round(x, 1) for x in frame_us],
+                           "note": ("one event pair per frame, a second pass over the frames"
+                                    if not K else "one event pair around the whole sequence "
+                                    "(a second pass), per frame")}
+    return prof, rev, errs, extra
+
+
+def diagnostic_report(args, prof, rev, errs, extra, P, n_pts, lib_path):
+    """The result line's --full entries from what diagnostic_passes measured."""
+    import numpy as np
+    gen = roofline_entry("k_pso_gen", prof, P, n_pts, lib_path, P)
+    ref_launches = prof["k_refine"]["launches"]
+    ref = (roofline_entry("k_refine", prof, rev.value / ref_launches, n_pts, lib_path, P)
+           if ref_launches and rev.value else None)
+    kernels_rf = {"k_pso_gen": gen, "k_refine": ref}
+    # the dominant kernel: the most device time per frame (hipExtLaunchKernel events)
+    dom = max((k for k in kernels_rf if kernels_rf[k]),
+              key=lambda k: prof[k]["total_ms"], default=None)
+    roof = dict(kernels_rf[dom]) if dom else {}
+    if roof:
+        roof["note"] = (
+            "dominant kernel by device time per frame; algorithmic bytes per launch = "
+            "evaluations per launch x (12N + 600) (SURVEY.md §8 d2), per-launch time from "
+            "hipExtLaunchKernel events on the tracker stream; " + (
+                "k_pso_gen = one generation of the swarm per launch, one particle per "
+                "workgroup" if dom == "k_pso_gen" else
+                "k_refine = refine_init_pose as ONE workgroup (a serial chain of "
+                "evaluations), plus the next frame's preparation workgroups") +
+            "; latency-bound (dependent generations / a serial line search), DESIGN.md §5")
+        roof["limiter"] = "latency"
+    dominant = {"kernel": dom,
+                "ms_per_frame": {k: prof[k]["total_ms"] / max(args.steps, 1)
+                                 for k in ("k_pso_gen", "k_refine", "k_pso_init",
+                                           "k_pso_final")}}
+    return {
+        "tracking_err_mm": ({"sum_wrist_tips_mean": float(np.mean(errs)),
+                             "per_joint_mean": float(np.mean(errs) / 6),
+                             "note": "gnd_truth_err (costfunc.cpp:476-507) vs the synthetic "
+                                     "trajectory's true poses, second pass over the frames"}
+                            if errs else None),
+        "roofline": roof or None,
+        "dominant_kernel": dominant,
+        "roofline_kernels": kernels_rf,
+        "refine_exact_ms_per_step": extra["refine_exact_ms_per_step"],
+        "per_frame_graph_ms_per_step": extra["per_frame_graph_ms_per_step"],
+        "scaling_baseline_ms_per_step": extra["scaling_baseline_ms_per_step"],
+        "exchange_off_ms_per_step": extra["exchange_off_ms_per_step"],
+        "extra_passes_note": extra["note"],
+        "refine_evals_per_frame": rev.value / max(ref_launches, 1),
+        "kernels": prof,
+    }
 
 
 # ------------------------------------------------------------------------- launcher
@@ -479,6 +643,11 @@ def stub_main(args, world, rank):
         el, ranks = rank_report(args, world, rank, el, state.numpy(), "cpu",
                                 {"pci": "cpu", "uuid": f"stub-rank{rank}", "name": "stub",
                                  "local_rank": rank})
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "bestp.npy"), state[:26].numpy())
+        np.save(os.path.join(args.dump_outputs, "cost.npy"), state[26:27].numpy())
     if rank == 0:
         print(json.dumps({"metric": "stub exchange", "value": args.steps * world / el,
                           "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -536,7 +705,7 @@ def main():
     else:
         poses = synth.trajectory(n_frames, args.seed, revert=TRAJ_REVERT)
         raw = [np.ascontiguousarray(ctx.render_depth(th)) for th in poses]
-    sizes = [len(hpe.preprocess_depth(d, True, ds)["cloud"]) for d in raw]
+    n_pts = len(hpe.preprocess_depth(raw[args.warmup], True, ds)["cloud"])  # first timed frame
     if args.resident:  # frames preprocessed and resident in HBM before the timed region
         for f in range(n_frames):
             ctx.prepare_frame(f, raw[f], True, ds)
@@ -663,119 +832,19 @@ def main():
         np.save(os.path.join(args.dump, f"states_rank{rank}.npy"), np.array(dumped))
     if sub_info is not None:  # in_graphs: the exchange ran inside the captured frame graphs
         sub_info.update(ctx.subswarm_info())
-    # per-frame device time: the same frames again with one event pair per frame on the
-    # tracker stream (not in the timed region: each timing event adds a marker, ~5 us)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(args.steps)]
-    state.copy_(state0)
-    torch.cuda.synchronize()
-    if not args.resident and not K:
-        ctx.pipeline_begin(raw[args.warmup], True, ds)
-    if K:  # one event pair around the whole sequence
-        ev[0][0].record(ext)
-        run_sequence(args.warmup, args.steps)
-        ev[0][1].record(ext)
-    ex = []  # the per-frame exchange (N > 1): event pairs around it on the tracker stream
-    for k, f in enumerate(range(args.warmup, n_frames if not K else 0)):
-        ev[k][0].record(ext)
-        step(f, ex if world > 1 else None)
-        ev[k][1].record(ext)
-    ctx.check(lib.hpe_sync(ctx.h))
-    torch.cuda.synchronize()
-    frame_us = ([a.elapsed_time(b) * 1e3 for a, b in ev] if not K else
-                [ev[0][0].elapsed_time(ev[0][1]) * 1e3 / args.steps])
-    ex_us = [x if isinstance(x, float) else x[0].elapsed_time(x[1]) * 1e3 for x in ex]
-    if ranks is not None and ex_us:
-        ranks["exchange_us"] = {
-            "mean": float(np.mean(ex_us)), "median": float(np.median(ex_us)),
-            "max": float(np.max(ex_us)), "frames": len(ex_us),
-            "note": ("rank 0: events around the all-gather + pick on the tracker stream (the "
-                     "wait for the other ranks included), second pass" if args.backend == "nccl"
-                     else "rank 0: host wall time of the gloo exchange, second pass")}
-    # per-kernel durations: the same frames once more with every dispatch bracketed by
-    # hipExtLaunchKernel start/stop events on the tracker stream the kernels run on
-    # (direct launches; kernels are identical)
-    ctx.check(lib.hpe_profile_enable(ctx.h, 1))
-    rev = C.c_uint64(0)
-    ctx.check(lib.hpe_refine_eval_count(ctx.h, C.byref(rev), 1))  # reset
-    state.copy_(state0)
-    torch.cuda.synchronize()
-    if not args.resident:
-        ctx.pipeline_begin(raw[args.warmup], True, ds)
-    errs = []  # gnd_truth_err (costfunc.cpp:476-507) of each frame's bestp vs the true pose
-    for f in range(args.warmup, n_frames):
-        step(f)
-        ctx.check(lib.hpe_sync(ctx.h))
-        torch.cuda.synchronize()
-        if poses is None:
-            continue
-        bp = state[:26].cpu().numpy()
-        hand.build_hand_model(bp)
-        est = hand.hand_joints.copy()
-        hand.build_hand_model(poses[f])
-        gt = hand.hand_joints * 10.0
-        gt[:, 1:3] *= -1
-        errs.append(hpe.gnd_truth_err(est, gt.ravel()))
-    ctx.check(lib.hpe_sync(ctx.h))
-    ctx.check(lib.hpe_refine_eval_count(ctx.h, C.byref(rev), 1))
-    prof = {}
-    for name, kid in (("k_pso_gen", 0), ("k_refine", 1), ("k_pso_init", 2), ("k_pso_final", 3),
-                      ("k_preprocess", 4), ("exchange", hpe._lib.PROF_EXCHANGE)):
-        nl = C.c_int32(0); tot = C.c_double(0); mn = C.c_double(0); mx = C.c_double(0)
-        ctx.check(lib.hpe_profile_read_kernel(ctx.h, kid, C.byref(nl), C.byref(tot),
-                                              C.byref(mn), C.byref(mx)))
-        prof[name] = {"launches": nl.value, "avg_us": tot.value / max(nl.value, 1) * 1e3,
-                      "min_us": mn.value * 1e3, "max_us": mx.value * 1e3,
-                      "total_ms": tot.value}
-    ctx.check(lib.hpe_profile_enable(ctx.h, 0))
-    if args.lib_exchange:  # event pairs around the library's all-gather + pick, per frame
-        xs = {"mean": prof["exchange"]["avg_us"], "min": prof["exchange"]["min_us"],
-              "max": prof["exchange"]["max_us"], "frames": prof["exchange"]["launches"],
-              "note": ("rank 0: hipEvents around the library's RCCL all-gather + k_pick_best on "
-                       "the tracker stream (the wait for the other ranks included), in the "
-                       "direct-launch profiling pass; inside the timed graphs the same nodes run "
-                       "without the events")}
-        if ranks is not None:
-            ranks["exchange_us"] = xs
-        sub_info["exchange_us"] = xs
-    extra = extra_passes(args, ctx, lib, state, state0, raw, n_frames, P, refine, ds, world, rank,
-                         local)
-    prof["frame_graph"] = {"launches": len(frame_us), "avg_us": sum(frame_us) / len(frame_us),
-                           "min_us": min(frame_us), "max_us": max(frame_us),
-                           "median_us": float(np.median(frame_us)),
-                           "per_frame_us": [round(x, 1) for x in frame_us],
-                           "note": ("one event pair per frame, a second pass over the frames"
-                                    if not K else "one event pair around the whole sequence "
-                                    "(a second pass), per frame")}
+    if args.dump_outputs and rank == 0:  # what the timed path returned for its last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "bestp.npy"), final[:26].astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "cost.npy"), final[26:27].astype(np.float64))
+    rinfo = refine_info(ctx, lib)
+    if args.full:
+        prof, rev, errs, extra = diagnostic_passes(args, hand, state, state0, raw, poses, ext, step,
+                                                   run_sequence, ranks, sub_info, P, refine, ds,
+                                                   world, rank, local)
     lib_path = hpe._lib.load()._name
 
     if rank == 0:
-        n_pts = sizes[args.warmup]
         evals = P * (G + 1) * args.steps * world
-        gen = roofline_entry("k_pso_gen", prof, P, n_pts, lib_path, P)
-        ref_launches = prof["k_refine"]["launches"]
-        ref = (roofline_entry("k_refine", prof, rev.value / ref_launches, n_pts, lib_path, P)
-               if ref_launches and rev.value else None)
-        kernels_rf = {"k_pso_gen": gen, "k_refine": ref}
-        # the dominant kernel: the most device time per frame (hipExtLaunchKernel events)
-        dom = max((k for k in kernels_rf if kernels_rf[k]),
-                  key=lambda k: prof[k]["total_ms"], default=None)
-        roof = dict(kernels_rf[dom]) if dom else {}
-        if roof:
-            roof["note"] = (
-                "dominant kernel by device time per frame; algorithmic bytes per launch = "
-                "evaluations per launch x (12N + 600) (SURVEY.md §8 d2), per-launch time from "
-                "hipExtLaunchKernel events on the tracker stream; " + (
-                    "k_pso_gen = one generation of the swarm per launch, one particle per "
-                    "workgroup" if dom == "k_pso_gen" else
-                    "k_refine = refine_init_pose as ONE workgroup (a serial chain of "
-                    "evaluations), plus the next frame's preparation workgroups") +
-                "; latency-bound (dependent generations / a serial line search), DESIGN.md §5")
-            roof["limiter"] = "latency"
-        dominant = {"kernel": dom,
-                    "ms_per_frame": {k: prof[k]["total_ms"] / max(args.steps, 1)
-                                     for k in ("k_pso_gen", "k_refine", "k_pso_init",
-                                               "k_pso_final")}}
         line = {
             "metric": "particle-evals/sec + tracked FPS, 320x240 depth, 256p x 30gen",
             "value": evals / el,
@@ -811,8 +880,8 @@ def main():
                                       {"seed": args.seed, "revert": TRAJ_REVERT,
                                        "frames": n_frames}),
                        "cloud_points": n_pts, "refine": bool(refine),
-                       "refine_form": extra["refine_form"],
-                       "refine_kernel": extra["refine_kernel"],
+                       "refine_form": rinfo["refine_form"],
+                       "refine_kernel": rinfo["refine_kernel"],
                        "exchange_form": (
                            "library: libhpe.so's RCCL all-gather + pick after every frame, "
                            + ("captured in the frame graphs" if sub_info["in_graphs"] else
@@ -831,28 +900,16 @@ def main():
                                             else ")"))},
             "tracked_fps": args.steps / el,
             "final_cost": float(final[26]),
-            "tracking_err_mm": ({"sum_wrist_tips_mean": float(np.mean(errs)),
-                                 "per_joint_mean": float(np.mean(errs) / 6),
-                                 "note": "gnd_truth_err (costfunc.cpp:476-507) vs the synthetic "
-                                         "trajectory's true poses, second pass over the frames"}
-                                if errs else None),
-            "roofline": roof or None,
-            "dominant_kernel": dominant,
-            "roofline_kernels": kernels_rf,
-            "refine_exact_ms_per_step": extra["refine_exact_ms_per_step"],
-            "per_frame_graph_ms_per_step": extra["per_frame_graph_ms_per_step"],
-            "scaling_baseline_ms_per_step": extra["scaling_baseline_ms_per_step"],
-            "exchange_off_ms_per_step": extra["exchange_off_ms_per_step"],
             "subswarm": sub_info,
-            "extra_passes_note": extra["note"],
-            "refine_evals_per_frame": rev.value / max(ref_launches, 1),
-            "kernels": prof,
             "host_us_per_step": host_s / args.steps * 1e6,
             "cold_graphs_ms_per_step": cold_ms,
             "ranks": ranks,
             "lib_sha256": lib_sha256(lib_path),
+            "full": bool(args.full),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line.update(diagnostic_report(args, prof, rev, errs, extra, P, n_pts, lib_path))
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args, raw if args.frames else None)
             line["cpu_baseline"] = cb
             line["speedup_vs_cpu"] = {"particle_evals": line["value"] / cb["value"],

@@ -42,6 +42,34 @@ def test_single_rank_stub():
     assert r["n_gpus"] == 1 and r["winner_rank"] == 0
 
 
+def test_dump_outputs_stub(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the last timed step's {bestp, cost} as float64 .npy;
+    the same arguments give the same arrays."""
+    import numpy as np
+    got = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        r = _bench("--stub", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+        assert sorted(p.name for p in d.iterdir()) == ["bestp.npy", "cost.npy"]
+        bestp, cost = np.load(d / "bestp.npy"), np.load(d / "cost.npy")
+        assert bestp.dtype == np.float64 and bestp.shape == (26,)
+        assert cost.dtype == np.float64 and cost.shape == (1,)
+        assert cost[0] == r["winner_cost"] and np.all(bestp == r["winner_rank"])
+        got.append((bestp, cost))
+    np.testing.assert_array_equal(got[0][0], got[1][0])
+    np.testing.assert_array_equal(got[0][1], got[1][1])
+
+
+def test_full_is_off_by_default(monkeypatch):
+    sys.path.insert(0, str(hand_data.ROOT))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
 def test_frames_per_graph_defaults(monkeypatch):
     """The frame loop bench.py times: on one GPU, and with N > 1 over the library exchange
     (hpe_subswarm_init, the default with nccl: the all-gather inside the frames' graphs), the

@@ -27,7 +27,7 @@ def _bench_ranks(dump, *extra):
         env.pop(k, None)
     cmd = [sys.executable, str(hand_data.ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo",
            "--same-device", "--config", "subswarm8", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--dump", str(dump), *extra]
+           "--full", "--no-cpu-baseline", "--dump", str(dump), *extra]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

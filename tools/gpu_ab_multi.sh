@@ -7,7 +7,7 @@ O=gpurun_out/abm
 rm -rf $O; mkdir -p $O
 for r in $(seq 1 $R); do
   for v in "$@"; do
-    HPE_LIB_VARIANT=$v timeout -k 10 200 python bench.py --steps 40 --no-cpu-baseline $BENCH_ARGS > $O/bench_$(basename $v .so)_$r.log 2>&1 || exit 1
+    HPE_LIB_VARIANT=$v timeout -k 10 200 python bench.py --full --steps 40 --no-cpu-baseline $BENCH_ARGS > $O/bench_$(basename $v .so)_$r.log 2>&1 || exit 1
   done
 done
 python3 - <<'PY'

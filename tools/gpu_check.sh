@@ -8,4 +8,4 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$R
 mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -x -v -m gpu ${K:+-k "$K"} --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1 && \
-timeout -k 10 300 python -u bench.py > $O/bench.log 2>&1
+timeout -k 10 300 python -u bench.py --full > $O/bench.log 2>&1
