@@ -235,6 +235,12 @@ struct hpe_ctx {
     // context stream -- captured into the tracking graphs with the frames
     struct Subswarm {
         ncclComm_t comm = nullptr;
+        // the scripted transport (hpe_subswarm_init_scripted) in the communicator's place:
+        // peer rows [script_frames][nranks][27] and the device exchange counter
+        double *d_script = nullptr;
+        int *d_script_k = nullptr;
+        int script_frames = 0;
+        bool transport() const { return comm || d_script; }
         int nranks = 0, rank = 0;
         bool on = false;
         double *d_gath = nullptr;  // [nranks][27]: row `rank` is this rank's frame result
@@ -549,21 +555,30 @@ static int exchange_after(hpe_ctx *c, const DevSwarm &d, int g, int G) {
 // *cur - 1) gets the picked state too.  ss.defer (a refine launch follows in the same chunk):
 // the pick rides in that launch instead (DevPick), one launch fewer per frame.  While
 // profiling, an event pair brackets the exchange (HPE_PROF_EXCHANGE).
-static bool subswarm_active(const hpe_ctx *c) { return c->ss.comm && c->ss.on; }
+// With the scripted transport a one-wave kernel stands where the all-gather does: it copies
+// the peers' rows of the script frame the device exchange counter names (k_script_rows).
+static bool subswarm_active(const hpe_ctx *c) { return c->ss.transport() && c->ss.on; }
 static double *subswarm_out(hpe_ctx *c, double *d_state) {
     return subswarm_active(c) ? c->ss.d_gath + (size_t)c->ss.rank * (HPE_DOF + 1) : d_state;
 }
 static int subswarm_exchange(hpe_ctx *c, double *d_state, double *hist, const int *cur) {
     if (!subswarm_active(c)) return HPE_OK;
-    const RcclApi &api = rccl_api();
     hpe_ctx::Pool &pl = c->pools[HPE_PROF_EXCHANGE];
     const bool timed = c->prof && pl.used + 2 <= pl.ev.size();
     if (timed) HIPCHK(c, hipEventRecord(pl.ev[pl.used], c->stream));
-    double *row = c->ss.d_gath + (size_t)c->ss.rank * (HPE_DOF + 1);
-    const ncclResult_t r = api.all_gather(row, c->ss.d_gath, HPE_DOF + 1, ncclFloat64,
-                                          c->ss.comm, c->stream);
-    if (r != ncclSuccess)
-        return fail(c, HPE_E_HIP, "subswarm all-gather: %s", api.error_string(r));
+    if (c->ss.comm) {
+        const RcclApi &api = rccl_api();
+        double *row = c->ss.d_gath + (size_t)c->ss.rank * (HPE_DOF + 1);
+        const ncclResult_t r = api.all_gather(row, c->ss.d_gath, HPE_DOF + 1, ncclFloat64,
+                                              c->ss.comm, c->stream);
+        if (r != ncclSuccess)
+            return fail(c, HPE_E_HIP, "subswarm all-gather: %s", api.error_string(r));
+    } else {
+        hipLaunchKernelGGL(k_script_rows, dim3(1), dim3(64), 0, c->stream,
+                           (const double *)c->ss.d_script, c->ss.script_frames, c->ss.nranks,
+                           c->ss.rank, c->ss.d_script_k, c->ss.d_gath);
+        HIPCHK(c, hipGetLastError());
+    }
     if (c->ss.defer) {
         c->ss.pick = DevPick{c->ss.d_gath, hist, cur, c->ss.nranks};
         c->ss.pending = true;
@@ -832,6 +847,8 @@ int hpe_destroy(hpe_ctx *c) {
     drop_graphs(c);  // before the communicator their exchange nodes use
     if (c->ss.comm) (void)rccl_api().comm_destroy(c->ss.comm);
     dfree(c->ss.d_gath);
+    dfree(c->ss.d_script);
+    dfree(c->ss.d_script_k);
     free_swarm(c->sw);
     free_opt(c->opt);
     dfree(c->d_hand);
@@ -1486,16 +1503,63 @@ int hpe_subswarm_unique_id(unsigned char id_out[HPE_SUBSWARM_ID_BYTES]) {
 
 int hpe_subswarm_fini(hpe_ctx *c) {
     if (!c) return HPE_E_ARG;
-    if (!c->ss.comm) return HPE_OK;
+    if (!c->ss.transport()) return HPE_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    drop_graphs(c);  // graphs holding the exchange go before the communicator
-    const ncclResult_t r = rccl_api().comm_destroy(c->ss.comm);
+    drop_graphs(c);  // graphs holding the exchange go before the communicator / the script
+    const ncclResult_t r = c->ss.comm ? rccl_api().comm_destroy(c->ss.comm) : ncclSuccess;
     c->ss.comm = nullptr;
+    dfree(c->ss.d_script);
+    dfree(c->ss.d_script_k);
+    c->ss.script_frames = 0;
     c->ss.on = false;
     c->ss.nranks = 0;
     dfree(c->ss.d_gath);
     ++c->epoch;  // the captured tracking graphs hold the exchange
     if (r != ncclSuccess) return fail(c, HPE_E_HIP, "ncclCommDestroy: %s", rccl_api().error_string(r));
+    return HPE_OK;
+}
+
+int hpe_subswarm_init_scripted(hpe_ctx *c, int nranks, int rank, const double *script, int frames) {
+    if (!c) return HPE_E_ARG;
+    if (!script || nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks || frames < 1)
+        return fail(c, HPE_E_ARG, "subswarm_init_scripted: null script, %d frames, or rank %d of "
+                                  "%d outside [0, %d), world 1..64", frames, rank, nranks, nranks);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t rows = (size_t)nranks * (HPE_DOF + 1), n = (size_t)frames * rows;
+    // a script of the live one's shape: new contents into the same buffers (the captured
+    // graphs read them at replay); anything else is a new transport
+    const bool same = c->ss.d_script && !c->ss.comm && c->ss.on && c->ss.nranks == nranks &&
+                      c->ss.rank == rank && c->ss.script_frames == frames;
+    if (same) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+        int rc = hpe_subswarm_fini(c);
+        if (rc) return rc;
+        double *gath = nullptr, *scr = nullptr;
+        int *k = nullptr;
+        if (dalloc(&gath, rows) != hipSuccess || dalloc(&scr, n) != hipSuccess ||
+            dalloc(&k, (size_t)1) != hipSuccess) {
+            dfree(gath);
+            dfree(scr);
+            dfree(k);
+            (void)hipGetLastError();
+            return fail(c, HPE_E_HIP, "subswarm_init_scripted: no device memory for %d frames", frames);
+        }
+        c->ss.d_gath = gath;
+        c->ss.d_script = scr;
+        c->ss.d_script_k = k;
+        c->ss.script_frames = frames;
+        c->ss.nranks = nranks;
+        c->ss.rank = rank;
+        c->ss.on = true;
+        c->ss.graphs = true;
+        c->ss.note[0] = 0;
+        ++c->epoch;
+    }
+    c->ss.pending = false;
+    HIPCHK(c, hipMemcpy(c->ss.d_script, script, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(c->ss.d_script_k, 0, sizeof(int)));  // rewound
+    HIPCHK(c, hipMemset(c->ss.d_gath, 0xFF, sizeof(double) * rows));  // NaN
     return HPE_OK;
 }
 
@@ -1548,7 +1612,7 @@ int hpe_subswarm_init(hpe_ctx *c, const unsigned char id[HPE_SUBSWARM_ID_BYTES],
 int hpe_subswarm_enable(hpe_ctx *c, int on) {
     if (!c) return HPE_E_ARG;
     if (on < 0 || on > 2) return fail(c, HPE_E_ARG, "subswarm_enable: mode %d not in 0..2", on);
-    if (!c->ss.comm) return fail(c, HPE_E_STATE, "hpe_subswarm_init not called");
+    if (!c->ss.transport()) return fail(c, HPE_E_STATE, "hpe_subswarm_init not called");
     if (c->ss.on != (on != 0)) {
         c->ss.on = on != 0;
         ++c->epoch;  // the captured tracking graphs hold the exchange (or not)
@@ -1561,16 +1625,17 @@ int hpe_subswarm_enable(hpe_ctx *c, int on) {
 int hpe_subswarm_info(hpe_ctx *c, int32_t *nranks, int32_t *rank, int32_t *version,
                       int32_t *in_graphs, double *gathered_out) {
     if (!c) return HPE_E_ARG;
-    if (in_graphs) *in_graphs = (c->ss.comm && c->ss.graphs) ? 1 : 0;
-    if (nranks) *nranks = c->ss.comm ? c->ss.nranks : 0;
-    if (rank) *rank = c->ss.comm ? c->ss.rank : 0;
+    const bool set = c->ss.transport();
+    if (in_graphs) *in_graphs = (set && c->ss.graphs) ? 1 : 0;
+    if (nranks) *nranks = set ? c->ss.nranks : 0;
+    if (rank) *rank = set ? c->ss.rank : 0;
     if (version) {
         *version = 0;
         const RcclApi &api = rccl_api();
         int v = 0;
         if (api.ok && api.get_version(&v) == ncclSuccess) *version = v;
     }
-    if (gathered_out && c->ss.comm) {
+    if (gathered_out && set) {
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipMemcpy(gathered_out, c->ss.d_gath, sizeof(double) * c->ss.nranks * (HPE_DOF + 1),

@@ -821,6 +821,24 @@ __global__ __launch_bounds__(64) void k_pick_best(const double *__restrict__ gat
     pick_apply(gathered, pick_best_row(gathered, world, l), l, state, hist, cur);
 }
 
+// The scripted transport of the subswarm exchange (hpe_subswarm_init_scripted), in the place
+// of the all-gather: rows w != rank of script frame *k ([frames][world][27]) into the gather
+// buffer; row `rank` (the frame's own result, k_pso_final's) is never written.  *k is the
+// device-resident exchange counter, advanced here (past the last frame: back to 0), so a
+// replayed chunk graph reads the script frame of its own exchange.  One wave.
+__global__ __launch_bounds__(64) void k_script_rows(const double *__restrict__ script, int frames,
+                                                    int world, int rank, int *__restrict__ k,
+                                                    double *__restrict__ gathered) {
+    const int l = threadIdx.x;
+    int f = __builtin_amdgcn_readfirstlane(*k);  // every lane, before lane 0's store below
+    if (f < 0 || f >= frames) f = 0;
+    const int n = world * (HPE_DOF + 1);
+    const double *__restrict__ src = script + (size_t)f * n;
+    for (int i = l; i < n; i += 64)
+        if (i / (HPE_DOF + 1) != rank) gathered[i] = src[i];
+    if (l == 0) *k = f + 1 < frames ? f + 1 : 0;
+}
+
 // u64 wave helpers of k_pso_final's replay: lane l - 1's value (lane 0: fill), the
 // inclusive prefix minimum over lanes 0..l (DPP row_shr 1/2/4/8, row_bcast 15/31; lanes
 // without a source keep the identity, all ones), a lane's value in every lane.

@@ -156,6 +156,18 @@ class Context:
         b = (C.c_ubyte * _lib.SUBSWARM_ID_BYTES).from_buffer_copy(bytes(uid))
         self.check(self.lib.hpe_subswarm_init(self._h, b, int(nranks), int(rank)))
 
+    def subswarm_init_scripted(self, script, rank: int):
+        """The exchange over a scripted transport, which communicates with nobody (one GPU,
+        one process, no RCCL): script is a (frames, nranks, 27) float64 array, and exchange k
+        puts rows w != rank of script[k] where the all-gather would have put the peers'
+        {bestp, cost}.  Loading a script of the live one's shape rewinds the exchange counter
+        and keeps the captured graphs."""
+        s = np.ascontiguousarray(script, dtype=np.float64)
+        if s.ndim != 3 or s.shape[2] != 27:
+            raise ValueError("script must be a (frames, nranks, 27) array")
+        self.check(self.lib.hpe_subswarm_init_scripted(self._h, int(s.shape[1]), int(rank),
+                                                       ptr(s, C.c_double), int(s.shape[0])))
+
     def subswarm_enable(self, on, direct=False):
         """Suspend (False) / resume (True) the exchange; direct=True resumes it with direct
         launches instead of captured graphs (the library's own fallback form)."""

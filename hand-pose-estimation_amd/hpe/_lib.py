@@ -73,6 +73,7 @@ SIGNATURES = {
     "hpe_pick_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "hpe_subswarm_unique_id": (C.c_int, [C.c_void_p]),
     "hpe_subswarm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "hpe_subswarm_init_scripted": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp, C.c_int]),
     "hpe_subswarm_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_subswarm_fini": (C.c_int, [C.c_void_p]),
     "hpe_subswarm_info": (C.c_int, [C.c_void_p, ip, ip, ip, ip, dp]),

@@ -188,6 +188,25 @@ int hpe_subswarm_fini(hpe_ctx *ctx);
 int hpe_subswarm_info(hpe_ctx *ctx, int32_t *nranks, int32_t *rank, int32_t *version,
                       int32_t *in_graphs, double *gathered_out);
 
+/* The scripted transport of the same exchange.  It communicates with NOBODY: it exists so
+ * that the N-rank device path (the final kernel writing gather row `rank`, the pick over
+ * several rows inside the next refine launch and at a chunk's end, the history row) can be
+ * executed and checked on one GPU, in one process, with no communicator and without RCCL.
+ * script is host memory, frames x nranks x 27 doubles ({bestp, cost} per rank and exchange);
+ * the library copies it to device memory of its own.  Where hpe_subswarm_init's exchange
+ * calls the all-gather, a one-wave kernel on hpe_stream(ctx) copies rows w != rank of
+ * script[k] into the gather buffer (row `rank` stays the frame's own result) and advances k,
+ * a device-resident exchange counter: a replayed chunk graph reads the script frame of its
+ * own exchange; past the last frame k wraps to 0.  Everything after "the gather buffer holds
+ * nranks rows" is the RCCL transport's own code, and hpe_subswarm_enable / _info / _fini act
+ * on either transport.  Calling it again on a context whose live scripted transport has the
+ * same nranks, rank and frames (exchange not suspended) loads the new contents and rewinds
+ * k, and the captured tracking graphs keep serving; any other call replaces the live
+ * transport (either kind), as hpe_subswarm_init does.  The gather buffer is NaN afterwards.
+ * HPE_E_ARG: null ctx or script, nranks outside 1..64, rank outside [0, nranks), frames < 1. */
+int hpe_subswarm_init_scripted(hpe_ctx *ctx, int nranks, int rank, const double *script,
+                               int frames);
+
 /* Opt-in per-generation exchange between subswarms (ICP-PSO style; NOT the reference's
  * algorithm, whose gbest never enters the velocity, PSO.cpp:824-832).  every > 0: after
  * every `every`-th generation g < maxiter-1 of each pso_evolve of this context (standalone

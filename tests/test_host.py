@@ -73,6 +73,15 @@ def test_errors_fail_loudly(lib):
     assert lib.hpe_subswarm_fini(None) == _lib.HPE_E_ARG
     assert lib.hpe_subswarm_info(None, None, None, None, None, None) == _lib.HPE_E_ARG
     assert lib.hpe_pick_best(None, None, 2, None) == _lib.HPE_E_ARG
+    # the scripted transport's entry: null ctx with a good script, and (still without a
+    # context, so nothing is touched) a bad world, a bad rank, frames = 0 and a null script;
+    # the same argument errors on a live context: tests/test_gpu_subswarm_world.py
+    scr = np.zeros((2, 2, 27))
+    sp = scr.ctypes.data_as(_lib.dp)
+    assert lib.hpe_subswarm_init_scripted(None, 2, 0, sp, 2) == _lib.HPE_E_ARG
+    for nranks, rank, s, frames in ((0, 0, sp, 2), (65, 0, sp, 2), (2, 2, sp, 2), (2, -1, sp, 2),
+                                    (2, 0, sp, 0), (2, 0, None, 2)):
+        assert lib.hpe_subswarm_init_scripted(None, nranks, rank, s, frames) == _lib.HPE_E_ARG
     import hpe
     with pytest.raises(hpe.HpeError):
         hpe.Context(p, device=10 ** 6)
