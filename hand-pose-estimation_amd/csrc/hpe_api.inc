@@ -49,6 +49,12 @@ struct Swarm {
     Sig *sig = nullptr;
     int *outl = nullptr;
     std::vector<InboxCounts> kin;  // per generation 0..G (P <= KIN_MAX)
+    // hpe_track_batch_dev: the mutable arrays (xh, pch, pb, v, inbox, gmin, sig, gpos) of
+    // `lanes` lanes, one arena per lane `stride` bytes apart; off[]: the arrays within an arena.
+    // The arrays above stay the single-sequence calls' own (their cached graphs keep them).
+    char *arena = nullptr;
+    size_t stride = 0, off[8] = {0};
+    int lanes = 0;
 };
 
 // RCCL entry points of the library's own subswarm exchange (hpe_subswarm_init), opened at
@@ -185,6 +191,7 @@ struct hpe_ctx {
     struct SeqGraph {
         int P, G, refine, k;
         unsigned staged;
+        unsigned filt;  // bit i: frame i's cloud bound is above HPE_NT / 2 (launch_pso's FILT forms)
         double *state, *hist;
         uint64_t seed;
         unsigned epoch;
@@ -202,6 +209,21 @@ struct hpe_ctx {
         hipGraphExec_t exec;
     };
     std::vector<RawGraph> rgraphs;
+    // batched lanes (hpe_track_batch_dev): per lane the current-frame descriptor the chunk
+    // graphs read, the cursor {slot, history row} and the refine evaluation counter
+    DevObs *d_bobs = nullptr;  // [HPE_BATCH_MAX]
+    int *d_bcur = nullptr;     // [HPE_BATCH_MAX][2]
+    int *d_bevals = nullptr;   // [HPE_BATCH_MAX][HPE_EVALS_N]
+    struct BatchGraph {
+        int P, G, refine, k;
+        unsigned filt;  // bit i: frame i of the chunk takes the FILT kernels
+        int B;
+        double *states, *hist;
+        uint64_t seed;
+        unsigned epoch;
+        hipGraphExec_t exec;
+    };
+    std::vector<BatchGraph> bgraphs;
     hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
     bool pipe_counting = false;  // set while a pipelined frame is enqueued (k_pso_final args)
@@ -392,6 +414,8 @@ static void free_swarm(Swarm &s) {
     dfree(s.sig);
     dfree(s.outl);
     dfree(s.ibtc);
+    dfree(s.arena);
+    s.lanes = 0;
     s.P = 0;
     s.G = -1;
 }
@@ -412,10 +436,42 @@ static void free_opt(OptState &s) {
     s.n_cap = 0;
 }
 
-// Swarm buffers + draw tables for (P, G, seed); rebuilt only when one changes.
-static int ensure_swarm(hpe_ctx *c, int P, int G) {
+// The lane arenas of a batch call (Swarm::arena): grown, never shrunk, with the epoch bumped
+// so that batch graphs holding the old arenas are dropped.
+static int ensure_lanes(hpe_ctx *c, int lanes) {
     Swarm &s = c->sw;
-    if (s.P == P && s.G == G && s.seed == c->seed) return HPE_OK;
+    if (lanes <= s.lanes) return HPE_OK;
+    ++c->epoch;
+    dfree(s.arena);
+    s.lanes = 0;
+    const size_t n = (size_t)s.P * HPE_DOF, G1 = (size_t)s.G + 1;
+    const size_t bytes[8] = {sizeof(double) * G1 * n,                                      // xh
+                             sizeof(double) * G1 * s.P,                                    // pch
+                             sizeof(double) * n,                                           // pb
+                             sizeof(double) * n,                                           // v
+                             sizeof(double) * 4 * s.P * s.K * IB_STRIDE,                   // inbox
+                             sizeof(unsigned long long) * G1 * GMIN_SHARDS * GMIN_STRIDE,  // gmin
+                             sizeof(Sig) * G1,                                             // sig
+                             sizeof(double) * HPE_DOF};                                    // gpos
+    size_t at = 0;
+    for (int k = 0; k < 8; ++k) {  // every array on a 256-byte boundary, as hipMalloc gives
+        s.off[k] = at;
+        at += (bytes[k] + 255) & ~(size_t)255;
+    }
+    s.stride = at;
+    HIPCHK(c, dalloc(&s.arena, s.stride * lanes));
+    // empty inbox slots (tag -1) and unwritten gmin cells are all-ones; the rest is written
+    // before it is read
+    HIPCHK(c, hipMemset(s.arena, 0xFF, s.stride * lanes));
+    s.lanes = lanes;
+    return HPE_OK;
+}
+
+// Swarm buffers + draw tables for (P, G, seed); rebuilt only when one changes.  lanes > 0
+// (hpe_track_batch_dev): also that many lane arenas.
+static int ensure_swarm(hpe_ctx *c, int P, int G, int lanes = 0) {
+    Swarm &s = c->sw;
+    if (s.P == P && s.G == G && s.seed == c->seed) return ensure_lanes(c, lanes);
     ++c->epoch;
     free_swarm(s);
     if (G > 32767) return fail(c, HPE_E_ARG, "maxiter %d too large", G + 1);
@@ -464,7 +520,7 @@ static int ensure_swarm(hpe_ctx *c, int P, int G) {
     s.K = K;
     s.seed = c->seed;
     c->bounds_dirty = true;
-    return HPE_OK;
+    return ensure_lanes(c, lanes);
 }
 
 static DevSwarm dev_swarm(hpe_ctx *c) {
@@ -490,6 +546,25 @@ static DevSwarm dev_swarm(hpe_ctx *c) {
     d.P = s.P;
     d.G = s.G;
     d.K = s.K;
+    return d;
+}
+
+// Lane 0 of the batch arenas (the kernels add blockIdx.y * stride); the tables every lane
+// shares come from the swarm.  No trace (hpe_pso_trace is not updated), no exchange.
+static DevSwarm batch_swarm(hpe_ctx *c) {
+    Swarm &s = c->sw;
+    DevSwarm d = dev_swarm(c);
+    d.xh = (double *)(s.arena + s.off[0]);
+    d.pch = (double *)(s.arena + s.off[1]);
+    d.pb = (double *)(s.arena + s.off[2]);
+    d.v = (double *)(s.arena + s.off[3]);
+    d.inbox = (double *)(s.arena + s.off[4]);
+    d.gmin = (unsigned long long *)(s.arena + s.off[5]);
+    d.sig = (Sig *)(s.arena + s.off[6]);
+    d.gpos = (double *)(s.arena + s.off[7]);
+    d.trace_g = nullptr;
+    d.trace_count = d.trace_topo = nullptr;
+    d.ext = nullptr;
     return d;
 }
 
@@ -825,6 +900,8 @@ static void drop_graphs(hpe_ctx *c) {
     for (auto &ge : c->pgraphs) (void)hipGraphExecDestroy(ge.exec);
     for (auto &sg : c->sgraphs) (void)hipGraphExecDestroy(sg.exec);
     for (auto &rg : c->rgraphs) (void)hipGraphExecDestroy(rg.exec);
+    for (auto &bg : c->bgraphs) (void)hipGraphExecDestroy(bg.exec);
+    c->bgraphs.clear();
     c->pgraphs.clear();
     c->sgraphs.clear();
     c->rgraphs.clear();
@@ -869,6 +946,9 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->d_obs_active);
     dfree(c->d_seq_obs);
     dfree(c->d_seq_cur);
+    dfree(c->d_bobs);
+    dfree(c->d_bcur);
+    dfree(c->d_bevals);
     dfree(c->d_raw);
     dfree(c->d_tmp);
     dfree(c->d_ctb);
@@ -1925,13 +2005,15 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
             if ((rc = enqueue_seq_chunk(c, P, refine, d_state, slot0, k, hist))) return rc;
             continue;
         }
-        unsigned staged = 0;
-        for (int i = 0; i < k; ++i)
+        unsigned staged = 0, filt = 0;
+        for (int i = 0; i < k; ++i) {
             if (c->slots[slot0 + i].n_max <= RF_STAGE_MAX) staged |= 1u << i;
+            if (c->slots[slot0 + i].n_max > HPE_NT / 2) filt |= 1u << i;
+        }
         hipGraphExec_t exec = nullptr;
         for (auto &sg : c->sgraphs)  // keyed by the chunk's shape, not its slots
             if (sg.P == P && sg.G == G && sg.refine == refine && sg.k == k &&
-                sg.staged == staged && sg.state == d_state && sg.hist == hist &&
+                sg.staged == staged && sg.filt == filt && sg.state == d_state && sg.hist == hist &&
                 sg.seed == c->seed && sg.epoch == c->epoch)
                 exec = sg.exec;
         if (!exec) {
@@ -1966,12 +2048,166 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
                 for (auto &sg : c->sgraphs) (void)hipGraphExecDestroy(sg.exec);
                 c->sgraphs.clear();
             }
-            c->sgraphs.push_back({P, G, refine, k, staged, d_state, hist, c->seed, c->epoch, exec});
+            c->sgraphs.push_back({P, G, refine, k, staged, filt, d_state, hist, c->seed, c->epoch, exec});
         }
         HIPCHK(c, hipGraphLaunch(exec, c->stream));
     }
     // the last frame's descriptor is the selected one now (handed back by its final kernel)
     c->cur = first_slot + n - 1;
+    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
+    c->seq_done_valid = true;
+    return HPE_OK;
+}
+
+// k frames of B lanes, one after the other on the tracking stream: per frame the launches of
+// enqueue_seq_chunk with a lane dimension -- refine on grid (1, B), init and the generations
+// on (P, B), the final kernel on (1, B) -- each lane on its own descriptor d_bobs[b], cursor
+// d_bcur[2 b] and arena.  filt: bit i = frame i takes the FILT kernels (all lanes agree).
+static int enqueue_batch_chunk(hpe_ctx *c, int P, int refine, int B, double *d_states, unsigned filt,
+                               int k, double *hist) {
+    const DevSwarm d = batch_swarm(c);
+    const size_t stride = c->sw.stride;
+    const int G = d.G;
+    const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
+    static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
+    const bool r16 = d.K <= 15;
+    const DevObs *obs = c->d_bobs;
+    const DevHand *hand = c->d_hand;
+    for (int i = 0; i < k; ++i) {
+        const bool f = (filt >> i) & 1u;
+        if (refine)  // testmodel.cpp:126; the CU-filling LDS size puts the lanes on B CUs
+            launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
+                   dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals);
+        launch(c, HPE_PROF_PSO_INIT, f ? k_pso_init_b<true> : k_pso_init_b<false>, dim3(P, B),
+               dim3(HPE_NT), 0, d, stride, (const double *)d_states, obs, hand);
+        for (int g = 1; g <= G; ++g) {
+            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
+            launch(c, HPE_PROF_PSO_GEN,
+                   f ? (r16 ? k_pso_gen_b<true, true> : k_pso_gen_b<false, true>)
+                     : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
+                   dim3(P, B), dim3(HPE_NT), 0, d, stride, obs, hand, g, W1, C1, C2, kg);
+        }
+        launch(c, HPE_PROF_PSO_FINAL, f ? k_pso_final_b<true> : k_pso_final_b<false>, dim3(1, B),
+               dim3(HPE_NT), 0, d, stride, d_states, c->d_bobs, hand, (DevObs *)nullptr, 1,
+               (unsigned long long *)nullptr, (unsigned long long *)nullptr, hist,
+               (const int *)nullptr, (const DevObs *)c->d_obs, c->d_bcur);
+        HIPCHK(c, hipGetLastError());
+    }
+    return HPE_OK;
+}
+
+int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                        const int32_t *first_slots, int n, int frames_per_graph, double *d_hist) {
+    if (!c) return HPE_E_ARG;
+    if (int erc = mw_check_async(c)) return erc;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!d_states || !first_slots) return fail(c, HPE_E_ARG, "null device states or first slots");
+    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
+    int rc = check_P(c, P);
+    if (rc) return rc;
+    if (pso_wave_form(c, P))
+        return fail(c, HPE_E_ARG, "num_p %d takes the wave form: a batch needs the workgroup form "
+                    "(num_p < %d)", P, c->wave_form_min_p);
+    if (c->ss.transport())
+        return fail(c, HPE_E_STATE, "a subswarm transport is live: a batch runs without the "
+                    "exchange (hpe_subswarm_fini)");
+    if (c->xch_every > 0)
+        return fail(c, HPE_E_STATE, "the per-generation exchange is on (hpe_set_exchange)");
+    if (frames_per_graph < 0 || frames_per_graph > HPE_SEQ_MAX_CHUNK)
+        return fail(c, HPE_E_ARG, "frames_per_graph %d out of range [0, %d]", frames_per_graph,
+                    HPE_SEQ_MAX_CHUNK);
+    if (n < 1) return fail(c, HPE_E_ARG, "n = %d frames", n);
+    for (int b = 0; b < B; ++b) {
+        const int s0 = first_slots[b];
+        if (s0 < 0 || (long long)s0 + n > (long long)c->slots.size())
+            return fail(c, HPE_E_ARG, "lane %d: frames [%d, %lld) are not all stored slots", b, s0,
+                        (long long)s0 + n);
+        for (int f = 0; f < n; ++f) {
+            const Slot &s = c->slots[s0 + f];
+            if (!s.valid) return fail(c, HPE_E_ARG, "lane %d: slot %d holds no frame", b, s0 + f);
+            if (s.n_max > RF_STAGE_MAX)
+                return fail(c, HPE_E_ARG, "lane %d: slot %d holds up to %d points, a batch takes the "
+                            "single-workgroup refine (<= %d)", b, s0 + f, s.n_max, RF_STAGE_MAX);
+            if ((s.n_max > HPE_NT / 2) != (c->slots[first_slots[0] + f].n_max > HPE_NT / 2))
+                return fail(c, HPE_E_ARG, "frame %d: lanes 0 and %d disagree on clouds above %d "
+                            "points (one kernel form per launch)", f, b, HPE_NT / 2);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
+    if (!c->d_bobs) {
+        HIPCHK(c, dalloc(&c->d_bobs, HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&c->d_bcur, 2 * HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&c->d_bevals, HPE_BATCH_MAX * HPE_EVALS_N));
+        HIPCHK(c, hipMemset(c->d_bevals, 0, sizeof(int) * HPE_BATCH_MAX * HPE_EVALS_N));
+    }
+    if ((rc = ensure_swarm(c, P, G, B))) return rc;
+    if ((rc = upload_bounds(c))) return rc;
+    // frames prepared on the preprocessing stream: the tracking stream waits for the ones
+    // still running, once, before the first chunk
+    for (int b = 0; b < B; ++b)
+        for (int f = 0; f < n; ++f) {
+            Slot &s = c->slots[first_slots[b] + f];
+            if (s.dev && s.ready && hipEventQuery(s.ready) != hipSuccess)
+                HIPCHK(c, hipStreamWaitEvent(c->stream, s.ready, 0));
+        }
+    BatchFirst first{};
+    for (int b = 0; b < B; ++b) first.slot[b] = first_slots[b];
+    hipLaunchKernelGGL(k_seq_begin_b, dim3(1, B), dim3(64), 0, c->stream, (const DevObs *)c->d_obs,
+                       first, n, c->d_bobs, c->d_bcur);
+    HIPCHK(c, hipGetLastError());
+    const int K = frames_per_graph ? frames_per_graph : HPE_SEQ_CHUNK;
+    for (int f0 = 0; f0 < n; f0 += K) {
+        const int k = n - f0 < K ? n - f0 : K;
+        unsigned filt = 0;
+        for (int i = 0; i < k; ++i)
+            if (c->slots[first_slots[0] + f0 + i].n_max > HPE_NT / 2) filt |= 1u << i;
+        if (direct_launches(c)) {
+            if ((rc = enqueue_batch_chunk(c, P, refine, B, d_states, filt, k, d_hist))) return rc;
+            continue;
+        }
+        hipGraphExec_t exec = nullptr;
+        for (auto &bg : c->bgraphs)  // keyed by the chunk's shape, not its slots
+            if (bg.P == P && bg.G == G && bg.refine == refine && bg.k == k && bg.filt == filt &&
+                bg.B == B && bg.states == d_states && bg.hist == d_hist && bg.seed == c->seed &&
+                bg.epoch == c->epoch)
+                exec = bg.exec;
+        if (!exec) {
+            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+            ++c->captures;
+            bool direct = false;
+            if ((rc = end_capture(c, enqueue_batch_chunk(c, P, refine, B, d_states, filt, k, d_hist),
+                                  &exec, &direct)))
+                return rc;
+            if (direct) {  // end_capture's exchange fallback: a batch never holds the exchange
+                if ((rc = enqueue_batch_chunk(c, P, refine, B, d_states, filt, k, d_hist))) return rc;
+                continue;
+            }
+            // drop graphs of an older epoch or seed (one may still be in flight: wait first),
+            // and all of them at the cap, as hpe_track_sequence_dev does
+            bool stale = false;
+            for (auto &bg : c->bgraphs) stale |= bg.epoch != c->epoch || bg.seed != c->seed;
+            if (stale || c->bgraphs.size() >= 64) HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (size_t q = 0; q < c->bgraphs.size();) {
+                if (stale && (c->bgraphs[q].epoch != c->epoch || c->bgraphs[q].seed != c->seed)) {
+                    (void)hipGraphExecDestroy(c->bgraphs[q].exec);
+                    c->bgraphs[q] = c->bgraphs.back();
+                    c->bgraphs.pop_back();
+                } else {
+                    ++q;
+                }
+            }
+            if (c->bgraphs.size() >= 64) {
+                for (auto &bg : c->bgraphs) (void)hipGraphExecDestroy(bg.exec);
+                c->bgraphs.clear();
+            }
+            c->bgraphs.push_back({P, G, refine, k, filt, B, d_states, d_hist, c->seed, c->epoch, exec});
+        }
+        HIPCHK(c, hipGraphLaunch(exec, c->stream));
+    }
+    // the lanes' slots have this call as their last reader (hpe_prepare_frame waits for it)
     if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
     c->seq_done_valid = true;
@@ -2253,6 +2489,16 @@ int hpe_refine_eval_count(hpe_ctx *c, uint64_t *total, int reset) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     unsigned long long v = 0;
     HIPCHK(c, hipMemcpy(&v, c->d_evals + 2, sizeof(v), hipMemcpyDeviceToHost));
+    if (c->d_bevals) {  // the lanes of hpe_track_batch_dev count for themselves
+        int lanes[HPE_BATCH_MAX * HPE_EVALS_N];
+        HIPCHK(c, hipMemcpy(lanes, c->d_bevals, sizeof(lanes), hipMemcpyDeviceToHost));
+        for (int b = 0; b < HPE_BATCH_MAX; ++b) {
+            unsigned long long lv;
+            std::memcpy(&lv, lanes + HPE_EVALS_N * b + 2, sizeof(lv));
+            v += lv;
+        }
+        if (reset) HIPCHK(c, hipMemset(c->d_bevals, 0, sizeof(lanes)));
+    }
     *total = v;
     if (reset) HIPCHK(c, hipMemset(c->d_evals + 2, 0, sizeof(v)));
     return HPE_OK;

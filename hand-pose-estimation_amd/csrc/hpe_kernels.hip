@@ -892,213 +892,7 @@ __global__ __launch_bounds__(HPE_NT) void k_pso_final(DevSwarm sw, double *__res
                                                       const DevObs *__restrict__ seq_table = nullptr,
                                                       DevObs *seq_obs = nullptr,  // aliases og
                                                       int *__restrict__ seq_cur = nullptr) {
-    constexpr int CH = 2048;  // generations staged per pass
-    // offline sequences (hpe_track_sequence_dev): the frame's history row and slot come
-    // from the device cursor {slot, row}, and the next frame's descriptor is staged into the
-    // descriptor every kernel of the chunk graph reads -- the graph is independent of the
-    // slot range it tracks
-    int seq_slot = 0;
-    if (TAIL && seq_cur) {
-        seq_slot = seq_cur[0];
-        if (hist) hist += (size_t)(HPE_DOF + 1) * seq_cur[1];
-    }
-    // a timed-out multi-workgroup refine (DevMw::err, set until the host has reported it):
-    // this frame's result is undefined, so bestp and cost become NaN
-    const int failed = __builtin_amdgcn_readfirstlane(
-        (TAIL && fail) ? __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0);
-    __shared__ Smem sm;
-    __shared__ double gm[CH];
-    __shared__ int tp[CH];
-    const int t = threadIdx.x, G = sw.G, P = sw.P;
-    if (TAIL && seq_dev && t == HPE_NT - 64) {
-        // pipelined tracking: this frame's refine launch (and the preparation of the next
-        // frame inside it, which read a pinned host buffer) has completed; publish the
-        // frame's sequence number to the host, which polls it before reusing that buffer.
-        // Relaxed: the kernel boundary already retired those reads, and no store of this
-        // kernel needs publishing with it.  Wave 7, idle until the first barrier, takes the
-        // counter's load round trip instead of wave 0, which reads the gmin history.
-        const unsigned long long n = *seq_dev + 1;
-        *seq_dev = n;
-        __hip_atomic_store(done_host, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (TAIL) stage_hand<HPE_NT>(sm.hand, Hg);
-    // this frame's descriptor, read before the tail stages the next frame's into it (og IS
-    // seq_obs in sequence mode).  (A round-5 form staged the next descriptor after
-    // the tail's own evaluation, behind a barrier, and returned early before it on `failed`
-    // (a per-lane atomic load) and `same_eval && last >= 0` (`last` read from LDS): exits the
-    // compiler could not prove uniform, ahead of barriers -- undefined behaviour in the HIP
-    // barrier model, not a proven compiler bug.  On the box its same-eval frames came out
-    // with a re-evaluated cost (3.3e-7 relative off).  The cause was not isolated further;
-    // every such exit is now made provably uniform (readfirstlane).)
-    DevObs o_early{};
-    if (TAIL) o_early = *og;
-    // the frame descriptor handed back at the end, loaded now (off the final chain)
-    const unsigned long long obs_word =
-        (TAIL && obs_out && t < (int)(sizeof(DevObs) / 8)) ? ((const unsigned long long *)og)[t] : 0ull;
-    double bp = 0.0;  // gbest_pos = zeros<vec> (PSO.cpp:739) if nothing beat 1e100
-    double gcost = 1e100;
-    int last = -1, count = 100;
-    if (G <= 63) {
-        // G + 1 <= 64 generations: the replay as scans over wave 0's lanes (lane k =
-        // generation k), not a serial loop.  Costs are >= 0 or NaN, so their u64 bits
-        // order like their values and NaN bits (never written, or all NaN) sort above
-        // every cost: a u64 minimum is fmin, and "fm < gcost" is a u64 compare.
-        if (t < 64) {
-            unsigned long long key = ~0ull;
-            if (t <= G) {
-                double m = __builtin_nan("");
-                for (int c = 0; c < GMIN_SHARDS; ++c) m = fmin(m, bits_to_f64(*gmin_cell(sw, t, c)));
-                key = f64_to_bits(m);
-            }
-            const int topo = (t >= 1 && t <= G) ? sw.sig[t].topo : -1;
-            const unsigned long long cap = f64_to_bits(1e100);  // gbest starts at 1e100
-            const unsigned long long incl = wave_prefix_min_u64(key);
-            const unsigned long long excl = min(from_left_u64(incl, ~0ull), cap);
-            const bool imp = t >= 1 && t <= G && key < excl;  // PSO.cpp:864-872
-            const unsigned long long mask = __ballot(imp);
-            const int last0 = (readlane_u64(key, 0) < cap) ? 0 : -1;  // generation 0 (:755-760)
-            last = mask ? 63 - __builtin_clzll(mask) : last0;
-            if (t >= 1 && t <= G && sw.trace_g) {
-                // count after generation t: 0 at an improvement, +1 otherwise, from 100
-                const unsigned long long upto = mask & ((2ull << t) - 1);
-                const int L = upto ? 63 - __builtin_clzll(upto) : 0;
-                sw.trace_g[t - 1] = bits_to_f64(min(incl, cap));
-                sw.trace_count[t - 1] = L >= 1 ? t - L : 100 + t;
-                sw.trace_topo[t - 1] = topo;
-            }
-            if (t == 0) {
-                sm.iscal[2] = last;
-                sm.dscal[5] = bits_to_f64(min(readlane_u64(incl, G), cap));
-            }
-        }
-    }
-    for (int base = 0; G > 63 && base <= G; base += CH) {
-        // all loads of the pass at once, then a serial replay from LDS by thread 0
-        for (int k = t; k < CH && base + k <= G; k += HPE_NT) {
-            double m = __builtin_nan("");  // all-ones (never written) is a NaN too
-            for (int c = 0; c < GMIN_SHARDS; ++c)
-                m = fmin(m, bits_to_f64(*gmin_cell(sw, base + k, c)));
-            gm[k] = m;
-            tp[k] = (base + k >= 1) ? sw.sig[base + k].topo : -1;
-        }
-        __syncthreads();
-        if (t == 0) {
-            const int n = (G - base + 1) < CH ? (G - base + 1) : CH;
-            for (int k = 0; k < n; ++k) {
-                const int g = base + k;
-                const double fm = gm[k];
-                if (g == 0) {
-                    if (fm < gcost) {
-                        gcost = fm;
-                        last = 0;
-                    }
-                    continue;
-                }
-                if (fm < gcost) {
-                    gcost = fm;
-                    count = 0;
-                    last = g;
-                } else {
-                    count += 1;
-                }
-                if (sw.trace_g) {
-                    sw.trace_g[g - 1] = gcost;
-                    sw.trace_count[g - 1] = count;
-                    sw.trace_topo[g - 1] = tp[k];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (G > 63 && t == 0) {
-        sm.iscal[2] = last;
-        sm.dscal[5] = gcost;
-    }
-    __syncthreads();
-    last = __builtin_amdgcn_readfirstlane(sm.iscal[2]);  // decides the exit below (§7)
-    gcost = sm.dscal[5];
-    if (last >= 0 && P <= HPE_NT) {
-        // one particle per thread: its pbest cost and its position row of generation
-        // `last` in one round trip; the winner's thread writes bestp
-        const int k = t < P ? t : P - 1;
-        const double *row = sw.xh + ((size_t)last * P + k) * HPE_DOF;
-        double r[HPE_DOF];
-#pragma unroll
-        for (int d = 0; d < HPE_DOF; ++d) r[d] = row[d];
-        VI mine = {t < P ? nan_inf(sw.pch[(size_t)last * P + k]) : __builtin_inf(), t < P ? t : 0};
-        const VI b = block_argmin(sm, mine);
-        if (t == b.i) {
-#pragma unroll
-            for (int d = 0; d < HPE_DOF; ++d) {
-                out[d] = r[d];
-                sw.gpos[d] = r[d];
-                if (hist) hist[d] = r[d];
-            }
-        }
-        if (TAIL && !same_eval) {  // the tail below evaluates cal_cost(bestp)
-            if (t == b.i) {
-#pragma unroll
-                for (int d = 0; d < HPE_DOF; ++d) sm.pbr[d] = r[d];
-            }
-            __syncthreads();
-            if (t < HPE_DOF) bp = sm.pbr[t];
-        }
-    } else {
-        if (last >= 0) {
-            const double *pc = sw.pch + (size_t)last * P;
-            VI mine = {__builtin_inf(), 0};
-            for (int k = t; k < P; k += HPE_NT) {
-                const double v = nan_inf(pc[k]);
-                if (v < mine.v) {
-                    mine.v = v;
-                    mine.i = k;
-                }
-            }
-            const VI b = block_argmin(sm, mine);
-            if (t < HPE_DOF) bp = sw.xh[((size_t)last * P + b.i) * HPE_DOF + t];
-        }
-        // bestp stays in each thread's register: no barrier and no re-read of `out`
-        if (t < HPE_DOF) {
-            out[t] = bp;
-            sw.gpos[t] = bp;
-            if (hist) hist[t] = bp;
-        }
-    }
-    if (t == 0) {
-        out[HPE_DOF] = gcost;
-        if (hist) hist[HPE_DOF] = gcost;
-    }
-    for (int c = t; c < (G + 1) * GMIN_SHARDS; c += HPE_NT) sw.gmin[(size_t)c * GMIN_STRIDE] = ~0ull;
-    if (TAIL) {
-        if (obs_out && t < (int)(sizeof(DevObs) / 8)) ((unsigned long long *)obs_out)[t] = obs_word;
-        if (seq_cur) {
-            const int nx = seq_slot + 1 < HPE_MAX_SLOTS ? seq_slot + 1 : seq_slot;
-            if (seq_table && t < (int)(sizeof(DevObs) / 8))
-                ((unsigned long long *)seq_obs)[t] = ((const unsigned long long *)(seq_table + nx))[t];
-            if (t == 0) {
-                seq_cur[0] = seq_slot + 1;
-                seq_cur[1] = seq_cur[1] + 1;
-            }
-        }
-        if (failed) {
-            if (t <= HPE_DOF) {
-                out[t] = __builtin_nan("");
-                if (hist) hist[t] = __builtin_nan("");
-            }
-            return;
-        }
-        if (same_eval && last >= 0) return;  // out[26] = gcost = cal_cost(bestp)
-        const DevObs o = o_early;
-        if (t < HPE_DOF) sm.fk.th[t] = bp;
-        const CloudGlobal cv = obs_cloud(o);
-        const Pt pre = load_pt(cv, t);
-        __syncthreads();
-        const double c = eval_block<EV_COST, HPE_NT, true, FILT>(sm, o, cv, &sm.hand, nullptr, pre);
-        if (t == 0) {
-            out[HPE_DOF] = c;
-            if (hist) hist[HPE_DOF] = c;
-        }
-    }
+#include "hpe_final_body.inc"
 }
 
 // Start of an offline sequence (hpe_track_sequence_dev): the first frame's descriptor into
@@ -1585,257 +1379,106 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
                                                   int32_t *__restrict__ match_g,
                                                   int *__restrict__ evals_out, int do_refine,
                                                   PrepArgs pa, DevMw mw, DevPick pk) {
-    extern __shared__ __align__(16) unsigned char dyn[];  // staged cloud + matchId / prep
-    const int nhelp = MW ? mw.Q : 0;
-    if (MW && blockIdx.x >= 1 && (int)blockIdx.x <= nhelp) {
-        if (do_refine) mw_helper<RIGID>(mw, blockIdx.x - 1, og, Hg, match_g);
-        return;
-    }
-    if (blockIdx.x >= 1) {
-        const unsigned long long t0 = HPE_STAMPS ? __builtin_amdgcn_s_memtime() : 0;
-        prep_workgroup(pa, blockIdx.x - 1 - nhelp, dyn);
-        if (HPE_STAMPS && threadIdx.x == 0) {  // diagnostic build: prep workgroup spans
-            const int k = ((int)blockIdx.x - 1 - nhelp < PREP_BANDS) ? 24 : 25;
-            atomicAdd(&hpe_stamps[k], __builtin_amdgcn_s_memtime() - t0);
-            atomicAdd(&hpe_stamps[32 + k], 1ull);
-        }
-        return;
-    }
-    if (!do_refine) return;
-    const DevObs o = *og;  // the selected frame (device-resident: graph-stable args)
-    __shared__ RefineSm rs;
-    __shared__ DevHand hs;  // hand constants in LDS: keeps them out of the loop's registers
-    const int t = threadIdx.x, w = t >> 6, l = t & 63;
-    stage_hand<RF_NT>(hs, Hg);
-    const DevHand *__restrict__ H = &hs;
-    using CV = std::conditional_t<STAGED, CloudView, CloudGlobal>;
-    CV cv;
-    int32_t *match = match_g;
-    if (STAGED) {
-        double *cx = (double *)dyn, *cy = cx + o.n, *cz = cy + o.n;
-        for (int p = t; p < o.n; p += RF_NT) {
-            cx[p] = gp(o.cx)[p];
-            cy[p] = gp(o.cy)[p];
-            cz[p] = gp(o.cz)[p];
-        }
-        if constexpr (STAGED) cv = CV{cx, cy, cz, o.n};
-        match = (int32_t *)(cz + o.n);
-    }
-    if constexpr (!STAGED) cv = obs_cloud(o);
-    if (pk.gath) {
-        // the previous frame's subswarm exchange: x0 = the best all-gathered state (k_pick_best's
-        // rule), also stored to d_state and the previous frame's history row
-        if (w == 0) {
-            const double x = pick_apply(pk.gath, pick_best_row(pk.gath, pk.world, l), l, x0g,
-                                        pk.hist, pk.cur);
-            if (l < HPE_DOF) rs.x0[l] = x;
-        }
-    } else if (t < HPE_DOF) {
-        rs.x0[t] = x0g[t];
-    }
-    if (t == 0) rs.ts_n = 0;
-    REF_TS(rs.ts_n, 0);
-    __shared__ int mwflag;
-    MwLeader ml{mw, 0u, false};
-    __syncthreads();
-    if (RIGID) {
-        // hand-frame centres q (x0's digits, theta0 = -180, theta1..5 = 0: Tgb = I, u = 0)
-        // and the call's constant self-collision penalty
-        if (w == 0) {
-            const double xl = rs.x0[l < HPE_DOF ? l : 0];
-            const double thq = (l == 0) ? -180.0 : (l < 6) ? 0.0 : xl;
-            if (l < HPE_DOF) rs.w[0].th[l] = thq;
-            wave_sync();
-            SphXYZ own;
-            fk_wave<true>(rs.w[0], H, &own, &thq);
-            if (l < HPE_NS) {
-                rs.rg.q[l][0] = own.x;
-                rs.rg.q[l][1] = own.y * -1;
-                rs.rg.q[l][2] = own.z * -1;
-            }
-            CollPair cp[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) cp[k] = collide_load(rs.w[0], k < 2 ? l + 64 * k : ((l < 16) ? l + 128 : l), H);
-            double co = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double v = collide_value(cp[k], sqrt(collide_d2(cp[k])));
-                co += (k < 2 || l < 16) ? v : 0.0;
-            }
-            co = wave_sum(co);
-            if (l == 0) rs.rg.C = co;
-        }
-        __syncthreads();
-    }
-    StampClock sc;
-    sc.start();
-    int evals = 0;
-    bool base_valid = false;
-    const double e = 1e-5;  // cal_grad step (PSO.cpp:195)
-    // clouds of at most FP_MAX points: each lane keeps its frozen points in registers
-    const bool small = !MW && STAGED && o.n >= 1 && o.n <= FP_MAX;  // (N = 0: no point to clamp to)
-    FrozenPts fpts;
-    // the lane's sphere (lane l, clamped) off-image depth value, the same for every
-    // evaluation of the call (depth_finish's md * md, computed once)
-    const double md2_l = depth_off_sq(o, H->radii[l < HPE_NS ? l : HPE_NS - 1]);
-    for (int blk = 0; blk < 2; ++blk) {
-        const int lo = 3 * blk;  // start_idx (PSO.cpp:226-227); end_idx = lo + 2
-        // Block 2 moves only the global position u = x0[3..5]: every FK of the block is
-        // the stored rotation terms of x0 plus u (FK_TRANSLATE, bit-identical).
-        FkX *Xt = nullptr;
-        if (RIGID && blk == 1) {  // P = Rg q of the block's fixed rotation
-            if (w == 0) rigid_wave<RG_STORE_P>(rs.w[0], rs.rg, rs.x0[l < HPE_DOF ? l : 0], nullptr, rs.rg.P);
-            __syncthreads();
-        } else if (blk == 1) {
-            if (w == 0) {
-                if (l < HPE_DOF) rs.w[0].th[l] = rs.x0[l];
-                wave_sync();
-                fk_wave_t<FK_STORE_X, true>(rs.w[0], H, &rs.X);
-            }
-            __syncthreads();
-            Xt = &rs.X;
-        }
-        double tol = 1;
-        int cnt = 0, iter = 0;
-        while (tol > 1e-6 && iter < 15 && cnt < 1 && !(MW && ml.failed)) {
-            // f_k = cal_cost2(x0, matchId, true).  The spheres of x0 are already in rs.base
-            // when x0 is the accepted Goldstein point of the previous iteration
-            // (x0 + tk*p == x0 - tk*g bitwise) or an unchanged x0.
-            if (!base_valid) {
-                if (t < HPE_DOF) rs.base.th[t] = rs.x0[t];
-                __syncthreads();
-                if (w == 0) {
-                    if (RIGID) {
-                        const double thl = rs.x0[l < HPE_DOF ? l : 0];
-                        if (blk) rigid_wave<RG_TRANS>(rs.base, rs.rg, thl);
-                        else rigid_wave<RG_ROT>(rs.base, rs.rg, thl);
-                    } else if (Xt) {
-                        fk_wave_t<FK_TRANSLATE>(rs.base, H, Xt);
-                    } else {
-                        fk_wave<true>(rs.base, H);
-                    }
-                }
-                __syncthreads();
-            }
-            REF_TS(rs.ts_n, 1);
-            double fk;
-            if (MW) {
-                fk = eval_corr<MW, RIGID>(rs, o, cv, H, match, &ml, &mwflag);
-                REF_TS(rs.ts_n, 2);
-                // cal_grad: x0 +/- e along the 3 block dims, one wave per evaluation
-                if (w < 6) {
-                    const int d = lo + (w >> 1);
-                    if (l < HPE_DOF)
-                        rs.w[w].th[l] = (l == d) ? ((w & 1) ? rs.x0[l] - e : rs.x0[l] + e) : rs.x0[l];
-                }
-                eval_nodes<MW, RIGID>(rs, 6, o, cv, H, match, Xt, &ml, &mwflag, nullptr, nullptr, blk);
-            } else {
-                // f_k = cal_cost2(x0, matchId, true) and cal_grad's six frozen evaluations
-                // (x0 +/- e along the 3 block dims, one wave each) with one barrier between
-                // them: the search stores matchId, and while the slowest search waves and the
-                // corr sums finish, waves 0..5 already run the parts of their gradient point
-                // that need no matchId (FK, depth gathers, collision)
-                FrozenHead hd{};
-                auto head = [&]() {
-                    if (w < 6) {
-                        const int d = lo + (w >> 1);
-                        const double xl = rs.x0[l < HPE_DOF ? l : 0];
-                        const double thl = (l == d) ? ((w & 1) ? xl - e : xl + e) : xl;
-                        if (l < HPE_DOF) rs.w[w].th[l] = thl;
-                        wave_sync();
-                        if (RIGID) hd = blk ? rigid_head<RG_TRANS>(rs.w[w], o, H, rs.rg, thl)
-                                            : rigid_head<RG_ROT>(rs.w[w], o, H, rs.rg, thl);
-                        else hd = frozen_head<true>(rs.w[w], o, H, Xt, &thl);
-                    }
-                };
-                const DepthG dgc = depth_issue_w0(rs.base, o, H);
-                const bool young = w >= HPE_SETPRIO_FROM;  // as in eval_block
-                if (young) __builtin_amdgcn_s_setprio(1);
-                // (n <= 256) the items go where the SIMDs have room.  Chain form: waves 0..5
-                // also run a gradient point's head below (FK), two of them on SIMDs 0 and 1
-                // each, one on SIMDs 2 and 3; so waves 4, 5 search nothing and waves 6, 7 two
-                // items.  Hand-frame form (HPE_RF_SPREAD): the heads are short (no DH chain),
-                // so every wave takes one item and no wave searches twice.
-                double al;
-                if (small) {
-                    const bool spread = RIGID && HPE_RF_SPREAD;
-                    const int f0 = (w < 4 || spread) ? 64 * w : (w >= 6) ? 256 + 128 * (w - 6) : 0;
-                    const int cnt = (w < 4 || spread) ? 1 : (w >= 6) ? 2 : 0;
-                    al = search_align<RF_NT, true>(rs.base, cv, H, match, load_pt(cv, f0 + l),
-                                                   f0 + l, BT_GENS, 64, cnt);
-                } else {
-                    al = search_align<RF_NT, true>(rs.base, cv, H, match, load_pt(cv, t));
-                }
-                if (young) __builtin_amdgcn_s_setprio(0);
-                double co = (!RIGID && t < 144) ? collide_term(rs.base, t, H) : 0.0;
-                const double dep = depth_finish(dgc, o, t < HPE_NS);
-                const double tot = wave_sum((al * o.lambda + dep) + co);  // as block_sum1
-                if (l == 0) rs.red[w][0] = tot;
-                head();
-                __syncthreads();  // matchId complete, the corr partial sums in red
-                if (small) load_frozen_pts(fpts, cv, match, l);
-                fk = 0;
-#pragma unroll
-                for (int k = 0; k < RF_NW; ++k) fk += rs.red[k][0];
-                if (RIGID) fk = fk + rs.rg.C;
-                REF_TS(rs.ts_n, 2);
-                if (w < 6) {
-                    double f = RIGID ? frozen_tail<true>(rs.w[w], o, cv, H, match, hd,
-                                                         small ? &fpts : nullptr, &md2_l)
-                                     : frozen_tail(rs.w[w], o, cv, H, match, hd, small ? &fpts : nullptr);
-                    if (RIGID) f = f + rs.rg.C;
-                    if (l == 0) rs.fg[w] = f;
-                }
-                __syncthreads();
-            }
-            ++evals;
-            sc.lap(20);
-            evals += 6;
-            // cal_grad (PSO.cpp:197-212): g on the block dims, p = -1 * g, computed by every
-            // thread for its lane -- no barrier: fg is rewritten only by the next iteration's
-            // gradient points (the multi-workgroup form's rs.f by this search's first round,
-            // hence its barrier)
-            const double *fg = MW ? rs.f : rs.fg;
-            const double g0 = (fg[0] - fg[1]) / (2 * e), g1 = (fg[2] - fg[3]) / (2 * e),
-                         g2 = (fg[4] - fg[5]) / (2 * e);
-            const int dl = l - lo;
-            const double gl = (dl == 0) ? g0 : (dl == 1) ? g1 : (dl == 2) ? g2 : 0.0;
-            const double pl = -1 * gl;
-            if (MW) __syncthreads();
-            REF_TS(rs.ts_n, 3);
-            sc.lap(21);
-            // g'p by op_dot::direct_dot_arma (two accumulators: even / odd indices).  g is
-            // zero outside the block, and a zero term leaves an accumulator unchanged
-            // (x + -0 = x; the empty sums stay zero), so the sums reduce to the block's
-            // terms in the same order: block 0 (dims 0..2) v1 = g0 p0 + g2 p2, v2 = g1 p1;
-            // block 1 (dims 3..5) v1 = g4 p4, v2 = g3 p3 + g5 p5.  Same for |g|^2 (tol).
-            const double q0 = g0 * (-1 * g0), q1 = g1 * (-1 * g1), q2 = g2 * (-1 * g2);
-            const double s0 = g0 * g0, s1 = g1 * g1, s2 = g2 * g2;
-            const double gp = (blk == 0) ? (q0 + q2) + q1 : q1 + (q0 + q2);
-            // goldstein(x0, grad, matchId, f_k, optfunc, tk, 30)
-            // goldstein(x0, grad, matchId, f_k, optfunc, tk, 30), then x0 = x0 - tk*grad
-            const double tk = gold_tree<MW, HPE_GOLD_POLICY, true, RIGID>(
-                rs, o, cv, H, match, fk, gp, pl, gl, evals, nullptr, Xt, &ml, &mwflag,
-                small ? &fpts : nullptr, blk, &md2_l);
-            sc.lap(22);
-            if (tk == 0) cnt += 1;
-            // tol = sqrt(sum(grad % grad)): arrayops::accumulate (two accumulators)
-            tol = uniform_f64(sqrt((blk == 0) ? (s0 + s2) + s1 : s1 + (s0 + s2)));
-            iter += 1;
-            // gold_tree's last barrier published x0 and the accepted node's spheres
-            base_valid = true;  // accepted node copied, or tk == 0 and x0 unchanged
-            REF_TS(rs.ts_n, 5);
-            sc.lap(23);
-        }
-    }
-    if (MW) mw_publish(ml, rs, MW_JOB_EXIT, 0);
-    REF_TS(rs.ts_n, 7);
-    // a timed-out multi-workgroup refine has no defined result: the pose becomes NaN, so
-    // this frame's PSO (and its cost) is NaN and never wins an exchange
-    if (t < HPE_DOF) x0g[t] = (MW && ml.failed) ? __builtin_nan("") : rs.x0[t];
-    if (t == 0 && evals_out) {
-        *evals_out = evals;
-        atomicAdd((unsigned long long *)(evals_out + 2), (unsigned long long)evals);  // running total
+#include "hpe_refine_body.inc"
+}
+
+// ------------------------------------------------------------------ batched lanes
+// hpe_track_batch_dev: B independent sequences in the same launches.  Lane = blockIdx.y; each
+// kernel runs the body of the kernel it mirrors on its lane's state, so a lane computes what
+// the single-sequence path computes, bit for bit.  The swarm stays BY VALUE in the arguments:
+// the mutable arrays of all lanes are B identical arenas `stride` bytes apart, the argument
+// holds lane 0's pointers, and a lane rebases them with scalar adds on the entry batch's
+// words (no table of per-lane structs to load first).  normals, outl, bounds and the inbox
+// counts are shared: every lane draws under the context's seed.  Lanes never communicate.
+__device__ __forceinline__ DevSwarm lane_swarm(DevSwarm sw, size_t stride) {
+    const size_t off = stride * blockIdx.y;
+    sw.xh = (double *)((char *)sw.xh + off);
+    sw.pch = (double *)((char *)sw.pch + off);
+    sw.pb = (double *)((char *)sw.pb + off);
+    sw.v = (double *)((char *)sw.v + off);
+    sw.inbox = (double *)((char *)sw.inbox + off);
+    sw.gmin = (unsigned long long *)((char *)sw.gmin + off);
+    sw.sig = (Sig *)((char *)sw.sig + off);
+    sw.gpos = (double *)((char *)sw.gpos + off);
+    return sw;
+}
+#define HPE_STATE_N (HPE_DOF + 1)  // {x0 -> bestp, cost} of one lane
+#define HPE_EVALS_N 4              // a lane's refine evaluation counter {last, -, total (u64)}
+
+// states: B x 27; obs: B descriptors, lane b's current frame (k_seq_begin_b / k_pso_final_b)
+template <bool FILT>
+__global__ __launch_bounds__(HPE_NT) void k_pso_init_b(DevSwarm sw, size_t stride,
+                                                       const double *__restrict__ states,
+                                                       const DevObs *__restrict__ obs,
+                                                       const DevHand *__restrict__ Hg) {
+    pso_init_body<HPE_NT, FILT>(lane_swarm(sw, stride), states + (size_t)HPE_STATE_N * blockIdx.y,
+                                obs + blockIdx.y, Hg);
+}
+
+template <bool ROW16, bool FILT>
+__global__ __launch_bounds__(HPE_NT) void k_pso_gen_b(DevSwarm sw, size_t stride,
+                                                      const DevObs *__restrict__ obs,
+                                                      const DevHand *__restrict__ Hg, int g,
+                                                      double W1, double C1, double C2,
+                                                      InboxCounts kin) {
+    pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, Hg, g, W1, C1,
+                                             C2, kin);
+}
+
+// k_pso_final's TAIL form on the lane's cursor cur[2 b] = {slot, row}: the row indexes hist
+// over all lanes (lane b starts at row b n), and the next slot's descriptor is staged into
+// obs[b].  The arguments are k_pso_final's own (the host passes same_eval = 1 and no
+// selected-frame hand-back, pipeline counter or refine failure flag), so the body compiles as
+// it does there.
+template <bool FILT, bool TAIL = true>
+__global__ __launch_bounds__(HPE_NT) void k_pso_final_b(DevSwarm sw, size_t stride,
+                                                        double *__restrict__ states, DevObs *obs,
+                                                        const DevHand *__restrict__ Hg,
+                                                        DevObs *__restrict__ obs_out, int same_eval,
+                                                        unsigned long long *__restrict__ seq_dev,
+                                                        unsigned long long *done_host,
+                                                        double *__restrict__ hist,
+                                                        const int *__restrict__ fail,
+                                                        const DevObs *__restrict__ seq_table,
+                                                        int *__restrict__ cur) {
+    sw = lane_swarm(sw, stride);
+    double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
+    DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
+    const DevObs *const og = seq_obs;
+    int *__restrict__ const seq_cur = cur + 2 * blockIdx.y;
+#include "hpe_final_body.inc"
+}
+
+// The single-workgroup staged refine, one workgroup per lane (grid (1, B)): no preparation
+// workgroups, no exchange pick, no helpers.
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_b(double *__restrict__ states,
+                                                    const DevObs *__restrict__ obs,
+                                                    const DevHand *__restrict__ Hg,
+                                                    int *__restrict__ evals_b) {
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    const int do_refine = 1;
+    const PrepArgs pa{};
+    const DevMw mw{};
+    const DevPick pk{};
+#include "hpe_refine_body.inc"
+}
+
+// Start of a batch call: lane b's first descriptor staged, its cursor at {first slot, row b n}.
+struct BatchFirst {
+    int slot[16];
+};
+__global__ void k_seq_begin_b(const DevObs *__restrict__ table, BatchFirst first, int n,
+                              DevObs *__restrict__ obs, int *__restrict__ cur) {
+    const int t = threadIdx.x, b = blockIdx.y;
+    if (t < (int)(sizeof(DevObs) / 8))
+        ((unsigned long long *)(obs + b))[t] = ((const unsigned long long *)(table + first.slot[b]))[t];
+    if (t == 0) {
+        cur[2 * b] = first.slot[b];
+        cur[2 * b + 1] = b * n;
     }
 }
 

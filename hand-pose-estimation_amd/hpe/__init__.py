@@ -137,6 +137,22 @@ class Context:
             self._h, int(num_p), int(refine), C.c_void_p(d_state_ptr), int(first_slot), int(n),
             int(frames_per_graph), C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
 
+    def track_batch(self, num_p, refine, d_states_ptr, first_slots, n, frames_per_graph=0,
+                    d_hist_ptr=None):
+        """Track B = len(first_slots) independent sequences in the same launches: lane b is
+        track_sequence(num_p, refine, d_states_ptr + 27*8 b, first_slots[b], n, ...) bit for
+        bit, with its history at d_hist_ptr + 27*8 n b (device, optional).  d_states_ptr:
+        B x 27 device doubles.  Asynchronous on the context stream."""
+        fs = [int(s) for s in first_slots]
+        if not 1 <= len(fs) <= _lib.BATCH_MAX:
+            raise ValueError(f"track_batch takes 1..{_lib.BATCH_MAX} lanes, got {len(fs)}")
+        if not d_states_ptr:
+            raise ValueError("track_batch needs the device states")
+        arr = (C.c_int32 * len(fs))(*fs)
+        self.check(self.lib.hpe_track_batch_dev(
+            self._h, int(num_p), int(refine), len(fs), C.c_void_p(d_states_ptr), arr, int(n),
+            int(frames_per_graph), C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
+
     def track_raw_sequence(self, num_p, refine, d_state_ptr, d_raw_ptr, n, to_cm=True,
                            downsample=True, focal=241.42, frames_per_graph=0, d_hist_ptr=None):
         """Track n raw depth frames resident in HBM (d_raw_ptr: n x 240x320 float mm) in

@@ -17,6 +17,7 @@ LIB_PATH = PKG_DIR / "libhpe.so"
 PROF_PSO_GEN, PROF_REFINE, PROF_PSO_INIT, PROF_PSO_FINAL, PROF_PREP = 0, 1, 2, 3, 4
 PROF_OPT_DESCENT, PROF_OPT_MOVE, PROF_SWARM_BEST, PROF_EXCHANGE = 5, 6, 7, 8
 SUBSWARM_ID_BYTES = 128
+BATCH_MAX = 16  # HPE_BATCH_MAX
 HPE_OK, HPE_E_ARG, HPE_E_HIP, HPE_E_STATE, HPE_E_NOMEM, HPE_E_NODEVICE = 0, -1, -2, -3, -4, -5
 
 dp = C.POINTER(C.c_double)
@@ -82,6 +83,8 @@ SIGNATURES = {
     "hpe_track_frame_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hpe_track_sequence_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                          C.c_int, C.c_int, C.c_void_p]),
+    "hpe_track_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, ip,
+                                      C.c_int, C.c_int, C.c_void_p]),
     "hpe_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_profile_read": (C.c_int, [C.c_void_p, ip, dp, dp, dp]),
     "hpe_profile_read_kernel": (C.c_int, [C.c_void_p, C.c_int, ip, dp, dp, dp]),

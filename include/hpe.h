@@ -274,6 +274,28 @@ int hpe_track_frame_dev(hpe_ctx *ctx, int num_p, int refine, double *d_state);
 int hpe_track_sequence_dev(hpe_ctx *ctx, int num_p, int refine, double *d_state,
                            int first_slot, int n, int frames_per_graph, double *d_hist);
 
+/* B independent sequences tracked in the SAME launches (a dataset run, two hands in one depth
+ * stream, a multi-camera rig): lane b is
+ *   hpe_track_sequence_dev(ctx, num_p, refine, d_states + 27 b, first_slots[b], n,
+ *                          frames_per_graph, d_hist + 27 n b)
+ * bit for bit -- the context's seed, PSO parameters and refine form -- but a generation launch
+ * covers B x num_p particles, a refine launch is B workgroups on B CUs, and one captured graph
+ * holds a chunk of frames of all lanes.  d_states: device, B x 27 {x0 -> bestp, cost}.
+ * first_slots: host, B entries (copied before return); the lanes' slot ranges may overlap or
+ * coincide (frames are only read).  d_hist (device, optional): B x n x 27, lane b's frame f at
+ * row b n + f.  Asynchronous on hpe_stream(ctx).  Chunk graphs are keyed by their shape
+ * (num_p, generations, refine, frames, kernel forms, B, d_states, d_hist), not by the slots or n:
+ * per-lane device cursors name each frame.  The selected frame stays as it was, hpe_pso_trace
+ * is not updated, and hpe_refine_eval_count counts every lane's evaluations.
+ * Supported (anything else is refused, never run another way): 1 <= B <= HPE_BATCH_MAX; num_p
+ * in the workgroup-per-particle form (below 1024 by default); every frame at most 2048 cloud
+ * points (the single-workgroup refine); for each frame index all lanes on the same side of 256
+ * cloud points (one kernel form per launch) -- HPE_E_ARG; no live subswarm transport and no
+ * hpe_set_exchange -- HPE_E_STATE. */
+#define HPE_BATCH_MAX 16
+int hpe_track_batch_dev(hpe_ctx *ctx, int num_p, int refine, int B, double *d_states,
+                        const int32_t *first_slots, int n, int frames_per_graph, double *d_hist);
+
 /* Pipelined tracking: test_full's loop (testmodel.cpp:117-139) with next_frame
  * (observedmodel.cpp:420-430) of frame f+1 running INSIDE frame f's refine launch, on CUs
  * the single-workgroup refine leaves idle: one stream, one replayed graph per frame.
