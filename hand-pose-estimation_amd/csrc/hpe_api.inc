@@ -224,6 +224,31 @@ struct hpe_ctx {
         hipGraphExec_t exec;
     };
     std::vector<BatchGraph> bgraphs;
+    // batched raw lanes (hpe_track_raw_batch_dev): per lane one arena holding two frame buffers
+    // (depth, DT, a 250-point cloud each) and the preparation scratch (tmp, ctb, dtf); the
+    // descriptors, PrepInfo and PrepArgs tables by [parity][lane]; the lane's hand-off counters
+    // (a 128-byte line each), raw base and cursor {frame, history row}.  The chunk graphs hold
+    // only the tables' addresses, which never change: arenas are added, never moved.
+    struct RawBatch {
+        char *arena[HPE_BATCH_MAX] = {};
+        int lanes = 0, to_cm = -1;
+        double focal = 0;
+        DevObs *d_obs = nullptr;      // [2][HPE_BATCH_MAX]
+        PrepInfo *d_info = nullptr;   // [2][HPE_BATCH_MAX]
+        PrepArgs *d_tab = nullptr;    // [2][HPE_BATCH_MAX]
+        unsigned *d_ctr = nullptr;    // [HPE_BATCH_MAX][32]
+        const float **d_raw = nullptr;  // [HPE_BATCH_MAX]
+        int *d_cur = nullptr;         // [HPE_BATCH_MAX][2]
+    } rb;
+    struct RawBatchGraph {
+        int P, G, refine, k, parity, tail_next, B, to_cm, downsample;
+        double focal;
+        double *states, *hist;
+        uint64_t seed;
+        unsigned epoch;
+        hipGraphExec_t exec;
+    };
+    std::vector<RawBatchGraph> rbgraphs;
     hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
     bool pipe_counting = false;  // set while a pipelined frame is enqueued (k_pso_final args)
@@ -901,6 +926,8 @@ static void drop_graphs(hpe_ctx *c) {
     for (auto &sg : c->sgraphs) (void)hipGraphExecDestroy(sg.exec);
     for (auto &rg : c->rgraphs) (void)hipGraphExecDestroy(rg.exec);
     for (auto &bg : c->bgraphs) (void)hipGraphExecDestroy(bg.exec);
+    for (auto &rg : c->rbgraphs) (void)hipGraphExecDestroy(rg.exec);
+    c->rbgraphs.clear();
     c->bgraphs.clear();
     c->pgraphs.clear();
     c->sgraphs.clear();
@@ -949,6 +976,13 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->d_bobs);
     dfree(c->d_bcur);
     dfree(c->d_bevals);
+    for (auto &a : c->rb.arena) dfree(a);
+    dfree(c->rb.d_obs);
+    dfree(c->rb.d_info);
+    dfree(c->rb.d_tab);
+    dfree(c->rb.d_ctr);
+    dfree(c->rb.d_raw);
+    dfree(c->rb.d_cur);
     dfree(c->d_raw);
     dfree(c->d_tmp);
     dfree(c->d_ctb);
@@ -2097,6 +2131,18 @@ static int enqueue_batch_chunk(hpe_ctx *c, int P, int refine, int B, double *d_s
     return HPE_OK;
 }
 
+// The lanes' descriptors, cursors and refine evaluation counters (both batch calls count in
+// d_bevals).
+static int ensure_batch_lanes(hpe_ctx *c) {
+    if (!c->d_bobs) {
+        HIPCHK(c, dalloc(&c->d_bobs, HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&c->d_bcur, 2 * HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&c->d_bevals, HPE_BATCH_MAX * HPE_EVALS_N));
+        HIPCHK(c, hipMemset(c->d_bevals, 0, sizeof(int) * HPE_BATCH_MAX * HPE_EVALS_N));
+    }
+    return HPE_OK;
+}
+
 int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
                         const int32_t *first_slots, int n, int frames_per_graph, double *d_hist) {
     if (!c) return HPE_E_ARG;
@@ -2137,12 +2183,7 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
     }
     HIPCHK(c, hipSetDevice(c->device));
     const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
-    if (!c->d_bobs) {
-        HIPCHK(c, dalloc(&c->d_bobs, HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&c->d_bcur, 2 * HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&c->d_bevals, HPE_BATCH_MAX * HPE_EVALS_N));
-        HIPCHK(c, hipMemset(c->d_bevals, 0, sizeof(int) * HPE_BATCH_MAX * HPE_EVALS_N));
-    }
+    if ((rc = ensure_batch_lanes(c))) return rc;
     if ((rc = ensure_swarm(c, P, G, B))) return rc;
     if ((rc = upload_bounds(c))) return rc;
     // frames prepared on the preprocessing stream: the tracking stream waits for the ones
@@ -2439,6 +2480,211 @@ int hpe_track_raw_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state,
     }
     // the last frame's descriptor is the selected one now (handed back by its final kernel)
     c->cur = -1;
+    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
+    c->seq_done_valid = true;
+    return HPE_OK;
+}
+
+// The raw batch's buffers for B lanes prepared with (to_cm, focal): the fixed tables once, an
+// arena per new lane, and the PrepArgs table rewritten when a lane is added or the preparation
+// parameters change (after the stream has drained: launches in flight read it).
+static int ensure_raw_batch(hpe_ctx *c, int B, int to_cm, double focal) {
+    hpe_ctx::RawBatch &rb = c->rb;
+    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W, M = HPE_BATCH_MAX;
+    if (!rb.d_obs) {
+        HIPCHK(c, dalloc(&rb.d_obs, 2 * M));
+        HIPCHK(c, dalloc(&rb.d_info, 2 * M));
+        HIPCHK(c, dalloc(&rb.d_tab, 2 * M));
+        HIPCHK(c, dalloc(&rb.d_ctr, 32 * M));
+        HIPCHK(c, hipMemset(rb.d_ctr, 0, sizeof(unsigned) * 32 * M));
+        HIPCHK(c, dalloc(&rb.d_raw, M));
+        HIPCHK(c, dalloc(&rb.d_cur, 2 * M));
+    }
+    if (B <= rb.lanes && to_cm == rb.to_cm && focal == rb.focal) return HPE_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rb.to_cm = -1;  // no table until it is written below
+    // a lane's arena: per parity {depth, dt, cx, cy, cz}, then tmp, ctb, dtf; every array on a
+    // 256-byte boundary
+    const size_t cloud = (sizeof(double) * 250 + 255) & ~(size_t)255;
+    const size_t o_dt = sizeof(double) * npix, o_c = o_dt + sizeof(float) * npix,
+                 frame = o_c + 3 * cloud;
+    const size_t o_tmp = 2 * frame, o_ctb = o_tmp + sizeof(double) * 3 * npix,
+                 o_dtf = o_ctb + sizeof(double) * npix, bytes = o_dtf + sizeof(int) * npix;
+    while (rb.lanes < B) {
+        HIPCHK(c, dalloc(&rb.arena[rb.lanes], bytes));
+        ++rb.lanes;
+    }
+    std::vector<PrepArgs> tab(2 * M);
+    std::memset((void *)tab.data(), 0, sizeof(PrepArgs) * tab.size());
+    for (int p = 0; p < 2; ++p)
+        for (int b = 0; b < rb.lanes; ++b) {
+            char *f = rb.arena[b] + p * frame;
+            PrepArgs &a = tab[p * M + b];
+            a.to_cm = to_cm;
+            a.downsample = 1;
+            a.focal = focal;
+            a.depth_cm = (double *)f;
+            a.dt = (float *)(f + o_dt);
+            a.cx = (double *)(f + o_c);
+            a.cy = (double *)(f + o_c + cloud);
+            a.cz = (double *)(f + o_c + 2 * cloud);
+            a.tmp = (double *)(rb.arena[b] + o_tmp);
+            a.ctb = (double *)(rb.arena[b] + o_ctb);
+            a.dtf = (int *)(rb.arena[b] + o_dtf);
+            a.info = rb.d_info + p * M + b;
+            a.obs_out = rb.d_obs + p * M + b;
+            a.ctr = rb.d_ctr + 32 * b;
+            a.raw_stride = npix;
+        }
+    HIPCHK(c, hipMemcpy(rb.d_tab, tab.data(), sizeof(PrepArgs) * tab.size(), hipMemcpyHostToDevice));
+    rb.to_cm = to_cm;
+    rb.focal = focal;
+    return HPE_OK;
+}
+
+// k frames of B raw lanes, the first in the lanes' prepared buffers `parity`: per frame the
+// launches of enqueue_batch_chunk on the parity's descriptors, the refine launch carrying every
+// lane's next preparation (grid (1 + PREP_WG, B)) whenever a next frame exists, as
+// enqueue_raw_chunk's does for one sequence.  Every cloud is bounded by 250 points: the staged
+// refine and the non-FILT kernels.
+static int enqueue_raw_batch_chunk(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                                   int parity, int k, bool tail_next, double *hist) {
+    hpe_ctx::RawBatch &rb = c->rb;
+    const DevSwarm d = batch_swarm(c);
+    const size_t stride = c->sw.stride;
+    const int G = d.G;
+    const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
+    static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
+    const bool r16 = d.K <= 15;
+    const DevHand *hand = c->d_hand;
+    for (int i = 0; i < k; ++i) {
+        const int cur = (parity + i) & 1, nxt = cur ^ 1;
+        const bool next = i + 1 < k || tail_next;
+        DevObs *obs = rb.d_obs + cur * HPE_BATCH_MAX;
+        if (next)  // testmodel.cpp:126 + next_frame of the following iteration
+            launch(c, HPE_PROF_REFINE,
+                   c->refine_exact ? k_refine_prep_b<false> : k_refine_prep_b<true>,
+                   dim3(1 + PREP_WG, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
+                   c->d_bevals, refine ? 1 : 0, (const PrepArgs *)(rb.d_tab + nxt * HPE_BATCH_MAX),
+                   (const float *const *)rb.d_raw, (const int *)rb.d_cur);
+        else if (refine)
+            launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
+                   dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
+                   c->d_bevals);
+        launch(c, HPE_PROF_PSO_INIT, k_pso_init_b<false>, dim3(P, B), dim3(HPE_NT), 0, d, stride,
+               (const double *)d_states, (const DevObs *)obs, hand);
+        for (int g = 1; g <= G; ++g) {
+            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
+            launch(c, HPE_PROF_PSO_GEN, r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>,
+                   dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)obs, hand, g, W1, C1, C2, kg);
+        }
+        // no slot table: the cursor's slot word counts the lane's frames (the preparation's)
+        launch(c, HPE_PROF_PSO_FINAL, k_pso_final_b<false>, dim3(1, B), dim3(HPE_NT), 0, d, stride,
+               d_states, obs, hand, (DevObs *)nullptr, 1, (unsigned long long *)nullptr,
+               (unsigned long long *)nullptr, hist, (const int *)nullptr, (const DevObs *)nullptr,
+               rb.d_cur);
+        HIPCHK(c, hipGetLastError());
+    }
+    return HPE_OK;
+}
+
+int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                            const float *const *d_raw_mm, int n, int to_cm, int downsample,
+                            double focal, int frames_per_graph, double *d_hist) {
+    if (!c) return HPE_E_ARG;
+    if (int erc = mw_check_async(c)) return erc;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!d_states || !d_raw_mm) return fail(c, HPE_E_ARG, "null device states or raw pointers");
+    for (int b = 0; b < B; ++b)
+        if (!d_raw_mm[b]) return fail(c, HPE_E_ARG, "lane %d: null raw frames", b);
+    if (n < 1) return fail(c, HPE_E_ARG, "n = %d frames", n);
+    if (!(focal > 0)) return fail(c, HPE_E_ARG, "focal %g is not positive", focal);
+    if (frames_per_graph < 0 || frames_per_graph > HPE_SEQ_MAX_CHUNK)
+        return fail(c, HPE_E_ARG, "frames_per_graph %d out of range [0, %d]", frames_per_graph,
+                    HPE_SEQ_MAX_CHUNK);
+    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
+    int rc = check_P(c, P);
+    if (rc) return rc;
+    if (pso_wave_form(c, P))
+        return fail(c, HPE_E_ARG, "num_p %d takes the wave form: a batch needs the workgroup form "
+                    "(num_p < %d)", P, c->wave_form_min_p);
+    if (!downsample)
+        return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
+                    "the single-workgroup refine (<= %d)", HPE_IMG_H * HPE_IMG_W, RF_STAGE_MAX);
+    if (c->ss.transport())
+        return fail(c, HPE_E_STATE, "a subswarm transport is live: a batch runs without the "
+                    "exchange (hpe_subswarm_fini)");
+    if (c->xch_every > 0)
+        return fail(c, HPE_E_STATE, "the per-generation exchange is on (hpe_set_exchange)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
+    to_cm = to_cm ? 1 : 0;
+    if ((rc = ensure_batch_lanes(c))) return rc;
+    if ((rc = ensure_raw_batch(c, B, to_cm, focal))) return rc;
+    if ((rc = ensure_swarm(c, P, G, B))) return rc;
+    if ((rc = upload_bounds(c))) return rc;
+    hpe_ctx::RawBatch &rb = c->rb;
+    // the lanes' raw bases and cursors, then frame 0 of every lane into buffer parity 0
+    BatchRaw first{};
+    for (int b = 0; b < B; ++b) first.raw[b] = d_raw_mm[b];
+    hipLaunchKernelGGL(k_raw_begin_b, dim3(1, B), dim3(64), 0, c->stream, first, n, rb.d_raw, rb.d_cur);
+    hipLaunchKernelGGL(k_prepare_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                       (const PrepArgs *)rb.d_tab, (const float *const *)rb.d_raw,
+                       (const int *)rb.d_cur);
+    HIPCHK(c, hipGetLastError());
+    const int K = frames_per_graph ? frames_per_graph : HPE_SEQ_CHUNK;
+    for (int f0 = 0; f0 < n; f0 += K) {
+        const int k = n - f0 < K ? n - f0 : K, parity = f0 & 1, tail_next = f0 + k < n;
+        if (direct_launches(c)) {
+            if ((rc = enqueue_raw_batch_chunk(c, P, refine, B, d_states, parity, k, tail_next, d_hist)))
+                return rc;
+            continue;
+        }
+        hipGraphExec_t exec = nullptr;
+        for (auto &rg : c->rbgraphs)  // keyed by the chunk's shape, not the raw buffers or n
+            if (rg.P == P && rg.G == G && rg.refine == refine && rg.k == k && rg.parity == parity &&
+                rg.tail_next == tail_next && rg.B == B && rg.to_cm == to_cm &&
+                rg.downsample == 1 && rg.focal == focal && rg.states == d_states &&
+                rg.hist == d_hist && rg.seed == c->seed && rg.epoch == c->epoch)
+                exec = rg.exec;
+        if (!exec) {
+            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+            ++c->captures;
+            bool direct = false;
+            rc = enqueue_raw_batch_chunk(c, P, refine, B, d_states, parity, k, tail_next, d_hist);
+            if ((rc = end_capture(c, rc, &exec, &direct))) return rc;
+            if (direct) {  // end_capture's exchange fallback: a batch never holds the exchange
+                if ((rc = enqueue_raw_batch_chunk(c, P, refine, B, d_states, parity, k, tail_next,
+                                                  d_hist)))
+                    return rc;
+                continue;
+            }
+            // drop graphs of an older epoch or seed (one may still be in flight: wait first),
+            // and all of them at the cap, as hpe_track_batch_dev does
+            bool stale = false;
+            for (auto &rg : c->rbgraphs) stale |= rg.epoch != c->epoch || rg.seed != c->seed;
+            if (stale || c->rbgraphs.size() >= 64) HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (size_t q = 0; q < c->rbgraphs.size();) {
+                if (stale && (c->rbgraphs[q].epoch != c->epoch || c->rbgraphs[q].seed != c->seed)) {
+                    (void)hipGraphExecDestroy(c->rbgraphs[q].exec);
+                    c->rbgraphs[q] = c->rbgraphs.back();
+                    c->rbgraphs.pop_back();
+                } else {
+                    ++q;
+                }
+            }
+            if (c->rbgraphs.size() >= 64) {
+                for (auto &rg : c->rbgraphs) (void)hipGraphExecDestroy(rg.exec);
+                c->rbgraphs.clear();
+            }
+            c->rbgraphs.push_back({P, G, refine, k, parity, tail_next, B, to_cm, 1, focal, d_states,
+                                   d_hist, c->seed, c->epoch, exec});
+        }
+        HIPCHK(c, hipGraphLaunch(exec, c->stream));
+    }
+    // the same "last reader" event the other sequence calls record
     if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
     c->seq_done_valid = true;

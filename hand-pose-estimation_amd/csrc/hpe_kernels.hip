@@ -1482,6 +1482,73 @@ __global__ void k_seq_begin_b(const DevObs *__restrict__ table, BatchFirst first
     }
 }
 
+// ------------------------------------------------------------------ batched raw lanes
+// hpe_track_raw_batch_dev: B resident raw sequences in the same launches.  Lane b owns two frame
+// buffers, their descriptors obs[parity][b], preparation scratch and hand-off counters (a
+// 128-byte line of its own), all named by the device table tab[parity][b] (PrepArgs with no raw
+// frame, written when the buffers are allocated); raw_base[b] is the lane's first raw frame and
+// cur[2 b] = {frame, history row} its cursor, which k_pso_final_b advances (no slot table: the
+// slot word counts frames).  The kernels take tab + parity * HPE_BATCH_MAX.
+
+// The preparation of lane blockIdx.y: its table entry, on raw frame cur + next.  Three
+// independent loads; only the preparation workgroups call it.
+__device__ __forceinline__ PrepArgs lane_prep(const PrepArgs *__restrict__ tab,
+                                              const float *const *__restrict__ raw_base,
+                                              const int *__restrict__ cur, int next) {
+    const int b = blockIdx.y;
+    PrepArgs a = tab[b];
+    a.raw = raw_base[b] + (size_t)(cur[2 * b] + next) * a.raw_stride;
+    a.raw_row = nullptr;  // a.raw is the frame itself
+    return a;
+}
+
+// Start of a raw batch call: lane b's raw base, its cursor at {frame 0, row b n}.  Frame 0 goes
+// to buffer parity 0 (k_prepare_b below).
+struct BatchRaw {
+    const float *raw[16];
+};
+__global__ void k_raw_begin_b(BatchRaw first, int n, const float **__restrict__ raw_base,
+                              int *__restrict__ cur) {
+    const int b = blockIdx.y;
+    if (threadIdx.x == 0) {
+        raw_base[b] = first.raw[b];
+        cur[2 * b] = 0;
+        cur[2 * b + 1] = b * n;
+    }
+}
+
+// k_prepare for every lane's frame at its cursor (frame 0 of a call), grid (PREP_WG, B)
+__global__ __launch_bounds__(PREP_NT) void k_prepare_b(const PrepArgs *__restrict__ tab,
+                                                       const float *const *__restrict__ raw_base,
+                                                       const int *__restrict__ cur) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    prep_workgroup(lane_prep(tab, raw_base, cur, 0), blockIdx.x, lds);
+}
+
+// k_refine_b with the lane's next frame prepared in the same launch, grid (1 + PREP_WG, B):
+// workgroup (0, b) is k_refine_b's (it reads what that one reads: tab, raw_base and cur are
+// touched by the preparation workgroups (1.., b) alone), the others run prep_workgroup into the
+// lane's other buffer, as k_refine's do.  do_refine = 0: the preparation only.
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_prep_b(double *__restrict__ states,
+                                                         const DevObs *__restrict__ obs,
+                                                         const DevHand *__restrict__ Hg,
+                                                         int *__restrict__ evals_b, int do_refine,
+                                                         const PrepArgs *__restrict__ tab,
+                                                         const float *const *__restrict__ raw_base,
+                                                         const int *__restrict__ cur) {
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    PrepArgs pa{};
+    if (blockIdx.x >= 1) pa = lane_prep(tab, raw_base, cur, 1);
+    const DevMw mw{};
+    const DevPick pk{};
+#include "hpe_refine_body.inc"
+}
+static_assert(PREP_NT == RF_NT, "the preparation workgroups ride in the refine launch");
+
 #include "hpe_optimise.hpp"
 
 // ------------------------------------------------------------------ synthetic frames

@@ -164,6 +164,24 @@ class Context:
             int(n), int(to_cm), int(downsample), float(focal), int(frames_per_graph),
             C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
 
+    def track_raw_batch(self, num_p, refine, d_states_ptr, d_raw_ptrs, n, to_cm=True,
+                        downsample=True, focal=241.42, frames_per_graph=0, d_hist_ptr=None):
+        """Track B = len(d_raw_ptrs) resident raw sequences in the same launches: lane b is
+        track_raw_sequence(num_p, refine, d_states_ptr + 27*8 b, d_raw_ptrs[b], n, ...) bit for
+        bit, with its history at d_hist_ptr + 27*8 n b (device, optional).  d_raw_ptrs: device
+        pointers, each to n x 240x320 float mm (lanes may share one).  d_states_ptr: B x 27
+        device doubles.  Asynchronous on the context stream."""
+        rp = [int(p) for p in d_raw_ptrs]
+        if not 1 <= len(rp) <= _lib.BATCH_MAX:
+            raise ValueError(f"track_raw_batch takes 1..{_lib.BATCH_MAX} lanes, got {len(rp)}")
+        if not d_states_ptr:
+            raise ValueError("track_raw_batch needs the device states")
+        arr = (C.c_void_p * len(rp))(*rp)
+        self.check(self.lib.hpe_track_raw_batch_dev(
+            self._h, int(num_p), int(refine), len(rp), C.c_void_p(d_states_ptr), arr, int(n),
+            int(to_cm), int(downsample), float(focal), int(frames_per_graph),
+            C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
+
     # ---- multi-GPU subswarms: the library's own per-frame exchange (hpe_subswarm_init)
     def subswarm_init(self, uid: bytes, nranks: int, rank: int):
         """Join the RCCL communicator named by uid (hpe.subswarm_unique_id() on rank 0, shared

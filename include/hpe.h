@@ -322,6 +322,29 @@ int hpe_track_raw_sequence_dev(hpe_ctx *ctx, int num_p, int refine, double *d_st
                                const float *d_raw_mm, int n, int to_cm, int downsample,
                                double focal, int frames_per_graph, double *d_hist);
 
+/* B resident raw sequences tracked in the SAME launches (what a multi-camera rig, two hands in
+ * one depth stream or a dataset run delivers): lane b is
+ *   hpe_track_raw_sequence_dev(ctx, num_p, refine, d_states + 27 b, d_raw_mm[b], n, to_cm,
+ *                              downsample, focal, frames_per_graph, d_hist + 27 n b)
+ * bit for bit -- the context's seed, PSO parameters and refine form -- in hpe_track_batch_dev's
+ * launches, with next_frame of every lane's frame f+1 inside frame f's refine launch: grid
+ * (1 + 9, B), lane b's refine workgroup and the nine that prepare its next frame, each on a CU
+ * of its own.  d_raw_mm: host array of B device pointers, each n x 240x320 float mm (copied
+ * before return; lanes may name the same buffer).  d_states: device, B x 27.  d_hist (device,
+ * optional): B x n x 27, lane b's frame f at row b n + f.  Asynchronous on hpe_stream(ctx).
+ * Chunk graphs are keyed by their shape (num_p, generations, refine, frames, buffer parity,
+ * whether the last frame prepares another, B, to_cm, downsample, focal, d_states, d_hist), not
+ * by the raw pointers or n: a lane's raw base and frame cursor live in device memory.  The call
+ * owns its frame buffers and preparation scratch (about 4.6 MB per lane): a pipelined sequence
+ * in progress and the other calls' cached graphs stay valid, the selected frame stays as it
+ * was, hpe_pso_trace is not updated, and hpe_refine_eval_count counts every lane's evaluations.
+ * Supported (anything else is refused, never run another way): 1 <= B <= HPE_BATCH_MAX; num_p
+ * in the workgroup-per-particle form; downsample != 0 (250-point clouds: the single-workgroup
+ * refine) -- HPE_E_ARG; no live subswarm transport and no hpe_set_exchange -- HPE_E_STATE. */
+int hpe_track_raw_batch_dev(hpe_ctx *ctx, int num_p, int refine, int B, double *d_states,
+                            const float *const *d_raw_mm, int n, int to_cm, int downsample,
+                            double focal, int frames_per_graph, double *d_hist);
+
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through
  * hipExtLaunchKernel with a start/stop event pair (dispatch-packet timestamps: the

@@ -6,9 +6,15 @@ Every lane has its own synthetic sequence (seeds 0..B-1, as tools/serve_streams.
 device-prepared into resident slots.  First checks on 6 frames that every lane of a batch
 equals the same lane tracked alone by track_sequence, bit for bit; then prints one JSON line
 per lane count with the aggregate tracked frames/s and the time of one batched frame.
-Usage (GPU box): python tools/bench_batch.py [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
+--raw: the same lane counts and workload over raw float mm frames resident in HBM
+(hpe_track_raw_batch_dev: every lane's next frame is prepared inside the lanes' refine launch);
+the check is then against track_raw_sequence alone.  --profile adds the mean device time of the
+refine, init, generation and final kernels of one more pass (HPE_PROF_*, direct launches).
+Usage (GPU box): python tools/bench_batch.py [--raw] [--profile] [--lanes 1,2,4,8,16]
+                                             [--frames 48] [--reps 3]
 """
 import argparse
+import ctypes as C
 import json
 import sys
 import time
@@ -30,6 +36,17 @@ def make_lanes(ctx, B, n):
         for f, th in enumerate(poses):
             ctx.prepare_frame(b * n + f, np.ascontiguousarray(ctx.render_depth(th)))
     ctx.check(ctx.lib.hpe_sync(ctx.h))
+
+
+def make_raw_lanes(ctx, torch, B, n):
+    """Lane b's n frames rendered and uploaded as one raw device tensor (n x 240 x 320 float mm)."""
+    from hpe import synth
+    out = []
+    for b in range(B):
+        poses = synth.trajectory(n, b, revert=0.02)
+        fr = np.stack([np.ascontiguousarray(ctx.render_depth(th)) for th in poses])
+        out.append(torch.from_numpy(fr.astype(np.float32)).to("cuda:0"))
+    return out
 
 
 def start_states(torch, x0, B):
@@ -54,11 +71,49 @@ def check_against_alone(ctx, torch, x0, B, n_frames, n=6):
             raise AssertionError(f"lane {b} of the batch differs from the lane tracked alone")
 
 
+def check_raw_against_alone(ctx, torch, x0, raws, n=6):
+    B = len(raws)
+    st = start_states(torch, x0, B)
+    hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0")
+    ctx.track_raw_batch(P, 1, st.data_ptr(), [r.data_ptr() for r in raws], n,
+                        frames_per_graph=FPG, d_hist_ptr=hist.data_ptr())
+    ctx.check(ctx.lib.hpe_sync(ctx.h))
+    s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
+    h1 = torch.empty((n, 27), dtype=torch.float64, device="cuda:0")
+    for b in range(B):
+        s1.copy_(start_states(torch, x0, 1)[0])
+        ctx.track_raw_sequence(P, 1, s1.data_ptr(), raws[b].data_ptr(), n, frames_per_graph=FPG,
+                               d_hist_ptr=h1.data_ptr())
+        ctx.check(ctx.lib.hpe_sync(ctx.h))
+        if not (np.array_equal(h1.cpu().numpy(), hist[b].cpu().numpy())
+                and np.array_equal(s1.cpu().numpy(), st[b].cpu().numpy())):
+            raise AssertionError(f"lane {b} of the raw batch differs from the lane tracked alone")
+
+
+def kernel_means_us(ctx, run):
+    """Mean device microseconds per launch of the profiled kernels over one pass of run()."""
+    from hpe import _lib
+    ctx.check(ctx.lib.hpe_profile_enable(ctx.h, 1))
+    run()
+    out = {}
+    for name, kid in (("refine", _lib.PROF_REFINE), ("init", _lib.PROF_PSO_INIT),
+                      ("gen", _lib.PROF_PSO_GEN), ("final", _lib.PROF_PSO_FINAL)):
+        nl = C.c_int32(0)
+        tot, mn, mx = C.c_double(0), C.c_double(0), C.c_double(0)
+        ctx.check(ctx.lib.hpe_profile_read_kernel(ctx.h, kid, C.byref(nl), C.byref(tot),
+                                                  C.byref(mn), C.byref(mx)))
+        out[name] = {"launches": nl.value, "mean_us": tot.value / max(nl.value, 1) * 1e3}
+    ctx.check(ctx.lib.hpe_profile_enable(ctx.h, 0))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", default="1,2,4,8,16")
     ap.add_argument("--frames", type=int, default=48)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--raw", action="store_true")
+    ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
     import torch
     torch.cuda.is_available()
@@ -71,10 +126,24 @@ def main():
     pso = hpe.PSO()
     pso.set_pso_params(ub, lb, sd, 0.7298, 1.49618, 1.49618, G + 1, 1e-8, 1e-8)
     pso._push(ctx)
-    make_lanes(ctx, max(counts), n)
-    check_against_alone(ctx, torch, hpe.X0, min(3, max(counts)), n)
+    if a.raw:
+        raws = make_raw_lanes(ctx, torch, max(counts), n)
+        check_raw_against_alone(ctx, torch, hpe.X0, raws[:min(3, max(counts))])
+    else:
+        make_lanes(ctx, max(counts), n)
+        check_against_alone(ctx, torch, hpe.X0, min(3, max(counts)), n)
     for B in counts:
         slots = [b * n for b in range(B)]
+        if a.raw:
+            ptrs = [r.data_ptr() for r in raws[:B]]
+
+        def run():
+            if a.raw:
+                ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG)
+            else:
+                ctx.track_batch(P, 1, st.data_ptr(), slots, n, FPG)
+            ctx.check(ctx.lib.hpe_sync(ctx.h))
+
         st = start_states(torch, hpe.X0, B)
         x0 = st.clone()
         times = []
@@ -82,16 +151,20 @@ def main():
             st.copy_(x0)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            ctx.track_batch(P, 1, st.data_ptr(), slots, n, FPG)
-            ctx.check(ctx.lib.hpe_sync(ctx.h))
+            run()
             times.append(time.perf_counter() - t0)
         el = float(np.median(times[1:]))
-        print(json.dumps({"lanes": B, "frames_per_lane": n, "reps": a.reps,
-                          "aggregate_tracked_fps": B * n / el,
-                          "ms_per_batched_frame": el / n * 1e3,
-                          "workload": "256 p x 30 gen, refine on, N = 250, resident prepared "
-                                      "frames, 8 frames per graph, one context, seeds 0..B-1"}),
-              flush=True)
+        line = {"lanes": B, "frames_per_lane": n, "reps": a.reps,
+                "aggregate_tracked_fps": B * n / el,
+                "ms_per_batched_frame": el / n * 1e3,
+                "workload": "256 p x 30 gen, refine on, N = 250, resident "
+                            + ("raw frames prepared in the refine launch" if a.raw else "prepared frames")
+                            + ", 8 frames per graph, one context, seeds 0..B-1"}
+        if a.profile:
+            st.copy_(x0)
+            torch.cuda.synchronize()
+            line["kernels"] = kernel_means_us(ctx, run)
+        print(json.dumps(line), flush=True)
     ctx.close()
     return 0
 
