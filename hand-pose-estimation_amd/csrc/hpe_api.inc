@@ -171,6 +171,10 @@ struct hpe_ctx {
         // host reuses pinned buffer k once h_done >= used_seq[k], the number of the frame
         // whose refine launch read it (zero copy)
         unsigned long long *d_seq = nullptr, *h_done = nullptr, *h_done_dev = nullptr;
+        // the split distance transform of resident raw sequences (PrepSplit): the forward
+        // scans by frame parity, and {first hand row [2], sequence length, -}
+        int *d_dtf2 = nullptr;   // [2][npix]
+        int *d_split = nullptr;  // [4]
         unsigned long long enq = 0, used_seq[2] = {0, 0};
         hipEvent_t used[2] = {nullptr, nullptr};
         hipStream_t copy = nullptr;
@@ -259,6 +263,9 @@ struct hpe_ctx {
     static constexpr int wpp2_max_p = 1024;
     bool fk_coop = true;  // the wave form's FK by the whole workgroup (HPE_FK_COOP)
     bool use_graph = true;
+    // resident raw sequences split each frame's distance transform over two refine launches
+    // (HPE_PREP_SPLIT=0: the whole transform in one, as the pipelined loop has it)
+    bool prep_split = true;
     double *h_pinned = nullptr; // 256 doubles: [0,64) results, [64,128) inputs
     int *d_evals = nullptr;
     // multi-workgroup refine (clouds > RF_STAGE_MAX); HPE_REFINE_MW=0 keeps one workgroup
@@ -909,6 +916,7 @@ int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
     if (const char *rm = std::getenv("HPE_REFINE_MW")) c->refine_mw = rm[0] != '0';
     if (const char *re = std::getenv("HPE_REFINE_EXACT")) c->refine_exact = re[0] == '1';
     if (const char *sp = std::getenv("HPE_MW_SPIN")) c->mw_spin = std::max(0, std::atoi(sp));
+    if (const char *ps = std::getenv("HPE_PREP_SPLIT")) c->prep_split = ps[0] != '0';
     *c->h_mw_err = 0;
     const char *ng = std::getenv("HPE_NO_GRAPH");
     c->use_graph = !(ng && ng[0] == '1');
@@ -1010,6 +1018,8 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->pipe.d_info);
     dfree(c->pipe.d_raw);
     dfree(c->pipe.d_seq);
+    dfree(c->pipe.d_dtf2);
+    dfree(c->pipe.d_split);
     if (c->pipe.h_done) (void)hipHostFree(c->pipe.h_done);
     if (c->h_mw_err) (void)hipHostFree(c->h_mw_err);
     for (int k = 0; k < 2; ++k)
@@ -1511,12 +1521,14 @@ static bool mw_fits(hpe_ctx *c) {
 
 // refine_init_pose on the selected frame (do_refine) and, when pa != NULL, the next
 // frame's preparation in the same launch (workgroups 1, 2).  n_hint bounds the cloud size.
-static int refine_launch(hpe_ctx *c, double *d_x0, int n_hint, int do_refine, const PrepArgs *pa) {
+static int refine_launch(hpe_ctx *c, double *d_x0, int n_hint, int do_refine, const PrepArgs *pa,
+                         const PrepSplit *split = nullptr) {
     int rc = ensure_match(c, (size_t)(n_hint > 0 ? n_hint : 1));
     if (rc) return rc;
     PrepArgs none;
     std::memset(&none, 0, sizeof(none));
     const PrepArgs a = pa ? *pa : none;
+    const PrepSplit ps = (pa && split) ? *split : PrepSplit{};
     DevMw mw;
     std::memset(&mw, 0, sizeof(mw));
     DevPick pk{};
@@ -1531,7 +1543,7 @@ static int refine_launch(hpe_ctx *c, double *d_x0, int n_hint, int do_refine, co
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<true> : k_refine<true, false, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0, c->obs_dev, (const DevHand *)c->d_hand,
-               c->d_match, c->d_evals, do_refine, a, mw, pk);
+               c->d_match, c->d_evals, do_refine, a, mw, pk, ps);
     } else if (c->refine_mw && mw_fits(c)) {  // multi-workgroup form: MW_MAX_Q helpers own cloud slices
         mw.job = c->d_mw_job;
         mw.part = c->d_mw_part;
@@ -1544,13 +1556,13 @@ static int refine_launch(hpe_ctx *c, double *d_x0, int n_hint, int do_refine, co
         launch(c, HPE_PROF_REFINE,
                c->refine_exact ? k_refine<false, true> : k_refine<false, true, true>, grid,
                dim3(RF_NT), (unsigned)prep_lds_bytes(), d_x0, c->obs_dev, (const DevHand *)c->d_hand,
-               c->d_match, c->d_evals, do_refine, a, mw, pk);
+               c->d_match, c->d_evals, do_refine, a, mw, pk, ps);
     } else {
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<false> : k_refine<false, false, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0,
                c->obs_dev, (const DevHand *)c->d_hand, c->d_match, c->d_evals, do_refine, a,
-               mw, pk);
+               mw, pk, ps);
     }
     HIPCHK(c, hipGetLastError());
     return HPE_OK;
@@ -1881,6 +1893,9 @@ static int ensure_pipe(hpe_ctx *c, int need) {
         HIPCHK(c, hipStreamCreateWithFlags(&pp.copy, hipStreamNonBlocking));
         if (const char *u = std::getenv("HPE_PIPE_UPLOAD")) pp.zero_copy = u[0] != '1';
         HIPCHK(c, dalloc(&pp.d_seq, 1));
+        HIPCHK(c, dalloc(&pp.d_dtf2, 2 * npix));
+        HIPCHK(c, dalloc(&pp.d_split, 4));
+        HIPCHK(c, hipMemset(pp.d_split, 0, 4 * sizeof(int)));
         HIPCHK(c, hipHostMalloc((void **)&pp.h_done, sizeof(unsigned long long),
                                 hipHostMallocMapped | hipHostMallocCoherent));
         HIPCHK(c, hipHostGetDevicePointer((void **)&pp.h_done_dev, pp.h_done, 0));
@@ -2374,9 +2389,20 @@ static int enqueue_raw_chunk(hpe_ctx *c, int P, int refine, double *d_state, con
                                 pp.d_obs + nxt, pp.d_info + nxt);
         pa.raw_row = c->d_seq_cur + 1;
         pa.raw_stride = npix;
+        // the split transform: this launch scans the next frame backward from the forward
+        // values the previous launch (or the prologue) left in that frame's parity, and the
+        // frame after it (if the sequence has one: a device word, not the graph) forward
+        PrepSplit ps{};
+        if (c->prep_split) {
+            pa.dtf = pp.d_dtf2 + nxt * npix;
+            ps.dtf_next = pp.d_dtf2 + cur * npix;
+            ps.r0 = pp.d_split + nxt;
+            ps.r0_next = pp.d_split + cur;
+            ps.seq_n = pp.d_split + 2;
+        }
         c->obs_dev = pp.d_obs + cur;
         if (refine || next)  // testmodel.cpp:126 (+ next_frame of the following iteration)
-            rc = refine_launch(c, d_state, pp.fr[cur].n_max, refine, next ? &pa : nullptr);
+            rc = refine_launch(c, d_state, pp.fr[cur].n_max, refine, next ? &pa : nullptr, &ps);
         DevObs on{};
         on.n = pp.fr[cur].n_max;  // a bound on n decides the kernel forms
         c->ss.defer = refine && i + 1 < k;  // the next frame's refine takes the exchange's pick
@@ -2421,9 +2447,18 @@ int hpe_track_raw_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state,
     if ((rc = upload_bounds(c))) return rc;
     // frame 0 prepared on the tracking stream, the row cursor at 0
     HIPCHK(c, hipMemsetAsync(c->d_seq_cur, 0, 2 * sizeof(int), c->stream));
-    const PrepArgs p0 = prep_args(c, pp.fr[0], d_raw_mm, pp.to_cm, pp.downsample, focal, pp.d_obs,
-                                  pp.d_info);
-    hipLaunchKernelGGL(k_prepare, dim3(PREP_WG), dim3(PREP_NT), 0, c->stream, p0);
+    PrepArgs p0 = prep_args(c, pp.fr[0], d_raw_mm, pp.to_cm, pp.downsample, focal, pp.d_obs,
+                            pp.d_info);
+    if (c->prep_split) {  // + the sequence length and frame 1's forward scan (parity 1)
+        p0.raw_stride = npix;
+        PrepSplit s0{};
+        s0.dtf_next = pp.d_dtf2 + npix;
+        s0.r0_next = pp.d_split + 1;
+        s0.seq_n = pp.d_split + 2;
+        hipLaunchKernelGGL(k_prepare_seq, dim3(PREP_WG + 1), dim3(PREP_NT), 0, c->stream, p0, s0, n);
+    } else {
+        hipLaunchKernelGGL(k_prepare, dim3(PREP_WG), dim3(PREP_NT), 0, c->stream, p0);
+    }
     HIPCHK(c, hipGetLastError());
     const int K = frames_per_graph ? frames_per_graph : HPE_SEQ_CHUNK;
     const int staged = pp.fr[0].n_max <= RF_STAGE_MAX;
@@ -2483,6 +2518,36 @@ int hpe_track_raw_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state,
     if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
     c->seq_done_valid = true;
+    return HPE_OK;
+}
+
+int hpe_pipe_readback(hpe_ctx *c, int parity, double *depth_cm, float *dt, double *cloud,
+                      int32_t *n_out, double *scale_out, double *dtmax_out) {
+    if (!c) return HPE_E_ARG;
+    hpe_ctx::Pipe &pp = c->pipe;
+    if (parity < 0 || parity > 1 || !pp.d_obs || !pp.fr[parity].depth)
+        return fail(c, HPE_E_ARG, "pipeline buffer %d holds no frame", parity);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const Slot &s = pp.fr[parity];
+    PrepInfo pi;
+    HIPCHK(c, hipMemcpy(&pi, pp.d_info + parity, sizeof(pi), hipMemcpyDeviceToHost));
+    if (pi.n < 0 || pi.n > s.cap) return fail(c, HPE_E_STATE, "pipeline buffer %d: n = %d", parity, pi.n);
+    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
+    if (depth_cm) HIPCHK(c, hipMemcpy(depth_cm, s.depth, sizeof(double) * npix, hipMemcpyDeviceToHost));
+    if (dt) HIPCHK(c, hipMemcpy(dt, s.dt, sizeof(float) * npix, hipMemcpyDeviceToHost));
+    if (cloud && pi.n > 0) {
+        const size_t n = (size_t)pi.n;
+        std::vector<double> soa(3 * n);
+        HIPCHK(c, hipMemcpy(soa.data(), s.cx, sizeof(double) * n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(soa.data() + n, s.cy, sizeof(double) * n, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(soa.data() + 2 * n, s.cz, sizeof(double) * n, hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < n; ++p)
+            for (int q = 0; q < 3; ++q) cloud[3 * p + q] = soa[(size_t)q * n + p];
+    }
+    if (n_out) *n_out = pi.n;
+    if (scale_out) *scale_out = pi.scale;
+    if (dtmax_out) *dtmax_out = pi.dtmax;
     return HPE_OK;
 }
 

@@ -994,7 +994,7 @@ struct MwLeader {
 };
 
 // Workgroup 0: publish the next job (CORR: theta = rs.x0; FROZEN: rs.w[0..nn).th).
-__device__ void mw_publish(MwLeader &ml, RefineSm &rs, int type, int nn) {
+__device__ __forceinline__ void mw_publish(MwLeader &ml, RefineSm &rs, int type, int nn) {
     const int t = threadIdx.x, w = t >> 6, l = t & 63;
     if (type == MW_JOB_CORR) {
         if (t < HPE_DOF) ml.mw.job->th[0][t] = rs.x0[t];
@@ -1120,7 +1120,7 @@ __device__ __forceinline__ double eval_corr(RefineSm &rs, const DevObs &o, const
 
 // Helper workgroup h of a multi-workgroup refine launch: serve jobs until EXIT.
 template <bool RIGID>
-__device__ void mw_helper(const DevMw &mw, int h, const DevObs *__restrict__ og,
+__device__ __forceinline__ void mw_helper(const DevMw &mw, int h, const DevObs *__restrict__ og,
                           const DevHand *__restrict__ Hg, int32_t *__restrict__ match_g) {
     __shared__ FkSm nodes[MW_MAX_NODES];
     __shared__ RigidSm hq;  // RIGID: hand-frame centres, built from the first job's digits
@@ -1378,7 +1378,7 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
                                                   const DevHand *__restrict__ Hg,
                                                   int32_t *__restrict__ match_g,
                                                   int *__restrict__ evals_out, int do_refine,
-                                                  PrepArgs pa, DevMw mw, DevPick pk) {
+                                                  PrepArgs pa, DevMw mw, DevPick pk, PrepSplit ps) {
 #include "hpe_refine_body.inc"
 }
 
@@ -1464,6 +1464,7 @@ __global__ __launch_bounds__(RF_NT) void k_refine_b(double *__restrict__ states,
     const PrepArgs pa{};
     const DevMw mw{};
     const DevPick pk{};
+    const PrepSplit ps{};
 #include "hpe_refine_body.inc"
 }
 
@@ -1545,6 +1546,7 @@ __global__ __launch_bounds__(RF_NT) void k_refine_prep_b(double *__restrict__ st
     if (blockIdx.x >= 1) pa = lane_prep(tab, raw_base, cur, 1);
     const DevMw mw{};
     const DevPick pk{};
+    const PrepSplit ps{};
 #include "hpe_refine_body.inc"
 }
 static_assert(PREP_NT == RF_NT, "the preparation workgroups ride in the refine launch");

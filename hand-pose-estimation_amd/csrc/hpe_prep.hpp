@@ -14,7 +14,8 @@
 //   one DT workgroup: the chamfer raster scans by ONE wave, lane l holding columns
 //     5l..5l+4, rows in registers; the in-row dependency T_c = min(a_c, T_{c-1} + 1) is a
 //     prefix minimum (lane-serial over 5 columns, DPP across lanes).  Integer min-plus
-//     arithmetic: exactly the raster-scan values.
+//     arithmetic: exactly the raster-scan values.  Resident raw sequences split the two
+//     scans over consecutive launches, on two waves (prep_dt_split).
 // Results equal hpe_preprocess_depth bit for bit.  Hand-offs between workgroups follow
 // MI355X_MICROARCH.md (inter-workgroup visibility): every storing wave waits for its
 // stores, workgroup barrier, agent release, arrival counter; the last arriver acquires.
@@ -54,6 +55,15 @@ struct PrepArgs {
     // captured chunk graph serves every chunk; null: raw is the frame itself
     const int *raw_row;
     unsigned long long raw_stride;  // floats per raw frame
+};
+
+// The distance transform split over two launches (resident raw sequences; prep_dt_split).
+// The frame a launch prepares has its forward scan in PrepArgs::dtf already; the scratch is
+// double-buffered by frame parity.
+struct PrepSplit {
+    int *dtf_next;      // forward scan of the frame after the one prepared; null: no split
+    int *r0, *r0_next;  // first hand row of the frame prepared / of the one after it
+    int *seq_n;         // frames in the sequence (the call's prologue stores it)
 };
 
 // LDS layout: chunk[PREP_CH] doubles | acc1, flag (64 B) | wcnt, hcnt | mask bits | wmax
@@ -300,170 +310,95 @@ __device__ __forceinline__ void prep_dt(const PrepArgs &a, unsigned char *lds) {
     unsigned *msk = (unsigned *)(lds + PREP_CH * 8 + 64 + 2 * (PREP_NT / 64) * 4);
     float *wmaxp = (float *)(msk + W * H / 32);
     const int t = threadIdx.x, l = t & 63;
-    // hand = non-zero raw depth: 150 pixels per thread in three batches of 50 loads, the
-    // next batch in flight while one is folded (unconditional: no branch splits them into
-    // one round trip each; the raw frame may sit in pinned host memory, behind PCIe)
-    constexpr int NPT = W * H / PREP_NT, B = NPT / 3;  // 150 pixels per thread, 3 batches
-    static_assert(W * H % PREP_NT == 0 && NPT % 3 == 0, "whole batches");
-    float va[B], vb[B];
-    auto issue = [&](float (&v)[B], int k0) {
-#pragma unroll
-        for (int q = 0; q < B; ++q) v[q] = a.raw[(k0 + q) * PREP_NT + t];
-    };
-    auto fold = [&](const float (&v)[B], int k0) {
-#pragma unroll
-        for (int q = 0; q < B; ++q) {
-            const unsigned long long bm = __ballot(v[q] != 0.f);
-            const int pix = (k0 + q) * PREP_NT + t;
-            if ((l & 31) == 0) msk[pix >> 5] = (unsigned)(bm >> (l & 32));
-        }
-    };
-    issue(va, 0);
-    issue(vb, B);
-    fold(va, 0);
-    issue(va, 2 * B);  // the third batch lands while the second is folded
-    fold(vb, B);
-    fold(va, 2 * B);
-    // the band workgroups hold their own raw reads until here (a scheduling hint only):
-    // when the frame sits in host memory the DT, the longer chain, gets PCIe to itself
-    if (t == 0) __hip_atomic_store(&a.ctr[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int *rfirst = (int *)(msk + W * H / 32 + 1);
-    if (t == 0) {
-        msk[W * H / 32] = 0u;  // the two-word window of the last pixels
-        *rfirst = 0x7FFFFFFF;
-    }
-    __syncthreads();
-    for (int k = t; k < W * H / 32; k += PREP_NT) {  // first mask word holding a hand pixel
-        if (msk[k] != 0u) {
-            atomicMin(rfirst, k);
-            break;
-        }
-    }
-    __syncthreads();
-    // The forward pass starts at the first row r0 holding a hand pixel.  Above it every
-    // forward value is >= DT_INIT; with a hand pixel anywhere, every pixel's final value is
-    // finite (< DT_INIT: a forward path right/down from some hand pixel, then a backward
-    // path up/left, stays inside the image), so forward values >= DT_INIT never win a min
-    // and any such value gives the same result: the rows above r0 start from DT_INIT, as
-    // row 0 does, and the backward pass reads DT_INIT for them.  No hand pixel: r0 = 0.
-    const int r0 = (*rfirst == 0x7FFFFFFF) ? 0 : *rfirst / (W / 32);
+#define DT_RAW a.raw
+#define DT_HINT &a.ctr[2]
+#define DT_FWD a.dtf
+#define DT_OUT a.dt
+#define DT_PART 0
+#include "hpe_dt_parts.inc"
     if (t < 64) {
-        // forward pass: lane l owns columns c0..c0+4; u1 / u2 = rows r-1 / r-2 at columns
-        // c0-2 .. c0+6 (halo from the neighbour lanes)
-        const int c0 = 5 * l;
-        int u1[9], u2[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) u1[i] = u2[i] = DT_INIT;
-        // rows in pairs from the even row at or above r0 (a row above r0 scanned from
-        // DT_INIT is as good as unscanned, see above), two rows per trip
-        static_assert(H % 2 == 0, "forward rows in pairs");
-        auto row = [&](int r) {
-            const int pix0 = r * W + c0;
-            const unsigned long long mw =
-                ((unsigned long long)msk[(pix0 >> 5) + 1] << 32) | msk[pix0 >> 5];
-            const unsigned hb = (unsigned)(mw >> (pix0 & 31));
-            int q[5], p[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const int i = k + 2;
-                // grouped by weight: min over the LONG, DIAG and HV neighbours, then the add
-                const int mL = min(min(u2[i - 1], u2[i + 1]), min(u1[i - 2], u1[i + 2]));
-                const int mD = min(u1[i - 1], u1[i + 1]);
-                const int av = min(min(mL + DT_LONG, mD + DT_DIAG), u1[i] + DT_HV);
-                // hand pixel -> 0: bit k sign-extended, then av & ~mask in one v_bfi
-                const int m = __builtin_amdgcn_sbfe((int)hb, k, 1);
-                q[k] = (av & ~m) - DT_HV * (c0 + k);
-            }
-            scan5_min(q, p);  // p[k] = min(q[0..k]), depth 2
-            const int ex = from_left(wave_prefix_min(p[4]), 0x7FFFFFFF);  // lanes < l
-            int T[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                // min(min(p, ex) + HV c, INIT + HV (c+1)) == min(p, ex, INIT + HV) + HV c
-                T[k] = min(min(p[k], ex), DT_INIT + DT_HV) + DT_HV * (c0 + k);
-                a.dtf[pix0 + k] = T[k];
-            }
-#pragma unroll
-            for (int i = 0; i < 9; ++i) u2[i] = u1[i];
-            u1[0] = from_left(T[3], DT_INIT);
-            u1[1] = from_left(T[4], DT_INIT);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) u1[k + 2] = T[k];
-            u1[7] = from_right(T[0], DT_INIT);
-            u1[8] = from_right(T[1], DT_INIT);
-        };
-        for (int r = r0 & ~1; r < H; r += 2) {
-            row(r);
-            row(r + 1);
-        }
+#define DT_PART 1
+#include "hpe_dt_parts.inc"
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        // backward pass: lane l owns columns cb-k (cb = 319 - 5l, k = 0..4), i.e. scan
-        // index j = 5l + k; d1 / d2 = rows r+1 / r+2 at scan positions j-2 .. j+6
-        const int cb = W - 1 - 5 * l;
-        int d1[9], d2[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) d1[i] = d2[i] = DT_INIT;
-        float mx = 0.f;
-        const float sc = 1.f / 65536;
-        // forward values three rows ahead: row r's values are loaded while row r+3 is
-        // scanned, into the register slot row r+3 just consumed (three slots, the loop
-        // unrolled by three, so no register copy makes a row wait for newer loads);
-        // unconditional loads of a clamped row
-        int f0[5], f1[5], f2[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            f0[k] = a.dtf[(H - 1) * W + cb - k];
-            f1[k] = a.dtf[(H - 2) * W + cb - k];
-            f2[k] = a.dtf[(H - 3) * W + cb - k];
-        }
-        auto step = [&](int r, int (&fs)[5]) {
-            int fw[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) fw[k] = (r >= r0) ? fs[k] : DT_INIT;  // rows above r0: not scanned
-            const int rn = r >= 3 ? r - 3 : 0;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) fs[k] = a.dtf[rn * W + cb - k];
-            int q[5], p[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const int i = k + 2;
-                const int mL = min(min(d2[i - 1], d2[i + 1]), min(d1[i - 2], d1[i + 2]));
-                const int mD = min(d1[i - 1], d1[i + 1]);
-                const int bv = min(min(fw[k], mL + DT_LONG), min(mD + DT_DIAG, d1[i] + DT_HV));
-                q[k] = bv - DT_HV * (5 * l + k);
-            }
-            scan5_min(q, p);
-            const int ex = from_left(wave_prefix_min(p[4]), 0x7FFFFFFF);
-            int T[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const int j = 5 * l + k;
-                T[k] = min(min(p[k], ex), DT_INIT + DT_HV) + DT_HV * j;
-                const float v = (float)T[k] * sc;
-                a.dt[r * W + cb - k] = v;
-                mx = v > mx ? v : mx;
-            }
-#pragma unroll
-            for (int i = 0; i < 9; ++i) d2[i] = d1[i];
-            d1[0] = from_left(T[3], DT_INIT);
-            d1[1] = from_left(T[4], DT_INIT);
-#pragma unroll
-            for (int k = 0; k < 5; ++k) d1[k + 2] = T[k];
-            d1[7] = from_right(T[0], DT_INIT);
-            d1[8] = from_right(T[1], DT_INIT);
-        };
-        static_assert(H % 3 == 0, "backward rows in threes");
-        for (int r = H - 1; r >= 2; r -= 3) {
-            step(r, f0);
-            step(r - 1, f1);
-            step(r - 2, f2);
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const float o = __shfl_xor(mx, off);
-            mx = o > mx ? o : mx;
-        }
+#define DT_PART 2
+#include "hpe_dt_parts.inc"
         if (l == 0) *wmaxp = mx;
+    }
+    __syncthreads();
+    if (t == 0) a.info->dtmax = *wmaxp;
+}
+#undef DT_RAW
+#undef DT_HINT
+#undef DT_FWD
+#undef DT_OUT
+
+// ---- the transform split over two launches (resident raw sequences).  The
+// backward scan starts where the forward scan ends, so one frame's transform cannot be
+// shortened; but a launch can scan the frame it prepares backward, from forward values the
+// PREVIOUS launch left, beside the forward scan of the frame after it for the NEXT launch:
+// two independent half-transforms on two waves, the hand-off a kernel boundary.
+// LDS words after the mask bits: [0] window / prep_dt's max, [1] first hand word, [2] the
+// split transform's max (its own word: wave 0 may still read the window).
+
+// Forward half by the whole workgroup: the mask of `raw` and its first hand row (all waves),
+// then the forward scan by wave 0 into dtf and the row into *r0_out.
+__device__ __forceinline__ void dt_forward_half(const float *raw, int *dtf, int *r0_out,
+                                                unsigned char *lds) {
+    constexpr int W = HPE_IMG_W, H = HPE_IMG_H;
+    unsigned *msk = (unsigned *)(lds + PREP_CH * 8 + 64 + 2 * (PREP_NT / 64) * 4);
+    const int t = threadIdx.x, l = t & 63;
+#define DT_RAW raw
+#define DT_FWD dtf
+#define DT_PART 0
+#include "hpe_dt_parts.inc"
+    if (t < 64) {
+#define DT_PART 1
+#include "hpe_dt_parts.inc"
+        if (l == 0) *r0_out = r0;
+    }
+#undef DT_RAW
+#undef DT_FWD
+}
+
+// The DT workgroup of a split preparation: wave 1 scans the frame being prepared backward
+// from a.dtf / *ps.r0 into a.dt and dtmax; the workgroup runs the forward half of the frame
+// after it (raw row *raw_row + 2) unless the sequence ends before it.
+__device__ __forceinline__ void prep_dt_split(const PrepArgs &a, const PrepSplit &ps,
+                                              unsigned char *lds) {
+    constexpr int W = HPE_IMG_W, H = HPE_IMG_H;
+    unsigned *msk = (unsigned *)(lds + PREP_CH * 8 + 64 + 2 * (PREP_NT / 64) * 4);
+    float *wmaxp = (float *)(msk + W * H / 32 + 2);
+    const int t = threadIdx.x, l = t & 63;
+    // this workgroup reads another raw frame than the bands do: they need not wait for it
+    if (t == 0) __hip_atomic_store(&a.ctr[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // decided from memory, and it decides barriers: uniform by readfirstlane
+    const bool fwd = __builtin_amdgcn_readfirstlane(*a.raw_row + 2 < *ps.seq_n ? 1 : 0) != 0;
+    // diagnostic build: the halves' spans from the workgroup's start, stamps 29 / 31 (100 MHz)
+    const unsigned long long ts = HPE_STAMPS ? __builtin_amdgcn_s_memrealtime() : 0;
+    auto span = [&](int k) {
+        if (HPE_STAMPS && l == 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            atomicAdd(&hpe_stamps[k], __builtin_amdgcn_s_memrealtime() - ts);
+            atomicAdd(&hpe_stamps[32 + k], 1ull);
+        }
+    };
+    // a.raw is raw row + 1 (prep_workgroup).  Every wave folds the mask (its barriers take the
+    // whole workgroup, a few microseconds); then waves 0 and 1 scan side by side
+    if (fwd) {
+        dt_forward_half(a.raw + a.raw_stride, ps.dtf_next, ps.r0_next, lds);
+        if (t < 64) span(29);
+    }
+    if ((t >> 6) == 1) {
+        const int r0 = __builtin_amdgcn_readfirstlane(*ps.r0);
+#define DT_FWD a.dtf
+#define DT_OUT a.dt
+#define DT_PART 2
+#include "hpe_dt_parts.inc"
+#undef DT_FWD
+#undef DT_OUT
+        if (l == 0) *wmaxp = mx;
+        span(31);
     }
     __syncthreads();
     if (t == 0) a.info->dtmax = *wmaxp;
@@ -488,8 +423,9 @@ __device__ __forceinline__ void prep_write_descriptor(const PrepArgs &a) {
 }
 
 // One preparing workgroup (index g in [0, PREP_WG)); the last to finish writes the
-// descriptor.
-__device__ __forceinline__ void prep_workgroup(const PrepArgs &a0, int g, unsigned char *lds) {
+// descriptor.  With a split (ps and ps->dtf_next) the DT workgroup runs prep_dt_split.
+__device__ __forceinline__ void prep_workgroup(const PrepArgs &a0, int g, unsigned char *lds,
+                                               const PrepSplit *ps = nullptr) {
     int *flag = (int *)(lds + PREP_CH * 8 + 8);
     PrepArgs a = a0;
     if (a0.raw_row) a.raw = a0.raw + (size_t)(*a0.raw_row + 1) * a0.raw_stride;
@@ -497,6 +433,8 @@ __device__ __forceinline__ void prep_workgroup(const PrepArgs &a0, int g, unsign
         prep_band(a, g, lds);
         if (!prep_arrive_last(a.ctr, PREP_BANDS, flag)) return;
         prep_merge(a, lds);
+    } else if (ps && ps->dtf_next) {
+        prep_dt_split(a, *ps, lds);
     } else {
         prep_dt(a, lds);
     }
@@ -509,4 +447,19 @@ __device__ __forceinline__ void prep_workgroup(const PrepArgs &a0, int g, unsign
 __global__ __launch_bounds__(PREP_NT) void k_prepare(PrepArgs a) {
     __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
     prep_workgroup(a, blockIdx.x, lds);
+}
+
+// Prologue of a resident raw sequence with the split transform, grid PREP_WG + 1: k_prepare's
+// workgroups on frame 0 (a.raw), and one more that stores the sequence length n and, when
+// there is a frame 1 (a.raw + a.raw_stride), its mask and forward scan for the first refine
+// launch's backward half.
+__global__ __launch_bounds__(PREP_NT) void k_prepare_seq(PrepArgs a, PrepSplit ps, int n) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    if (blockIdx.x < PREP_WG) {
+        prep_workgroup(a, blockIdx.x, lds);
+        return;
+    }
+    if (threadIdx.x == 0) *ps.seq_n = n;
+    if (n < 2) return;  // a kernel argument: uniform
+    dt_forward_half(a.raw + a.raw_stride, ps.dtf_next, ps.r0_next, lds);
 }

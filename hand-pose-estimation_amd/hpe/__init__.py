@@ -239,6 +239,18 @@ class Context:
         return dict(depth_cm=depth, dt=dt, cloud=cloud[:n.value].copy(), scale=scale.value,
                     dtmax=dtmax.value)
 
+    def pipe_readback(self, parity):
+        """frame_readback of the pipeline's prepared-frame buffer `parity` (frame f of a
+        pipelined or resident raw sequence is prepared into buffer f & 1)."""
+        depth = np.zeros((IMG_H, IMG_W)); dt = np.zeros((IMG_H, IMG_W), dtype=np.float32)
+        cloud = np.zeros((IMG_H * IMG_W, 3)); n = C.c_int32(0)
+        scale = C.c_double(0); dtmax = C.c_double(0)
+        self.check(self.lib.hpe_pipe_readback(self._h, int(parity), ptr(depth, C.c_double),
+                                              ptr(dt, C.c_float), ptr(cloud, C.c_double),
+                                              C.byref(n), C.byref(scale), C.byref(dtmax)))
+        return dict(depth_cm=depth, dt=dt, cloud=cloud[:n.value].copy(), scale=scale.value,
+                    dtmax=dtmax.value)
+
     def render_depth(self, theta, focal=241.42):
         th = _lib.as_f64(theta, (26,))
         out = np.zeros((IMG_H, IMG_W), dtype=np.float32)

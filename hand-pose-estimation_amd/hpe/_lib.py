@@ -57,6 +57,7 @@ SIGNATURES = {
     "hpe_track_raw_sequence_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                              C.c_int, C.c_void_p]),
+    "hpe_pipe_readback": (C.c_int, [C.c_void_p, C.c_int, dp, fp, dp, ip, dp, dp]),
     "hpe_track_raw_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
                                           C.c_double, C.c_int, C.c_void_p]),

@@ -322,6 +322,13 @@ int hpe_track_raw_sequence_dev(hpe_ctx *ctx, int num_p, int refine, double *d_st
                                const float *d_raw_mm, int n, int to_cm, int downsample,
                                double focal, int frames_per_graph, double *d_hist);
 
+/* Copies one of the pipeline's two prepared-frame buffers (hpe_track_pipelined,
+ * hpe_track_raw_sequence_dev: frame f of a sequence is prepared into buffer f & 1) back to the
+ * host, as hpe_frame_readback does for a slot (tests, debugging); synchronises.
+ * cloud: n*3 doubles (capacity 76800*3); any output may be NULL. */
+int hpe_pipe_readback(hpe_ctx *ctx, int parity, double *depth_cm, float *dt, double *cloud,
+                      int32_t *n_out, double *scale_out, double *dtmax_out);
+
 /* B resident raw sequences tracked in the SAME launches (what a multi-camera rig, two hands in
  * one depth stream or a dataset run delivers): lane b is
  *   hpe_track_raw_sequence_dev(ctx, num_p, refine, d_states + 27 b, d_raw_mm[b], n, to_cm,

@@ -38,6 +38,7 @@ names = {4: "gen: prologue (og + hand)", 5: "gen: block-0 span (cycles)",
          20: "refine: corr eval", 21: "refine: grad evals", 22: "refine: goldstein",
          23: "refine: iter glue", 24: "prep (fused): band workgroups (incl. merge)",
          25: "prep (fused): DT workgroup", 19: "goldstein: speculated round",
+         29: "prep (split DT): forward half (100MHz ticks)", 31: "prep (split DT): backward half (100MHz ticks)",
          26: "opt: m=0 corr eval", 27: "opt: grad (2 waves)", 28: "opt: step tail (+m=0 re-match)"}
 tot = np.zeros(64)
 for f in range(1, nfr + 1):
