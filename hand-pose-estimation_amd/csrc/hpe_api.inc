@@ -103,6 +103,52 @@ struct OptState {  // pso_optimise buffers, rebuilt when P / G / seed / cloud bo
     unsigned *ctr = nullptr;
 };
 
+// What a captured tracking graph depends on besides the context's seed and epoch: one key for
+// the six tracking calls, a field a call does not use left zero.  A launch decision that is not
+// in the key replays the wrong kernels (a cached chunk of 250-point frames on 400-point ones).
+struct GraphKey {
+    int P, G, refine, k;
+    // bit i: frame i of the chunk takes the staged refine (n_max <= RF_STAGE_MAX) / the FILT
+    // kernels (n_max > HPE_NT / 2, launch_pso's choice)
+    unsigned staged, filt;
+    int parity, tail_next, next, cur, B, to_cm, downsample;
+    double focal;
+    const void *in;  // the raw frames' base
+    double *state, *hist;  // a lane's or the batch's states; the history rows
+    bool operator==(const GraphKey &o) const {  // written out: the struct has padding
+        return P == o.P && G == o.G && refine == o.refine && k == o.k && staged == o.staged &&
+               filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
+               next == o.next && cur == o.cur && B == o.B && to_cm == o.to_cm &&
+               downsample == o.downsample && focal == o.focal && in == o.in &&
+               state == o.state && hist == o.hist;
+    }
+};
+
+// The fields every call sets; the rest zero until the call fills in its own.
+GraphKey graph_key(int P, int G, int refine, double *state, double *hist = nullptr) {
+    GraphKey key{};
+    key.P = P;
+    key.G = G;
+    key.refine = refine;
+    key.state = state;
+    key.hist = hist;
+    return key;
+}
+
+// One tracking call's captured graphs (run_graphed).  At `cap` entries the next capture empties
+// the cache; drop_stale: it also drops the graphs of another seed or epoch, which never match.
+struct GraphCache {
+    struct Entry {
+        GraphKey key;
+        uint64_t seed;
+        unsigned epoch;
+        hipGraphExec_t exec;
+    };
+    std::vector<Entry> entries;
+    size_t cap;
+    bool drop_stale;
+};
+
 }  // namespace
 
 struct hpe_ctx {
@@ -131,14 +177,15 @@ struct hpe_ctx {
     // the descriptor the kernels read: d_obs_active, or during a pipelined frame the
     // current frame buffer's own descriptor (one captured graph per buffer parity)
     DevObs *obs_dev = nullptr;
-    // one captured tracked frame (refine + pso_evolve + cal_cost), replayed per frame
-    struct Graph {
-        hipGraphExec_t exec = nullptr;
-        int P = 0, G = 0, refine = 0, staged = 0;
-        double *state = nullptr;
-        uint64_t seed = 0;
-        unsigned epoch = 0;
-    } graph;
+    // the captured graphs, a cache per tracking call:
+    // GC_FRAME: one tracked frame (refine + pso_evolve + cal_cost), replayed per frame
+    // GC_PIPE: a pipelined frame, per buffer parity and whether it prepares a next frame
+    // GC_SEQ, GC_RAW: a chunk of resident frames / of resident raw frames, keyed by its shape
+    //     (not its slots)
+    // GC_BATCH, GC_RAW_BATCH: the same chunks for B lanes
+    enum { GC_FRAME, GC_PIPE, GC_SEQ, GC_RAW, GC_BATCH, GC_RAW_BATCH, GC_N };
+    GraphCache graphs[GC_N] = {{{}, 1, false}, {{}, 16, false}, {{}, 64, true},
+                               {{}, 64, true}, {{}, 64, true}, {{}, 64, true}};
     // device preprocessing (hpe_prepare_frame): its own stream, one frame in flight at a time
     hipStream_t prep = nullptr;
     float *d_raw = nullptr;
@@ -183,51 +230,11 @@ struct hpe_ctx {
         int cur = -1, to_cm = 1, downsample = 1;
         double focal = 241.42;
     } pipe;
-    struct GraphEntry {
-        int P, G, refine, staged, next, cur;
-        double *state;
-        uint64_t seed;
-        unsigned epoch;
-        hipGraphExec_t exec;
-    };
-    std::vector<GraphEntry> pgraphs;
-    // offline sequences (hpe_track_sequence_dev): one graph per chunk of resident frames
-    struct SeqGraph {
-        int P, G, refine, k;
-        unsigned staged;
-        unsigned filt;  // bit i: frame i's cloud bound is above HPE_NT / 2 (launch_pso's FILT forms)
-        double *state, *hist;
-        uint64_t seed;
-        unsigned epoch;
-        hipGraphExec_t exec;
-    };
-    std::vector<SeqGraph> sgraphs;
-    // resident raw sequences (hpe_track_raw_sequence_dev): one graph per chunk shape
-    struct RawGraph {
-        int P, G, refine, k, parity, tail_next, staged, to_cm, downsample;
-        double focal;
-        const float *raw;
-        double *state, *hist;
-        uint64_t seed;
-        unsigned epoch;
-        hipGraphExec_t exec;
-    };
-    std::vector<RawGraph> rgraphs;
     // batched lanes (hpe_track_batch_dev): per lane the current-frame descriptor the chunk
     // graphs read, the cursor {slot, history row} and the refine evaluation counter
     DevObs *d_bobs = nullptr;  // [HPE_BATCH_MAX]
     int *d_bcur = nullptr;     // [HPE_BATCH_MAX][2]
     int *d_bevals = nullptr;   // [HPE_BATCH_MAX][HPE_EVALS_N]
-    struct BatchGraph {
-        int P, G, refine, k;
-        unsigned filt;  // bit i: frame i of the chunk takes the FILT kernels
-        int B;
-        double *states, *hist;
-        uint64_t seed;
-        unsigned epoch;
-        hipGraphExec_t exec;
-    };
-    std::vector<BatchGraph> bgraphs;
     // batched raw lanes (hpe_track_raw_batch_dev): per lane one arena holding two frame buffers
     // (depth, DT, a 250-point cloud each) and the preparation scratch (tmp, ctb, dtf); the
     // descriptors, PrepInfo and PrepArgs tables by [parity][lane]; the lane's hand-off counters
@@ -244,15 +251,6 @@ struct hpe_ctx {
         const float **d_raw = nullptr;  // [HPE_BATCH_MAX]
         int *d_cur = nullptr;         // [HPE_BATCH_MAX][2]
     } rb;
-    struct RawBatchGraph {
-        int P, G, refine, k, parity, tail_next, B, to_cm, downsample;
-        double focal;
-        double *states, *hist;
-        uint64_t seed;
-        unsigned epoch;
-        hipGraphExec_t exec;
-    };
-    std::vector<RawBatchGraph> rbgraphs;
     hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
     bool pipe_counting = false;  // set while a pipelined frame is enqueued (k_pso_final args)
@@ -737,6 +735,49 @@ static int end_capture(hpe_ctx *c, int rc, hipGraphExec_t *exec, bool *direct) {
     return fail(c, HPE_E_HIP, "graph instantiate: %s", hipGetErrorString(ei));
 }
 
+// Run the launches enqueue() makes on the context stream: directly (direct_launches, or the
+// capture's exchange fallback), or as gc's graph of this key, seed and epoch -- replayed, or
+// captured now and kept.  Before the new graph is kept, the cache's stale graphs go (drop_stale)
+// and, at its cap, all of them.
+template <class Enq>
+static int run_graphed(hpe_ctx *c, GraphCache &gc, const GraphKey &key, Enq enqueue) {
+    if (direct_launches(c)) return enqueue();
+    std::vector<GraphCache::Entry> &es = gc.entries;
+    hipGraphExec_t exec = nullptr;
+    for (const auto &e : es)
+        if (e.key == key && e.seed == c->seed && e.epoch == c->epoch) exec = e.exec;
+    if (!exec) {
+        HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        ++c->captures;
+        bool direct = false;
+        if (int rc = end_capture(c, enqueue(), &exec, &direct)) return rc;
+        if (direct) return enqueue();
+        const auto stale = [&](const GraphCache::Entry &e) {
+            return gc.drop_stale && (e.epoch != c->epoch || e.seed != c->seed);
+        };
+        size_t live = 0;
+        for (const auto &e : es) live += !stale(e);
+        const bool full = live >= gc.cap;
+        // A graph about to be destroyed may still be in flight: not every epoch bump comes
+        // from a reallocation that drained the device (hpe_set_refine_exact and
+        // hpe_set_exchange only bump it).  Wait for the stream first, once, and only when
+        // there is something to destroy.
+        if (full || live < es.size()) HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t q = 0; q < es.size();) {
+            if (full || stale(es[q])) {
+                (void)hipGraphExecDestroy(es[q].exec);
+                es[q] = es.back();
+                es.pop_back();
+            } else {
+                ++q;
+            }
+        }
+        es.push_back({key, c->seed, c->epoch, exec});
+    }
+    HIPCHK(c, hipGraphLaunch(exec, c->stream));
+    return HPE_OK;
+}
+
 // pso_evolve on the device: x0 and the result live in d_state (27 doubles).
 // tail: fuse cal_cost(bestp) (and the descriptor hand-back) into the final kernel.
 // hist (tail only): the frame's {bestp, cost} also stored there (offline sequences).
@@ -928,18 +969,10 @@ int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
 // subswarm exchange hold RCCL resources, so they go before the communicator does.
 static void drop_graphs(hpe_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->graph.exec) (void)hipGraphExecDestroy(c->graph.exec);
-    c->graph.exec = nullptr;
-    for (auto &ge : c->pgraphs) (void)hipGraphExecDestroy(ge.exec);
-    for (auto &sg : c->sgraphs) (void)hipGraphExecDestroy(sg.exec);
-    for (auto &rg : c->rgraphs) (void)hipGraphExecDestroy(rg.exec);
-    for (auto &bg : c->bgraphs) (void)hipGraphExecDestroy(bg.exec);
-    for (auto &rg : c->rbgraphs) (void)hipGraphExecDestroy(rg.exec);
-    c->rbgraphs.clear();
-    c->bgraphs.clear();
-    c->pgraphs.clear();
-    c->sgraphs.clear();
-    c->rgraphs.clear();
+    for (GraphCache &gc : c->graphs) {
+        for (auto &e : gc.entries) (void)hipGraphExecDestroy(e.exec);
+        gc.entries.clear();
+    }
 }
 
 int hpe_destroy(hpe_ctx *c) {
@@ -1595,6 +1628,41 @@ static int refine_dev(hpe_ctx *c, double *d_x0, const DevObs &o) {
     return refine_launch(c, d_x0, o.n, 1, nullptr);
 }
 
+// What the four chunked tracking calls (sequence, raw sequence and their batches) check first.
+static int check_chunked_call(hpe_ctx *c, int P, int frames_per_graph) {
+    if (int rc = mw_check_async(c)) return rc;
+    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
+    if (int rc = check_P(c, P)) return rc;
+    if (frames_per_graph < 0 || frames_per_graph > HPE_SEQ_MAX_CHUNK)
+        return fail(c, HPE_E_ARG, "frames_per_graph %d out of range [0, %d]", frames_per_graph,
+                    HPE_SEQ_MAX_CHUNK);
+    return HPE_OK;
+}
+
+// ... and the two batch calls after it: the lane count, and what a batch runs without.
+static int check_batch_call(hpe_ctx *c, int P, int B) {
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (pso_wave_form(c, P))
+        return fail(c, HPE_E_ARG, "num_p %d takes the wave form: a batch needs the workgroup form "
+                    "(num_p < %d)", P, c->wave_form_min_p);
+    if (c->ss.transport())
+        return fail(c, HPE_E_STATE, "a subswarm transport is live: a batch runs without the "
+                    "exchange (hpe_subswarm_fini)");
+    if (c->xch_every > 0)
+        return fail(c, HPE_E_STATE, "the per-generation exchange is on (hpe_set_exchange)");
+    return HPE_OK;
+}
+
+// The chunked calls' trailer: the call is its frames' last reader, and hpe_prepare_frame waits
+// for this event before it writes a slot.
+static int mark_seq_done(hpe_ctx *c) {
+    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
+    c->seq_done_valid = true;
+    return HPE_OK;
+}
+
 int hpe_pick_best(hpe_ctx *c, const double *d_gathered, int world, double *d_state) {
     if (!c) return HPE_E_ARG;
     if (!d_gathered || !d_state || world < 1 || world > 64)
@@ -1835,31 +1903,10 @@ int hpe_track_frame_dev(hpe_ctx *c, int P, int refine, double *d_state) {
     if ((rc = ensure_match(c, (size_t)HPE_IMG_H * HPE_IMG_W))) return rc;
     if ((rc = ensure_swarm(c, P, G))) return rc;
     if ((rc = upload_bounds(c))) return rc;
-    if (direct_launches(c)) return enqueue_frame(c, P, refine, d_state, o);
-    hpe_ctx::Graph &gr = c->graph;
-    const int staged = o.n <= RF_STAGE_MAX;
-    if (!gr.exec || gr.P != P || gr.G != G || gr.refine != refine || gr.staged != staged ||
-        gr.state != d_state || gr.seed != c->seed || gr.epoch != c->epoch) {
-        if (gr.exec) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipGraphExecDestroy(gr.exec));
-            gr.exec = nullptr;
-        }
-        HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        ++c->captures;
-        bool direct = false;
-        if ((rc = end_capture(c, enqueue_frame(c, P, refine, d_state, o), &gr.exec, &direct))) return rc;
-        if (direct) return enqueue_frame(c, P, refine, d_state, o);
-        gr.P = P;
-        gr.G = G;
-        gr.refine = refine;
-        gr.staged = staged;
-        gr.state = d_state;
-        gr.seed = c->seed;
-        gr.epoch = c->epoch;
-    }
-    HIPCHK(c, hipGraphLaunch(gr.exec, c->stream));
-    return HPE_OK;
+    GraphKey key = graph_key(P, G, refine, d_state);
+    key.staged = o.n <= RF_STAGE_MAX;
+    return run_graphed(c, c->graphs[hpe_ctx::GC_FRAME], key,
+                       [&] { return enqueue_frame(c, P, refine, d_state, o); });
 }
 
 int hpe_track_frame(hpe_ctx *c, int P, int refine, double x0[26], double *cost_out) {
@@ -2015,17 +2062,12 @@ static int enqueue_seq_chunk(hpe_ctx *c, int P, int refine, double *d_state, int
 int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int first_slot,
                            int n, int frames_per_graph, double *d_hist) {
     if (!c) return HPE_E_ARG;
-    if (int erc = mw_check_async(c)) return erc;
-    if (!d_state) return fail(c, HPE_E_ARG, "null device state");
-    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
-    int rc = check_P(c, P);
+    int rc = check_chunked_call(c, P, frames_per_graph);
     if (rc) return rc;
+    if (!d_state) return fail(c, HPE_E_ARG, "null device state");
     if (n < 1 || first_slot < 0 || first_slot + n > (int)c->slots.size())
         return fail(c, HPE_E_ARG, "frames [%d, %d) are not all stored slots", first_slot,
                     first_slot + n);
-    if (frames_per_graph < 0 || frames_per_graph > HPE_SEQ_MAX_CHUNK)
-        return fail(c, HPE_E_ARG, "frames_per_graph %d out of range [0, %d]", frames_per_graph,
-                    HPE_SEQ_MAX_CHUNK);
     for (int f = 0; f < n; ++f)
         if (!c->slots[first_slot + f].valid)
             return fail(c, HPE_E_ARG, "slot %d holds no frame", first_slot + f);
@@ -2050,99 +2092,72 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
     double *hist = d_hist;  // rows advance with the cursor
     for (int f0 = 0; f0 < n; f0 += K) {
         const int k = n - f0 < K ? n - f0 : K, slot0 = first_slot + f0;
-        if (direct_launches(c)) {
-            if ((rc = enqueue_seq_chunk(c, P, refine, d_state, slot0, k, hist))) return rc;
-            continue;
+        GraphKey key = graph_key(P, G, refine, d_state, hist);
+        key.k = k;
+        for (int i = 0; i < k; ++i) {  // keyed by the chunk's shape, not its slots
+            if (c->slots[slot0 + i].n_max <= RF_STAGE_MAX) key.staged |= 1u << i;
+            if (c->slots[slot0 + i].n_max > HPE_NT / 2) key.filt |= 1u << i;
         }
-        unsigned staged = 0, filt = 0;
-        for (int i = 0; i < k; ++i) {
-            if (c->slots[slot0 + i].n_max <= RF_STAGE_MAX) staged |= 1u << i;
-            if (c->slots[slot0 + i].n_max > HPE_NT / 2) filt |= 1u << i;
-        }
-        hipGraphExec_t exec = nullptr;
-        for (auto &sg : c->sgraphs)  // keyed by the chunk's shape, not its slots
-            if (sg.P == P && sg.G == G && sg.refine == refine && sg.k == k &&
-                sg.staged == staged && sg.filt == filt && sg.state == d_state && sg.hist == hist &&
-                sg.seed == c->seed && sg.epoch == c->epoch)
-                exec = sg.exec;
-        if (!exec) {
-            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            ++c->captures;
-            bool direct = false;
-            if ((rc = end_capture(c, enqueue_seq_chunk(c, P, refine, d_state, slot0, k, hist), &exec,
-                                  &direct)))
-                return rc;
-            if (direct) {
-                if ((rc = enqueue_seq_chunk(c, P, refine, d_state, slot0, k, hist))) return rc;
-                continue;
-            }
-            // drop graphs of an older epoch or seed.  Not every epoch bump comes from a
-            // reallocation that drained the device (hpe_set_refine_exact and hpe_set_exchange
-            // only bump it), so one of them may still be in flight: wait for the stream first
-            // (ADVICE r4), only when there is something to drop
-            bool stale = false;
-            for (auto &sg : c->sgraphs) stale |= sg.epoch != c->epoch || sg.seed != c->seed;
-            if (stale) HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (size_t q = 0; q < c->sgraphs.size();) {
-                if (c->sgraphs[q].epoch != c->epoch || c->sgraphs[q].seed != c->seed) {
-                    (void)hipGraphExecDestroy(c->sgraphs[q].exec);
-                    c->sgraphs[q] = c->sgraphs.back();
-                    c->sgraphs.pop_back();
-                } else {
-                    ++q;
-                }
-            }
-            if (c->sgraphs.size() >= 64) {  // many live shapes (states, histories, P, G)
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                for (auto &sg : c->sgraphs) (void)hipGraphExecDestroy(sg.exec);
-                c->sgraphs.clear();
-            }
-            c->sgraphs.push_back({P, G, refine, k, staged, filt, d_state, hist, c->seed, c->epoch, exec});
-        }
-        HIPCHK(c, hipGraphLaunch(exec, c->stream));
+        if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_SEQ], key, [&] {
+                 return enqueue_seq_chunk(c, P, refine, d_state, slot0, k, hist);
+             })))
+            return rc;
     }
     // the last frame's descriptor is the selected one now (handed back by its final kernel)
     c->cur = first_slot + n - 1;
-    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
-    c->seq_done_valid = true;
-    return HPE_OK;
+    return mark_seq_done(c);
 }
 
+// (defined below its first caller: the _b kernels are emitted in the order the host code first
+// names them, and the code object stays byte for byte what it was with k_refine_b first)
+static int launch_pso_lanes(hpe_ctx *c, int P, int B, const DevSwarm &d, double *d_states,
+                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur);
+
 // k frames of B lanes, one after the other on the tracking stream: per frame the launches of
-// enqueue_seq_chunk with a lane dimension -- refine on grid (1, B), init and the generations
-// on (P, B), the final kernel on (1, B) -- each lane on its own descriptor d_bobs[b], cursor
-// d_bcur[2 b] and arena.  filt: bit i = frame i takes the FILT kernels (all lanes agree).
+// enqueue_seq_chunk with a lane dimension -- refine on grid (1, B), then launch_pso_lanes --
+// each lane on its own descriptor d_bobs[b], cursor d_bcur[2 b] and arena.  filt: bit i = frame
+// i takes the FILT kernels (all lanes agree).
 static int enqueue_batch_chunk(hpe_ctx *c, int P, int refine, int B, double *d_states, unsigned filt,
                                int k, double *hist) {
     const DevSwarm d = batch_swarm(c);
+    for (int i = 0; i < k; ++i) {
+        if (refine)  // testmodel.cpp:126; the CU-filling LDS size puts the lanes on B CUs
+            launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
+                   dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)c->d_bobs,
+                   (const DevHand *)c->d_hand, c->d_bevals);
+        if (int rc = launch_pso_lanes(c, P, B, d, d_states, c->d_bobs, (filt >> i) & 1u, hist,
+                                      c->d_obs, c->d_bcur))
+            return rc;
+    }
+    return HPE_OK;
+}
+
+// pso_evolve and cal_cost(bestp) of one frame for B lanes: launch_pso's workgroup form with a
+// lane dimension -- init and the generations on (P, B), the final kernel on (1, B) -- lane b on
+// descriptor obs[b], arena b of d (batch_swarm) and cursor cur[2 b].  filt: the FILT kernels.
+// slots: the descriptor table the final kernel stages lane b's next frame from (null: the raw
+// lanes' preparation does that, and the cursor's slot word counts frames).
+static int launch_pso_lanes(hpe_ctx *c, int P, int B, const DevSwarm &d, double *d_states,
+                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur) {
     const size_t stride = c->sw.stride;
-    const int G = d.G;
     const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
     static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
     const bool r16 = d.K <= 15;
-    const DevObs *obs = c->d_bobs;
     const DevHand *hand = c->d_hand;
-    for (int i = 0; i < k; ++i) {
-        const bool f = (filt >> i) & 1u;
-        if (refine)  // testmodel.cpp:126; the CU-filling LDS size puts the lanes on B CUs
-            launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
-                   dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals);
-        launch(c, HPE_PROF_PSO_INIT, f ? k_pso_init_b<true> : k_pso_init_b<false>, dim3(P, B),
-               dim3(HPE_NT), 0, d, stride, (const double *)d_states, obs, hand);
-        for (int g = 1; g <= G; ++g) {
-            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
-            launch(c, HPE_PROF_PSO_GEN,
-                   f ? (r16 ? k_pso_gen_b<true, true> : k_pso_gen_b<false, true>)
-                     : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
-                   dim3(P, B), dim3(HPE_NT), 0, d, stride, obs, hand, g, W1, C1, C2, kg);
-        }
-        launch(c, HPE_PROF_PSO_FINAL, f ? k_pso_final_b<true> : k_pso_final_b<false>, dim3(1, B),
-               dim3(HPE_NT), 0, d, stride, d_states, c->d_bobs, hand, (DevObs *)nullptr, 1,
-               (unsigned long long *)nullptr, (unsigned long long *)nullptr, hist,
-               (const int *)nullptr, (const DevObs *)c->d_obs, c->d_bcur);
-        HIPCHK(c, hipGetLastError());
+    launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init_b<true> : k_pso_init_b<false>, dim3(P, B),
+           dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)obs, hand);
+    for (int g = 1; g <= d.G; ++g) {
+        const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
+        launch(c, HPE_PROF_PSO_GEN,
+               filt ? (r16 ? k_pso_gen_b<true, true> : k_pso_gen_b<false, true>)
+                    : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
+               dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)obs, hand, g, W1, C1, C2, kg);
     }
+    launch(c, HPE_PROF_PSO_FINAL, filt ? k_pso_final_b<true> : k_pso_final_b<false>, dim3(1, B),
+           dim3(HPE_NT), 0, d, stride, d_states, obs, hand, (DevObs *)nullptr, 1,
+           (unsigned long long *)nullptr, (unsigned long long *)nullptr, hist,
+           (const int *)nullptr, slots, cur);
+    HIPCHK(c, hipGetLastError());
     return HPE_OK;
 }
 
@@ -2161,24 +2176,9 @@ static int ensure_batch_lanes(hpe_ctx *c) {
 int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
                         const int32_t *first_slots, int n, int frames_per_graph, double *d_hist) {
     if (!c) return HPE_E_ARG;
-    if (int erc = mw_check_async(c)) return erc;
-    if (B < 1 || B > HPE_BATCH_MAX)
-        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    int rc = check_chunked_call(c, P, frames_per_graph);
+    if (rc || (rc = check_batch_call(c, P, B))) return rc;
     if (!d_states || !first_slots) return fail(c, HPE_E_ARG, "null device states or first slots");
-    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
-    int rc = check_P(c, P);
-    if (rc) return rc;
-    if (pso_wave_form(c, P))
-        return fail(c, HPE_E_ARG, "num_p %d takes the wave form: a batch needs the workgroup form "
-                    "(num_p < %d)", P, c->wave_form_min_p);
-    if (c->ss.transport())
-        return fail(c, HPE_E_STATE, "a subswarm transport is live: a batch runs without the "
-                    "exchange (hpe_subswarm_fini)");
-    if (c->xch_every > 0)
-        return fail(c, HPE_E_STATE, "the per-generation exchange is on (hpe_set_exchange)");
-    if (frames_per_graph < 0 || frames_per_graph > HPE_SEQ_MAX_CHUNK)
-        return fail(c, HPE_E_ARG, "frames_per_graph %d out of range [0, %d]", frames_per_graph,
-                    HPE_SEQ_MAX_CHUNK);
     if (n < 1) return fail(c, HPE_E_ARG, "n = %d frames", n);
     for (int b = 0; b < B; ++b) {
         const int s0 = first_slots[b];
@@ -2217,57 +2217,17 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
     const int K = frames_per_graph ? frames_per_graph : HPE_SEQ_CHUNK;
     for (int f0 = 0; f0 < n; f0 += K) {
         const int k = n - f0 < K ? n - f0 : K;
-        unsigned filt = 0;
+        GraphKey key = graph_key(P, G, refine, d_states, d_hist);  // the shape, not the slots
+        key.k = k;
+        key.B = B;
         for (int i = 0; i < k; ++i)
-            if (c->slots[first_slots[0] + f0 + i].n_max > HPE_NT / 2) filt |= 1u << i;
-        if (direct_launches(c)) {
-            if ((rc = enqueue_batch_chunk(c, P, refine, B, d_states, filt, k, d_hist))) return rc;
-            continue;
-        }
-        hipGraphExec_t exec = nullptr;
-        for (auto &bg : c->bgraphs)  // keyed by the chunk's shape, not its slots
-            if (bg.P == P && bg.G == G && bg.refine == refine && bg.k == k && bg.filt == filt &&
-                bg.B == B && bg.states == d_states && bg.hist == d_hist && bg.seed == c->seed &&
-                bg.epoch == c->epoch)
-                exec = bg.exec;
-        if (!exec) {
-            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            ++c->captures;
-            bool direct = false;
-            if ((rc = end_capture(c, enqueue_batch_chunk(c, P, refine, B, d_states, filt, k, d_hist),
-                                  &exec, &direct)))
-                return rc;
-            if (direct) {  // end_capture's exchange fallback: a batch never holds the exchange
-                if ((rc = enqueue_batch_chunk(c, P, refine, B, d_states, filt, k, d_hist))) return rc;
-                continue;
-            }
-            // drop graphs of an older epoch or seed (one may still be in flight: wait first),
-            // and all of them at the cap, as hpe_track_sequence_dev does
-            bool stale = false;
-            for (auto &bg : c->bgraphs) stale |= bg.epoch != c->epoch || bg.seed != c->seed;
-            if (stale || c->bgraphs.size() >= 64) HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (size_t q = 0; q < c->bgraphs.size();) {
-                if (stale && (c->bgraphs[q].epoch != c->epoch || c->bgraphs[q].seed != c->seed)) {
-                    (void)hipGraphExecDestroy(c->bgraphs[q].exec);
-                    c->bgraphs[q] = c->bgraphs.back();
-                    c->bgraphs.pop_back();
-                } else {
-                    ++q;
-                }
-            }
-            if (c->bgraphs.size() >= 64) {
-                for (auto &bg : c->bgraphs) (void)hipGraphExecDestroy(bg.exec);
-                c->bgraphs.clear();
-            }
-            c->bgraphs.push_back({P, G, refine, k, filt, B, d_states, d_hist, c->seed, c->epoch, exec});
-        }
-        HIPCHK(c, hipGraphLaunch(exec, c->stream));
+            if (c->slots[first_slots[0] + f0 + i].n_max > HPE_NT / 2) key.filt |= 1u << i;
+        if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_BATCH], key, [&] {
+                 return enqueue_batch_chunk(c, P, refine, B, d_states, key.filt, k, d_hist);
+             })))
+            return rc;
     }
-    // the lanes' slots have this call as their last reader (hpe_prepare_frame waits for it)
-    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
-    c->seq_done_valid = true;
-    return HPE_OK;
+    return mark_seq_done(c);
 }
 
 // Host wait for pipelined frame n (1-based) to have run its final kernel, by polling the
@@ -2317,45 +2277,17 @@ int hpe_track_pipelined(hpe_ctx *c, int P, int refine, double *d_state, const fl
     if ((rc = ensure_match(c, npix))) return rc;
     if ((rc = ensure_swarm(c, P, G))) return rc;
     if ((rc = upload_bounds(c))) return rc;
-    c->pipe_counting = pp.zero_copy;
-    if (direct_launches(c)) {
-        rc = enqueue_pipe_frame(c, P, refine, d_state, next);
+    GraphKey key = graph_key(P, G, refine, d_state);
+    key.staged = pp.fr[cur].n_max <= RF_STAGE_MAX;
+    key.next = next;
+    key.cur = cur;
+    rc = run_graphed(c, c->graphs[hpe_ctx::GC_PIPE], key, [&] {
+        c->pipe_counting = pp.zero_copy;  // the final kernel publishes the frame's number
+        const int erc = enqueue_pipe_frame(c, P, refine, d_state, next);
         c->pipe_counting = false;
-        if (rc) return rc;
-    } else {
-        const int staged = pp.fr[cur].n_max <= RF_STAGE_MAX;
-        hipGraphExec_t exec = nullptr;
-        for (auto &ge : c->pgraphs)
-            if (ge.P == P && ge.G == G && ge.refine == refine && ge.staged == staged &&
-                ge.next == next && ge.cur == cur && ge.state == d_state && ge.seed == c->seed &&
-                ge.epoch == c->epoch)
-                exec = ge.exec;
-        bool direct = false;
-        if (!exec) {
-            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            ++c->captures;
-            rc = enqueue_pipe_frame(c, P, refine, d_state, next);
-            c->pipe_counting = false;
-            if ((rc = end_capture(c, rc, &exec, &direct))) return rc;
-            if (!direct) {
-                if (c->pgraphs.size() >= 16) {  // stale keys (seed / buffers changed)
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    for (auto &ge : c->pgraphs) (void)hipGraphExecDestroy(ge.exec);
-                    c->pgraphs.clear();
-                }
-                c->pgraphs.push_back({P, G, refine, staged, next, cur, d_state, c->seed, c->epoch, exec});
-            }
-        }
-        if (direct) {  // the capture fell back (subswarm exchange): this frame, directly
-            c->pipe_counting = pp.zero_copy;
-            rc = enqueue_pipe_frame(c, P, refine, d_state, next);
-            c->pipe_counting = false;
-            if (rc) return rc;
-        } else {
-            c->pipe_counting = false;
-            HIPCHK(c, hipGraphLaunch(exec, c->stream));
-        }
-    }
+        return erc;
+    });
+    if (rc) return rc;
     ++pp.enq;  // this frame's number; its final kernel publishes it to h_done
     if (next) {
         if (pp.zero_copy) {
@@ -2419,14 +2351,9 @@ int hpe_track_raw_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state,
                                const float *d_raw_mm, int n, int to_cm, int downsample,
                                double focal, int frames_per_graph, double *d_hist) {
     if (!c) return HPE_E_ARG;
-    if (int erc = mw_check_async(c)) return erc;
-    if (!d_state || !d_raw_mm || n < 1 || !(focal > 0)) return fail(c, HPE_E_ARG, "bad arguments");
-    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
-    int rc = check_P(c, P);
+    int rc = check_chunked_call(c, P, frames_per_graph);
     if (rc) return rc;
-    if (frames_per_graph < 0 || frames_per_graph > HPE_SEQ_MAX_CHUNK)
-        return fail(c, HPE_E_ARG, "frames_per_graph %d out of range [0, %d]", frames_per_graph,
-                    HPE_SEQ_MAX_CHUNK);
+    if (!d_state || !d_raw_mm || n < 1 || !(focal > 0)) return fail(c, HPE_E_ARG, "bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
     const int need = downsample ? 250 : (int)npix;
@@ -2464,61 +2391,23 @@ int hpe_track_raw_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state,
     const int staged = pp.fr[0].n_max <= RF_STAGE_MAX;
     for (int f0 = 0; f0 < n; f0 += K) {
         const int k = n - f0 < K ? n - f0 : K, parity = f0 & 1, tail_next = f0 + k < n;
-        if (direct_launches(c)) {
-            if ((rc = enqueue_raw_chunk(c, P, refine, d_state, d_raw_mm, parity, k, tail_next, d_hist)))
-                return rc;
-            continue;
-        }
-        hipGraphExec_t exec = nullptr;
-        for (auto &rg : c->rgraphs)
-            if (rg.P == P && rg.G == G && rg.refine == refine && rg.k == k && rg.parity == parity &&
-                rg.tail_next == tail_next && rg.staged == staged && rg.to_cm == pp.to_cm &&
-                rg.downsample == pp.downsample && rg.focal == focal && rg.raw == d_raw_mm &&
-                rg.state == d_state && rg.hist == d_hist && rg.seed == c->seed &&
-                rg.epoch == c->epoch)
-                exec = rg.exec;
-        if (!exec) {
-            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            ++c->captures;
-            bool direct = false;
-            rc = enqueue_raw_chunk(c, P, refine, d_state, d_raw_mm, parity, k, tail_next, d_hist);
-            if ((rc = end_capture(c, rc, &exec, &direct))) return rc;
-            if (direct) {
-                if ((rc = enqueue_raw_chunk(c, P, refine, d_state, d_raw_mm, parity, k, tail_next, d_hist)))
-                    return rc;
-                continue;
-            }
-            // graphs of an older epoch or seed are dropped, after the stream has drained (an
-            // epoch bump need not have synchronised: see hpe_track_sequence_dev)
-            bool stale = false;
-            for (auto &rg : c->rgraphs) stale |= rg.epoch != c->epoch || rg.seed != c->seed;
-            if (stale) HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (size_t q = 0; q < c->rgraphs.size();) {
-                if (c->rgraphs[q].epoch != c->epoch || c->rgraphs[q].seed != c->seed) {
-                    (void)hipGraphExecDestroy(c->rgraphs[q].exec);
-                    c->rgraphs[q] = c->rgraphs.back();
-                    c->rgraphs.pop_back();
-                } else {
-                    ++q;
-                }
-            }
-            if (c->rgraphs.size() >= 64) {  // many live shapes (inputs, states, histories)
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                for (auto &rg : c->rgraphs) (void)hipGraphExecDestroy(rg.exec);
-                c->rgraphs.clear();
-            }
-            c->rgraphs.push_back({P, G, refine, k, parity, tail_next, staged, pp.to_cm,
-                                  pp.downsample, focal, d_raw_mm, d_state, d_hist, c->seed,
-                                  c->epoch, exec});
-        }
-        HIPCHK(c, hipGraphLaunch(exec, c->stream));
+        GraphKey key = graph_key(P, G, refine, d_state, d_hist);
+        key.k = k;
+        key.parity = parity;
+        key.tail_next = tail_next;
+        key.staged = staged;
+        key.to_cm = pp.to_cm;
+        key.downsample = pp.downsample;
+        key.focal = focal;
+        key.in = d_raw_mm;
+        if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_RAW], key, [&] {
+                 return enqueue_raw_chunk(c, P, refine, d_state, d_raw_mm, parity, k, tail_next, d_hist);
+             })))
+            return rc;
     }
     // the last frame's descriptor is the selected one now (handed back by its final kernel)
     c->cur = -1;
-    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
-    c->seq_done_valid = true;
-    return HPE_OK;
+    return mark_seq_done(c);
 }
 
 int hpe_pipe_readback(hpe_ctx *c, int parity, double *depth_cm, float *dt, double *cloud,
@@ -2617,11 +2506,6 @@ static int enqueue_raw_batch_chunk(hpe_ctx *c, int P, int refine, int B, double 
                                    int parity, int k, bool tail_next, double *hist) {
     hpe_ctx::RawBatch &rb = c->rb;
     const DevSwarm d = batch_swarm(c);
-    const size_t stride = c->sw.stride;
-    const int G = d.G;
-    const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
-    static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
-    const bool r16 = d.K <= 15;
     const DevHand *hand = c->d_hand;
     for (int i = 0; i < k; ++i) {
         const int cur = (parity + i) & 1, nxt = cur ^ 1;
@@ -2637,19 +2521,9 @@ static int enqueue_raw_batch_chunk(hpe_ctx *c, int P, int refine, int B, double 
             launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
                    dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
                    c->d_bevals);
-        launch(c, HPE_PROF_PSO_INIT, k_pso_init_b<false>, dim3(P, B), dim3(HPE_NT), 0, d, stride,
-               (const double *)d_states, (const DevObs *)obs, hand);
-        for (int g = 1; g <= G; ++g) {
-            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
-            launch(c, HPE_PROF_PSO_GEN, r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>,
-                   dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)obs, hand, g, W1, C1, C2, kg);
-        }
         // no slot table: the cursor's slot word counts the lane's frames (the preparation's)
-        launch(c, HPE_PROF_PSO_FINAL, k_pso_final_b<false>, dim3(1, B), dim3(HPE_NT), 0, d, stride,
-               d_states, obs, hand, (DevObs *)nullptr, 1, (unsigned long long *)nullptr,
-               (unsigned long long *)nullptr, hist, (const int *)nullptr, (const DevObs *)nullptr,
-               rb.d_cur);
-        HIPCHK(c, hipGetLastError());
+        if (int rc = launch_pso_lanes(c, P, B, d, d_states, obs, false, hist, nullptr, rb.d_cur))
+            return rc;
     }
     return HPE_OK;
 }
@@ -2658,31 +2532,16 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
                             const float *const *d_raw_mm, int n, int to_cm, int downsample,
                             double focal, int frames_per_graph, double *d_hist) {
     if (!c) return HPE_E_ARG;
-    if (int erc = mw_check_async(c)) return erc;
-    if (B < 1 || B > HPE_BATCH_MAX)
-        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    int rc = check_chunked_call(c, P, frames_per_graph);
+    if (rc || (rc = check_batch_call(c, P, B))) return rc;
     if (!d_states || !d_raw_mm) return fail(c, HPE_E_ARG, "null device states or raw pointers");
     for (int b = 0; b < B; ++b)
         if (!d_raw_mm[b]) return fail(c, HPE_E_ARG, "lane %d: null raw frames", b);
     if (n < 1) return fail(c, HPE_E_ARG, "n = %d frames", n);
     if (!(focal > 0)) return fail(c, HPE_E_ARG, "focal %g is not positive", focal);
-    if (frames_per_graph < 0 || frames_per_graph > HPE_SEQ_MAX_CHUNK)
-        return fail(c, HPE_E_ARG, "frames_per_graph %d out of range [0, %d]", frames_per_graph,
-                    HPE_SEQ_MAX_CHUNK);
-    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
-    int rc = check_P(c, P);
-    if (rc) return rc;
-    if (pso_wave_form(c, P))
-        return fail(c, HPE_E_ARG, "num_p %d takes the wave form: a batch needs the workgroup form "
-                    "(num_p < %d)", P, c->wave_form_min_p);
     if (!downsample)
         return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
                     "the single-workgroup refine (<= %d)", HPE_IMG_H * HPE_IMG_W, RF_STAGE_MAX);
-    if (c->ss.transport())
-        return fail(c, HPE_E_STATE, "a subswarm transport is live: a batch runs without the "
-                    "exchange (hpe_subswarm_fini)");
-    if (c->xch_every > 0)
-        return fail(c, HPE_E_STATE, "the per-generation exchange is on (hpe_set_exchange)");
     HIPCHK(c, hipSetDevice(c->device));
     const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
     to_cm = to_cm ? 1 : 0;
@@ -2702,58 +2561,21 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
     const int K = frames_per_graph ? frames_per_graph : HPE_SEQ_CHUNK;
     for (int f0 = 0; f0 < n; f0 += K) {
         const int k = n - f0 < K ? n - f0 : K, parity = f0 & 1, tail_next = f0 + k < n;
-        if (direct_launches(c)) {
-            if ((rc = enqueue_raw_batch_chunk(c, P, refine, B, d_states, parity, k, tail_next, d_hist)))
-                return rc;
-            continue;
-        }
-        hipGraphExec_t exec = nullptr;
-        for (auto &rg : c->rbgraphs)  // keyed by the chunk's shape, not the raw buffers or n
-            if (rg.P == P && rg.G == G && rg.refine == refine && rg.k == k && rg.parity == parity &&
-                rg.tail_next == tail_next && rg.B == B && rg.to_cm == to_cm &&
-                rg.downsample == 1 && rg.focal == focal && rg.states == d_states &&
-                rg.hist == d_hist && rg.seed == c->seed && rg.epoch == c->epoch)
-                exec = rg.exec;
-        if (!exec) {
-            HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-            ++c->captures;
-            bool direct = false;
-            rc = enqueue_raw_batch_chunk(c, P, refine, B, d_states, parity, k, tail_next, d_hist);
-            if ((rc = end_capture(c, rc, &exec, &direct))) return rc;
-            if (direct) {  // end_capture's exchange fallback: a batch never holds the exchange
-                if ((rc = enqueue_raw_batch_chunk(c, P, refine, B, d_states, parity, k, tail_next,
-                                                  d_hist)))
-                    return rc;
-                continue;
-            }
-            // drop graphs of an older epoch or seed (one may still be in flight: wait first),
-            // and all of them at the cap, as hpe_track_batch_dev does
-            bool stale = false;
-            for (auto &rg : c->rbgraphs) stale |= rg.epoch != c->epoch || rg.seed != c->seed;
-            if (stale || c->rbgraphs.size() >= 64) HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (size_t q = 0; q < c->rbgraphs.size();) {
-                if (stale && (c->rbgraphs[q].epoch != c->epoch || c->rbgraphs[q].seed != c->seed)) {
-                    (void)hipGraphExecDestroy(c->rbgraphs[q].exec);
-                    c->rbgraphs[q] = c->rbgraphs.back();
-                    c->rbgraphs.pop_back();
-                } else {
-                    ++q;
-                }
-            }
-            if (c->rbgraphs.size() >= 64) {
-                for (auto &rg : c->rbgraphs) (void)hipGraphExecDestroy(rg.exec);
-                c->rbgraphs.clear();
-            }
-            c->rbgraphs.push_back({P, G, refine, k, parity, tail_next, B, to_cm, 1, focal, d_states,
-                                   d_hist, c->seed, c->epoch, exec});
-        }
-        HIPCHK(c, hipGraphLaunch(exec, c->stream));
+        GraphKey key = graph_key(P, G, refine, d_states, d_hist);  // not the raw buffers or n
+        key.k = k;
+        key.parity = parity;
+        key.tail_next = tail_next;
+        key.B = B;
+        key.to_cm = to_cm;
+        key.downsample = 1;
+        key.focal = focal;
+        if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_RAW_BATCH], key, [&] {
+                 return enqueue_raw_batch_chunk(c, P, refine, B, d_states, parity, k, tail_next,
+                                                d_hist);
+             })))
+            return rc;
     }
-    // the same "last reader" event the other sequence calls record
-    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
-    c->seq_done_valid = true;
-    return HPE_OK;
+    return mark_seq_done(c);
 }
 
 int hpe_profile_enable(hpe_ctx *c, int on) {
