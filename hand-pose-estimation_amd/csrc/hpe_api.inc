@@ -104,7 +104,7 @@ struct OptState {  // pso_optimise buffers, rebuilt when P / G / seed / cloud bo
 };
 
 // What a captured tracking graph depends on besides the context's seed and epoch: one key for
-// the six tracking calls, a field a call does not use left zero.  A launch decision that is not
+// the tracking calls, a field a call does not use left zero.  A launch decision that is not
 // in the key replays the wrong kernels (a cached chunk of 250-point frames on 400-point ones).
 struct GraphKey {
     int P, G, refine, k;
@@ -183,9 +183,12 @@ struct hpe_ctx {
     // GC_SEQ, GC_RAW: a chunk of resident frames / of resident raw frames, keyed by its shape
     //     (not its slots)
     // GC_BATCH, GC_RAW_BATCH: the same chunks for B lanes
-    enum { GC_FRAME, GC_PIPE, GC_SEQ, GC_RAW, GC_BATCH, GC_RAW_BATCH, GC_N };
+    // GC_LIVE_BATCH: a pipelined frame of B lanes, per buffer parity and whether it prepares
+    //     next frames (GC_PIPE's cap)
+    enum { GC_FRAME, GC_PIPE, GC_SEQ, GC_RAW, GC_BATCH, GC_RAW_BATCH, GC_LIVE_BATCH, GC_N };
     GraphCache graphs[GC_N] = {{{}, 1, false}, {{}, 16, false}, {{}, 64, true},
-                               {{}, 64, true}, {{}, 64, true}, {{}, 64, true}};
+                               {{}, 64, true}, {{}, 64, true}, {{}, 64, true},
+                               {{}, 16, false}};
     // device preprocessing (hpe_prepare_frame): its own stream, one frame in flight at a time
     hipStream_t prep = nullptr;
     float *d_raw = nullptr;
@@ -250,7 +253,28 @@ struct hpe_ctx {
         unsigned *d_ctr = nullptr;    // [HPE_BATCH_MAX][32]
         const float **d_raw = nullptr;  // [HPE_BATCH_MAX]
         int *d_cur = nullptr;         // [HPE_BATCH_MAX][2]
+        std::vector<PrepArgs> tab;    // d_tab's host copy, and how often it was rewritten
+        unsigned tab_gen = 0;
     } rb;
+    // a live batch (hpe_batch_pipeline_begin / hpe_track_batch_pipelined) on the raw batch's
+    // lane arenas and descriptors: per lane two pinned mapped host buffers, a two-deep ring by
+    // frame parity, which the preparation workgroups read in place (zero copy); d_tab is rb.d_tab
+    // with each entry's raw frame naming its pinned buffer (rewritten when rb's is: tab_gen).
+    // The hand-off is the single pipeline's: the final launch bumps d_seq and stores it to the
+    // pinned word h_done, and the host refills the buffers of parity k once h_done >=
+    // used_seq[k], the number of the frame whose refine launch read them.
+    struct LiveBatch {
+        float *h_raw[2][HPE_BATCH_MAX] = {};
+        float *h_raw_dev[2][HPE_BATCH_MAX] = {};
+        int lanes = 0;  // lanes that have their pinned buffers
+        PrepArgs *d_tab = nullptr;  // [2][HPE_BATCH_MAX]
+        unsigned tab_gen = 0;
+        int tab_lanes = 0;
+        unsigned long long *d_seq = nullptr, *h_done = nullptr, *h_done_dev = nullptr;
+        unsigned long long enq = 0, used_seq[2] = {0, 0};
+        int B = 0, cur = -1, to_cm = 1;  // cur: the current frames' parity, -1: no batch
+        double focal = 0;
+    } live;
     hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
     bool pipe_counting = false;  // set while a pipelined frame is enqueued (k_pso_final args)
@@ -1024,6 +1048,12 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->rb.d_ctr);
     dfree(c->rb.d_raw);
     dfree(c->rb.d_cur);
+    for (auto &par : c->live.h_raw)
+        for (float *h : par)
+            if (h) (void)hipHostFree(h);
+    dfree(c->live.d_tab);
+    dfree(c->live.d_seq);
+    if (c->live.h_done) (void)hipHostFree(c->live.h_done);
     dfree(c->d_raw);
     dfree(c->d_tmp);
     dfree(c->d_ctb);
@@ -2110,8 +2140,13 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
 
 // (defined below its first caller: the _b kernels are emitted in the order the host code first
 // names them, and the code object stays byte for byte what it was with k_refine_b first)
+typedef void (*LaneFinalFn)(DevSwarm, size_t, double *, DevObs *, const DevHand *, DevObs *, int,
+                            unsigned long long *, unsigned long long *, double *, const int *,
+                            const DevObs *, int *);
 static int launch_pso_lanes(hpe_ctx *c, int P, int B, const DevSwarm &d, double *d_states,
-                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur);
+                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur,
+                            LaneFinalFn live_final = nullptr, unsigned long long *seq = nullptr,
+                            unsigned long long *done_host = nullptr);
 
 // k frames of B lanes, one after the other on the tracking stream: per frame the launches of
 // enqueue_seq_chunk with a lane dimension -- refine on grid (1, B), then launch_pso_lanes --
@@ -2136,9 +2171,13 @@ static int enqueue_batch_chunk(hpe_ctx *c, int P, int refine, int B, double *d_s
 // lane dimension -- init and the generations on (P, B), the final kernel on (1, B) -- lane b on
 // descriptor obs[b], arena b of d (batch_swarm) and cursor cur[2 b].  filt: the FILT kernels.
 // slots: the descriptor table the final kernel stages lane b's next frame from (null: the raw
-// lanes' preparation does that, and the cursor's slot word counts frames).
+// lanes' preparation does that, and the cursor's slot word counts frames).  live_final (the live
+// batch): that final kernel in k_pso_final_b's place, with the batch's frame counter seq and the
+// host word done_host it publishes to.
 static int launch_pso_lanes(hpe_ctx *c, int P, int B, const DevSwarm &d, double *d_states,
-                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur) {
+                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur,
+                            LaneFinalFn live_final, unsigned long long *seq,
+                            unsigned long long *done_host) {
     const size_t stride = c->sw.stride;
     const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
     static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
@@ -2153,10 +2192,10 @@ static int launch_pso_lanes(hpe_ctx *c, int P, int B, const DevSwarm &d, double 
                     : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
                dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)obs, hand, g, W1, C1, C2, kg);
     }
-    launch(c, HPE_PROF_PSO_FINAL, filt ? k_pso_final_b<true> : k_pso_final_b<false>, dim3(1, B),
-           dim3(HPE_NT), 0, d, stride, d_states, obs, hand, (DevObs *)nullptr, 1,
-           (unsigned long long *)nullptr, (unsigned long long *)nullptr, hist,
-           (const int *)nullptr, slots, cur);
+    const LaneFinalFn final_k =
+        live_final ? live_final : (filt ? k_pso_final_b<true> : k_pso_final_b<false>);
+    launch(c, HPE_PROF_PSO_FINAL, final_k, dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states, obs,
+           hand, (DevObs *)nullptr, 1, seq, done_host, hist, (const int *)nullptr, slots, cur);
     HIPCHK(c, hipGetLastError());
     return HPE_OK;
 }
@@ -2231,9 +2270,9 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
 }
 
 // Host wait for pipelined frame n (1-based) to have run its final kernel, by polling the
-// pinned word the kernel stores with system scope; bounded (~20 s), false on timeout.
-static bool wait_frame_done(hpe_ctx *c, unsigned long long n) {
-    const volatile unsigned long long *p = c->pipe.h_done;
+// pinned word p (the single pipeline's or the live batch's h_done) that the kernel stores with
+// system scope; bounded (~20 s), false on timeout.
+static bool wait_frame_done(const volatile unsigned long long *p, unsigned long long n) {
     if (__atomic_load_n(p, __ATOMIC_ACQUIRE) >= n) return true;
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned it = 0;; ++it) {
@@ -2259,7 +2298,7 @@ int hpe_track_pipelined(hpe_ctx *c, int P, int refine, double *d_state, const fl
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
     if (next) {  // the pinned and device buffers' previous frame (two ago) must be done
         if (pp.zero_copy) {
-            if (pp.used_seq[nxt] && !wait_frame_done(c, pp.used_seq[nxt]))
+            if (pp.used_seq[nxt] && !wait_frame_done(pp.h_done, pp.used_seq[nxt]))
                 return fail(c, HPE_E_HIP, "pipelined frame %llu did not complete",
                             (unsigned long long)pp.used_seq[nxt]);
         } else if (pp.used_valid[nxt]) {
@@ -2469,7 +2508,8 @@ static int ensure_raw_batch(hpe_ctx *c, int B, int to_cm, double focal) {
         HIPCHK(c, dalloc(&rb.arena[rb.lanes], bytes));
         ++rb.lanes;
     }
-    std::vector<PrepArgs> tab(2 * M);
+    std::vector<PrepArgs> &tab = rb.tab;
+    tab.resize(2 * M);
     std::memset((void *)tab.data(), 0, sizeof(PrepArgs) * tab.size());
     for (int p = 0; p < 2; ++p)
         for (int b = 0; b < rb.lanes; ++b) {
@@ -2492,6 +2532,7 @@ static int ensure_raw_batch(hpe_ctx *c, int B, int to_cm, double focal) {
             a.raw_stride = npix;
         }
     HIPCHK(c, hipMemcpy(rb.d_tab, tab.data(), sizeof(PrepArgs) * tab.size(), hipMemcpyHostToDevice));
+    ++rb.tab_gen;
     rb.to_cm = to_cm;
     rb.focal = focal;
     return HPE_OK;
@@ -2549,6 +2590,7 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
     if ((rc = ensure_raw_batch(c, B, to_cm, focal))) return rc;
     if ((rc = ensure_swarm(c, P, G, B))) return rc;
     if ((rc = upload_bounds(c))) return rc;
+    c->live.cur = -1;  // a live batch in progress (the same lane buffers) ends here
     hpe_ctx::RawBatch &rb = c->rb;
     // the lanes' raw bases and cursors, then frame 0 of every lane into buffer parity 0
     BatchRaw first{};
@@ -2576,6 +2618,162 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
             return rc;
     }
     return mark_seq_done(c);
+}
+
+// ---------------------------------------------------------------- live batched lanes
+// The live batch's own buffers for B lanes on the raw batch's (ensure_raw_batch first): the
+// pinned ring of every new lane, the frame counter, and the ring form of the PrepArgs table --
+// rb's entries with raw = the lane's pinned buffer of that parity -- rewritten whenever rb's
+// table was or a lane got its ring (the stream drained first: launches in flight read it).
+static int ensure_live_batch(hpe_ctx *c, int B) {
+    hpe_ctx::LiveBatch &lv = c->live;
+    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W, M = HPE_BATCH_MAX;
+    if (!lv.d_tab) {
+        HIPCHK(c, dalloc(&lv.d_tab, 2 * M));
+        HIPCHK(c, dalloc(&lv.d_seq, 1));
+        HIPCHK(c, hipHostMalloc((void **)&lv.h_done, sizeof(unsigned long long),
+                                hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(c, hipHostGetDevicePointer((void **)&lv.h_done_dev, lv.h_done, 0));
+    }
+    for (; lv.lanes < B; ++lv.lanes)
+        for (int p = 0; p < 2; ++p) {
+            float *&h = lv.h_raw[p][lv.lanes];
+            if (!h)
+                HIPCHK(c, hipHostMalloc((void **)&h, sizeof(float) * npix,
+                                        hipHostMallocMapped | hipHostMallocCoherent));
+            HIPCHK(c, hipHostGetDevicePointer((void **)&lv.h_raw_dev[p][lv.lanes], h, 0));
+        }
+    if (lv.tab_gen == c->rb.tab_gen && lv.tab_lanes == lv.lanes) return HPE_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<PrepArgs> tab = c->rb.tab;
+    for (int p = 0; p < 2; ++p)
+        for (int b = 0; b < lv.lanes; ++b) tab[p * M + b].raw = lv.h_raw_dev[p][b];
+    HIPCHK(c, hipMemcpy(lv.d_tab, tab.data(), sizeof(PrepArgs) * tab.size(), hipMemcpyHostToDevice));
+    lv.tab_gen = c->rb.tab_gen;
+    lv.tab_lanes = lv.lanes;
+    return HPE_OK;
+}
+
+// Every entry of a lane frame array non-null: 1; every entry null: 0; mixed: -1.
+static int lane_frames(const float *const *frames, int B) {
+    int set = 0;
+    for (int b = 0; b < B; ++b) set += frames[b] != nullptr;
+    return set == B ? 1 : set == 0 ? 0 : -1;
+}
+
+int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, int to_cm,
+                             int downsample, double focal) {
+    if (!c) return HPE_E_ARG;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!depth_mm || lane_frames(depth_mm, B) != 1)
+        return fail(c, HPE_E_ARG, "null frame array or lane frame");
+    if (!(focal > 0)) return fail(c, HPE_E_ARG, "focal %g is not positive", focal);
+    if (!downsample)
+        return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
+                    "the single-workgroup refine (<= %d)", HPE_IMG_H * HPE_IMG_W, RF_STAGE_MAX);
+    if (c->ss.transport())
+        return fail(c, HPE_E_STATE, "a subswarm transport is live: a batch runs without the "
+                    "exchange (hpe_subswarm_fini)");
+    if (c->xch_every > 0)
+        return fail(c, HPE_E_STATE, "the per-generation exchange is on (hpe_set_exchange)");
+    if (const char *u = std::getenv("HPE_PIPE_UPLOAD"))
+        if (u[0] == '1')
+            return fail(c, HPE_E_STATE, "HPE_PIPE_UPLOAD=1: the upload form is not built for lanes "
+                        "(a live batch reads its pinned buffers in place)");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the frames of a batch in progress are done with: its pinned buffers are free to refill
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hpe_ctx::LiveBatch &lv = c->live;
+    lv.cur = -1;
+    to_cm = to_cm ? 1 : 0;
+    int rc = ensure_batch_lanes(c);
+    if (rc || (rc = ensure_raw_batch(c, B, to_cm, focal)) || (rc = ensure_live_batch(c, B))) return rc;
+    HIPCHK(c, hipMemsetAsync(lv.d_seq, 0, sizeof(unsigned long long), c->stream));
+    __atomic_store_n(lv.h_done, 0ull, __ATOMIC_RELEASE);
+    lv.enq = 0;
+    lv.used_seq[0] = lv.used_seq[1] = 0;
+    // frame 0 of every lane: into its pinned buffer of parity 0, prepared from there
+    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
+    for (int b = 0; b < B; ++b) std::memcpy(lv.h_raw[0][b], depth_mm[b], sizeof(float) * npix);
+    hipLaunchKernelGGL(k_prepare_ring_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                       (const PrepArgs *)lv.d_tab);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    lv.B = B;
+    lv.to_cm = to_cm;
+    lv.focal = focal;
+    lv.cur = 0;
+    return HPE_OK;
+}
+
+// One tracked frame of the live batch, the current frames in the lanes' buffers `cur`: a frame of
+// enqueue_raw_batch_chunk with the ring's preparation (the next frames read from the pinned
+// buffers of parity cur ^ 1) and the final launch that publishes the batch's frame number.
+static int enqueue_live_batch_frame(hpe_ctx *c, int P, int refine, int B, double *d_states, int cur,
+                                    int next) {
+    hpe_ctx::LiveBatch &lv = c->live;
+    const DevSwarm d = batch_swarm(c);
+    const DevHand *hand = c->d_hand;
+    DevObs *obs = c->rb.d_obs + cur * HPE_BATCH_MAX;
+    if (next)  // testmodel.cpp:126 + next_frame of the following iteration
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_ring_b<false> : k_refine_ring_b<true>,
+               dim3(1 + PREP_WG, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
+               c->d_bevals, refine ? 1 : 0, (const PrepArgs *)(lv.d_tab + (cur ^ 1) * HPE_BATCH_MAX));
+    else if (refine)
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
+               dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
+               c->d_bevals);
+    return launch_pso_lanes(c, P, B, d, d_states, obs, false, nullptr, nullptr, nullptr,
+                            k_pso_final_live_b<false>, lv.d_seq, lv.h_done_dev);
+}
+
+int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                              const float *const *next_depth_mm) {
+    if (!c) return HPE_E_ARG;
+    if (int erc = mw_check_async(c)) return erc;
+    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
+    int rc = check_P(c, P);
+    if (rc || (rc = check_batch_call(c, P, B))) return rc;
+    if (!d_states) return fail(c, HPE_E_ARG, "null device states");
+    const int next = next_depth_mm ? lane_frames(next_depth_mm, B) : 0;
+    if (next < 0)
+        return fail(c, HPE_E_ARG, "next frames for some lanes only: lanes advance in lockstep");
+    hpe_ctx::LiveBatch &lv = c->live;
+    if (lv.cur < 0)
+        return fail(c, HPE_E_STATE, "no live batch: hpe_batch_pipeline_begin not called, or the "
+                    "batch ended");
+    if (B != lv.B)
+        return fail(c, HPE_E_STATE, "%d lanes, the batch began with %d (end it and begin another)",
+                    B, lv.B);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int cur = lv.cur, nxt = cur ^ 1;
+    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
+    if (next) {  // the pinned buffers' previous frames (two ago) must have been read
+        if (lv.used_seq[nxt] && !wait_frame_done(lv.h_done, lv.used_seq[nxt]))
+            return fail(c, HPE_E_HIP, "live batch frame %llu did not complete",
+                        (unsigned long long)lv.used_seq[nxt]);
+        for (int b = 0; b < B; ++b)
+            std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], sizeof(float) * npix);
+    }
+    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
+    if ((rc = ensure_swarm(c, P, G, B))) return rc;
+    if ((rc = upload_bounds(c))) return rc;
+    GraphKey key = graph_key(P, G, refine, d_states);  // the shape: never a host pointer
+    key.B = B;
+    key.cur = cur;
+    key.next = next;
+    key.to_cm = lv.to_cm;
+    key.downsample = 1;
+    key.focal = lv.focal;
+    if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_LIVE_BATCH], key, [&] {
+             return enqueue_live_batch_frame(c, P, refine, B, d_states, cur, next);
+         })))
+        return rc;
+    ++lv.enq;  // this frame's number; lane 0's final workgroup publishes it to h_done
+    if (next) lv.used_seq[nxt] = lv.enq;  // its refine launch reads h_raw[nxt]
+    lv.cur = next ? nxt : -1;
+    return HPE_OK;
 }
 
 int hpe_profile_enable(hpe_ctx *c, int on) {

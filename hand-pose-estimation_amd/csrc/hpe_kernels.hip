@@ -1551,6 +1551,66 @@ __global__ __launch_bounds__(RF_NT) void k_refine_prep_b(double *__restrict__ st
 }
 static_assert(PREP_NT == RF_NT, "the preparation workgroups ride in the refine launch");
 
+// ------------------------------------------------------------------ live batched lanes
+// hpe_track_batch_pipelined: the raw lanes above, fed a frame per call from host memory.  The
+// lane's raw frame is not raw_base + cursor frames but a two-deep ring: its pinned (mapped,
+// coherent) host buffer of the parity being prepared, which the table entry names itself --
+// tab[parity][b].raw, written once with the buffers, raw_row null.  So the preparation of lane
+// blockIdx.y is its table entry and nothing else; the preparation workgroups read the frame
+// over PCIe inside the launch they ride in, as k_refine's do for hpe_track_pipelined.
+
+// k_prepare for frame 0 of every lane (hpe_batch_pipeline_begin), grid (PREP_WG, B)
+__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_b(const PrepArgs *__restrict__ tab) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    prep_workgroup(tab[blockIdx.y], blockIdx.x, lds);
+}
+
+// k_refine_prep_b on the ring, grid (1 + PREP_WG, B): workgroup (0, b) is k_refine_b's, the
+// others prepare the lane's next frame from tab[b].raw.  do_refine = 0: the preparation only.
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_ring_b(double *__restrict__ states,
+                                                         const DevObs *__restrict__ obs,
+                                                         const DevHand *__restrict__ Hg,
+                                                         int *__restrict__ evals_b, int do_refine,
+                                                         const PrepArgs *__restrict__ tab) {
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    PrepArgs pa{};
+    if (blockIdx.x >= 1) pa = tab[blockIdx.y];
+    const DevMw mw{};
+    const DevPick pk{};
+    const PrepSplit ps{};
+#include "hpe_refine_body.inc"
+}
+
+// k_pso_final_b for the live batch, its arguments k_pso_final_b's: no cursor, history or slot
+// table, and the batch's frame counter (seq_b, published to done_host for the host's wait before
+// it refills a pinned buffer) bumped by lane 0's workgroup alone -- once per frame, not B times
+// on one word.  One counter serves the batch: the refine launch of every lane, which read the
+// pinned buffers, has retired before any workgroup of this launch starts.  blockIdx.y is
+// uniform, and the body's counter branch reaches no barrier.
+template <bool FILT, bool TAIL = true>
+__global__ __launch_bounds__(HPE_NT) void k_pso_final_live_b(DevSwarm sw, size_t stride,
+                                                             double *__restrict__ states, DevObs *obs,
+                                                             const DevHand *__restrict__ Hg,
+                                                             DevObs *__restrict__ obs_out, int same_eval,
+                                                             unsigned long long *__restrict__ seq_b,
+                                                             unsigned long long *done_host,
+                                                             double *__restrict__ hist,
+                                                             const int *__restrict__ fail,
+                                                             const DevObs *__restrict__ seq_table,
+                                                             int *__restrict__ cur) {
+    sw = lane_swarm(sw, stride);
+    double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
+    DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
+    const DevObs *const og = seq_obs;
+    int *__restrict__ const seq_cur = cur ? cur + 2 * blockIdx.y : nullptr;
+    unsigned long long *__restrict__ const seq_dev = blockIdx.y == 0 ? seq_b : nullptr;
+#include "hpe_final_body.inc"
+}
+
 #include "hpe_optimise.hpp"
 
 // ------------------------------------------------------------------ synthetic frames

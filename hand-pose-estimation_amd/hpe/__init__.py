@@ -182,6 +182,44 @@ class Context:
             int(to_cm), int(downsample), float(focal), int(frames_per_graph),
             C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
 
+    @staticmethod
+    def _host_frames(what, depths):
+        """The lanes' host frames as float32 240x320 arrays and the array of their addresses
+        (the arrays must outlive the call that takes the addresses)."""
+        ds = list(depths)
+        if not 1 <= len(ds) <= _lib.BATCH_MAX:
+            raise ValueError(f"{what} takes 1..{_lib.BATCH_MAX} lanes, got {len(ds)}")
+        if any(d is None for d in ds):
+            raise ValueError(f"{what}: a frame for every lane or for none (lanes advance in "
+                             "lockstep)")
+        fr = [np.ascontiguousarray(d, dtype=np.float32).reshape(IMG_H, IMG_W) for d in ds]
+        return fr, (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
+
+    def batch_pipeline_begin(self, depths, to_cm=True, downsample=True, focal=241.42):
+        """Begin a live batch of B = len(depths) lanes: lane b's first raw frame (host, float
+        mm 240x320) is copied and prepared.  Ends a live batch in progress."""
+        fr, arr = self._host_frames("batch_pipeline_begin", depths)
+        self.check(self.lib.hpe_batch_pipeline_begin(self._h, len(fr), arr, int(to_cm),
+                                                     int(downsample), float(focal)))
+        self._live_lanes = len(fr)
+
+    def track_batch_pipelined(self, num_p, refine, d_states_ptr, next_depths=None):
+        """Track the current frame of every lane of the live batch in the same launches -- lane b
+        is track_pipelined(num_p, refine, d_states_ptr + 27*8 b, next_depths[b]) bit for bit --
+        and prepare next_depths (one host frame per lane, copied before return) as the following
+        frames; None ends the batch.  d_states_ptr: B x 27 device doubles.  Asynchronous on the
+        context stream."""
+        if not d_states_ptr:
+            raise ValueError("track_batch_pipelined needs the device states")
+        if next_depths is None:
+            # the lane count of the begin (1 without one: the library then reports the state)
+            B, arr = getattr(self, "_live_lanes", 0) or 1, None
+        else:
+            fr, arr = self._host_frames("track_batch_pipelined", next_depths)
+            B = len(fr)
+        self.check(self.lib.hpe_track_batch_pipelined(self._h, int(num_p), int(refine), B,
+                                                      C.c_void_p(d_states_ptr), arr))
+
     # ---- multi-GPU subswarms: the library's own per-frame exchange (hpe_subswarm_init)
     def subswarm_init(self, uid: bytes, nranks: int, rank: int):
         """Join the RCCL communicator named by uid (hpe.subswarm_unique_id() on rank 0, shared

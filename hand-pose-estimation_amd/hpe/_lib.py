@@ -61,6 +61,10 @@ SIGNATURES = {
     "hpe_track_raw_batch_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
                                           C.c_double, C.c_int, C.c_void_p]),
+    "hpe_batch_pipeline_begin": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int,
+                                           C.c_int, C.c_double]),
+    "hpe_track_batch_pipelined": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.POINTER(C.c_void_p)]),
     "hpe_build_spheres": (C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),

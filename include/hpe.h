@@ -352,6 +352,38 @@ int hpe_track_raw_batch_dev(hpe_ctx *ctx, int num_p, int refine, int B, double *
                             const float *const *d_raw_mm, int n, int to_cm, int downsample,
                             double focal, int frames_per_graph, double *d_hist);
 
+/* A live batch: B raw depth streams whose frames arrive one at a time in host memory (a
+ * multi-camera rig), one frame of every lane tracked per call in hpe_track_raw_batch_dev's
+ * launches.  Lane b computes, bit for bit, what
+ *   hpe_pipeline_begin(ctx, depth_mm[b], to_cm, downsample, focal), then per frame
+ *   hpe_track_pipelined(ctx, num_p, refine, d_states + 27 b, next_depth_mm[b])
+ * computes on the same context (its seed, PSO parameters and refine form): one refine launch of
+ * grid (1 + 9, B) whose preparation workgroups read lane b's next frame straight from that
+ * lane's pinned host buffer, the batch's generation launches and one final launch -- one
+ * replayed graph per frame, keyed by its shape (num_p, generations, refine, B, d_states, buffer
+ * parity, whether a next frame is prepared, to_cm, focal), never by host pointers.
+ * depth_mm, next_depth_mm: host arrays of B host pointers, each one 240x320 float mm frame,
+ * copied into the library's pinned buffers before the call returns (the caller may overwrite
+ * its frames at once).  next_depth_mm == NULL (or every entry NULL) tracks the current frames
+ * and ends the batch; some but not all entries NULL is HPE_E_ARG: lanes advance in lockstep.
+ * To change the lane set, end the batch and begin another; the caller owns d_states (device,
+ * B x 27 {x0 -> bestp, cost}, read and overwritten every call), so poses carry over.
+ * Asynchronous on hpe_stream(ctx).  Before a pinned buffer is refilled the host waits (bounded,
+ * HPE_E_HIP on a timeout) for the frame number the final launch publishes to host memory.
+ * The batch shares hpe_track_raw_batch_dev's lane buffers: that call ends a live batch in
+ * progress.  A single pipelined sequence in progress and the other calls' cached graphs stay
+ * valid, the selected frame stays as it was, hpe_pso_trace is not updated, and
+ * hpe_refine_eval_count counts every lane's evaluations.
+ * Refused, never run another way: B outside 1..HPE_BATCH_MAX, a null array, lane pointer or
+ * d_states, focal <= 0, downsample == 0, num_p in the wave form -- HPE_E_ARG; a live subswarm
+ * transport or hpe_set_exchange, HPE_PIPE_UPLOAD=1 in the environment at begin (the upload form
+ * is not built for lanes), hpe_track_batch_pipelined without a begin, after the batch ended or
+ * with a B other than the begin's -- HPE_E_STATE. */
+int hpe_batch_pipeline_begin(hpe_ctx *ctx, int B, const float *const *depth_mm,
+                             int to_cm, int downsample, double focal);
+int hpe_track_batch_pipelined(hpe_ctx *ctx, int num_p, int refine, int B, double *d_states,
+                              const float *const *next_depth_mm);
+
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through
  * hipExtLaunchKernel with a start/stop event pair (dispatch-packet timestamps: the

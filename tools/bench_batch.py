@@ -8,9 +8,12 @@ equals the same lane tracked alone by track_sequence, bit for bit; then prints o
 per lane count with the aggregate tracked frames/s and the time of one batched frame.
 --raw: the same lane counts and workload over raw float mm frames resident in HBM
 (hpe_track_raw_batch_dev: every lane's next frame is prepared inside the lanes' refine launch);
-the check is then against track_raw_sequence alone.  --profile adds the mean device time of the
+the check is then against track_raw_sequence alone.  --live: the same lanes and workload fed a
+frame per lane and call from host memory (hpe_batch_pipeline_begin / hpe_track_batch_pipelined:
+one graph per frame, the next frames read from pinned host buffers inside the refine launch);
+the check is then against the single pipelined loop (track_pipelined) alone.  --profile adds the mean device time of the
 refine, init, generation and final kernels of one more pass (HPE_PROF_*, direct launches).
-Usage (GPU box): python tools/bench_batch.py [--raw] [--profile] [--lanes 1,2,4,8,16]
+Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--profile] [--lanes 1,2,4,8,16]
                                              [--frames 48] [--reps 3]
 """
 import argparse
@@ -90,6 +93,43 @@ def check_raw_against_alone(ctx, torch, x0, raws, n=6):
             raise AssertionError(f"lane {b} of the raw batch differs from the lane tracked alone")
 
 
+def make_host_lanes(ctx, B, n):
+    """Lane b's n frames rendered into host memory (float mm 240 x 320 each)."""
+    from hpe import synth
+    return [[np.ascontiguousarray(ctx.render_depth(th), dtype=np.float32)
+             for th in synth.trajectory(n, b, revert=0.02)] for b in range(B)]
+
+
+def run_live(ctx, st, host, n):
+    """n frames of every lane of host through the live batch, a frame per lane and call."""
+    ctx.batch_pipeline_begin([fr[0] for fr in host])
+    for f in range(n):
+        ctx.track_batch_pipelined(P, 1, st.data_ptr(),
+                                  [fr[f + 1] for fr in host] if f + 1 < n else None)
+
+
+def check_live_against_alone(ctx, torch, x0, host, n=6):
+    B = len(host)
+    st = start_states(torch, x0, B)
+    hist = []
+    ctx.batch_pipeline_begin([fr[0] for fr in host])
+    for f in range(n):
+        ctx.track_batch_pipelined(P, 1, st.data_ptr(),
+                                  [fr[f + 1] for fr in host] if f + 1 < n else None)
+        ctx.check(ctx.lib.hpe_sync(ctx.h))
+        hist.append(st.cpu().numpy().copy())
+    s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
+    for b in range(B):
+        s1.copy_(start_states(torch, x0, 1)[0])
+        ctx.pipeline_begin(host[b][0])
+        for f in range(n):
+            ctx.track_pipelined(P, 1, s1.data_ptr(), host[b][f + 1] if f + 1 < n else None)
+            ctx.check(ctx.lib.hpe_sync(ctx.h))
+            if not np.array_equal(s1.cpu().numpy(), hist[f][b]):
+                raise AssertionError(f"lane {b}, frame {f} of the live batch differs from the "
+                                     "lane tracked alone")
+
+
 def kernel_means_us(ctx, run):
     """Mean device microseconds per launch of the profiled kernels over one pass of run()."""
     from hpe import _lib
@@ -113,8 +153,11 @@ def main():
     ap.add_argument("--frames", type=int, default=48)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--raw", action="store_true")
+    ap.add_argument("--live", action="store_true")
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
+    if a.raw and a.live:
+        ap.error("--raw and --live are two modes")
     import torch
     torch.cuda.is_available()
     import hpe
@@ -126,7 +169,10 @@ def main():
     pso = hpe.PSO()
     pso.set_pso_params(ub, lb, sd, 0.7298, 1.49618, 1.49618, G + 1, 1e-8, 1e-8)
     pso._push(ctx)
-    if a.raw:
+    if a.live:
+        host = make_host_lanes(ctx, max(counts), n)
+        check_live_against_alone(ctx, torch, hpe.X0, host[:min(3, max(counts))])
+    elif a.raw:
         raws = make_raw_lanes(ctx, torch, max(counts), n)
         check_raw_against_alone(ctx, torch, hpe.X0, raws[:min(3, max(counts))])
     else:
@@ -138,7 +184,9 @@ def main():
             ptrs = [r.data_ptr() for r in raws[:B]]
 
         def run():
-            if a.raw:
+            if a.live:
+                run_live(ctx, st, host[:B], n)
+            elif a.raw:
                 ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG)
             else:
                 ctx.track_batch(P, 1, st.data_ptr(), slots, n, FPG)
@@ -157,9 +205,14 @@ def main():
         line = {"lanes": B, "frames_per_lane": n, "reps": a.reps,
                 "aggregate_tracked_fps": B * n / el,
                 "ms_per_batched_frame": el / n * 1e3,
-                "workload": "256 p x 30 gen, refine on, N = 250, resident "
-                            + ("raw frames prepared in the refine launch" if a.raw else "prepared frames")
-                            + ", 8 frames per graph, one context, seeds 0..B-1"}
+                "workload": "256 p x 30 gen, refine on, N = 250, "
+                            + ("host frames, one per lane and call, read from pinned buffers in "
+                               "the refine launch, one graph per frame" if a.live else
+                               "resident " + ("raw frames prepared in the refine launch" if a.raw
+                                              else "prepared frames") + ", 8 frames per graph")
+                            + ", one context, seeds 0..B-1"}
+        if a.live:
+            line["mode"] = "live"
         if a.profile:
             st.copy_(x0)
             torch.cuda.synchronize()
