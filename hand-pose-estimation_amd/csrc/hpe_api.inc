@@ -149,6 +149,44 @@ struct GraphCache {
     bool drop_stale;
 };
 
+// Everything the launches of one tracked frame of a single sequence depend on besides the swarm
+// (launch_pso, refine_launch, subswarm_exchange): built by the tracking call for each frame it
+// enqueues, so an enqueue function leaves nothing to set back, however often it runs.
+struct FrameIo {
+    const DevObs *obs;  // the descriptor the kernels read
+    int n_max;          // a bound on its n (no readback of a device-prepared frame): it picks the
+                        // kernel forms -- the staged refine, the FILT kernels
+    double *state;      // 27 doubles: x0 in, {bestp, cost} out
+    double *hist = nullptr;       // the frame's {bestp, cost} also stored there (sequences)
+    DevObs *hand_back = nullptr;  // the final kernel copies *obs there (d_obs_active), or null
+    // the sequence cursor: the final kernel stages the next frame's descriptor from slots into
+    // seq_obs and advances cur {slot, history row}; a raw sequence has the row cursor alone
+    const DevObs *slots = nullptr;
+    DevObs *seq_obs = nullptr;
+    int *cur = nullptr;
+    // a pipelined frame: the final kernel bumps *seq and publishes it to the host word
+    unsigned long long *seq = nullptr, *done_host = nullptr;
+    // the exchange's pick is left to the next frame's refine launch (it follows in the chunk)
+    bool defer_pick = false;
+};
+
+// The same for one frame of B lanes (track_lane_frame): lane b on descriptor obs[b] and cursor
+// cur[2 b].
+struct LaneFrameIo {
+    DevObs *obs;           // the lanes' descriptors (of this buffer parity)
+    bool filt;             // the FILT kernels (all lanes agree)
+    double *hist;          // the history rows, or null
+    const DevObs *slots;   // the table the final kernel stages lane b's next frame from; null:
+                           // the preparation does that, and the cursor's slot word counts frames
+    int *cur;              // the lanes' cursors, or null (the live batch keeps none)
+    // the other parity's preparation table: the refine launch prepares every lane's next frame
+    // (null: no next frame), from the lanes' raw bases read through cur (null: the pinned ring)
+    const PrepArgs *prep = nullptr;
+    const float *const *raw = nullptr;
+    // the live batch: its final kernel bumps *seq and publishes it to the host word
+    unsigned long long *seq = nullptr, *done_host = nullptr;
+};
+
 }  // namespace
 
 struct hpe_ctx {
@@ -172,11 +210,8 @@ struct hpe_ctx {
     // offline sequences: the descriptor the chunk graphs read and the cursor {slot, row}
     DevObs *d_seq_obs = nullptr;
     int *d_seq_cur = nullptr;
-    bool seq_mode = false;  // while enqueuing a sequence chunk (k_pso_final's cursor args)
-    bool raw_seq_mode = false;  // ... a resident raw sequence chunk (the row cursor alone)
-    // the descriptor the kernels read: d_obs_active, or during a pipelined frame the
-    // current frame buffer's own descriptor (one captured graph per buffer parity)
-    DevObs *obs_dev = nullptr;
+    // (no mode of the context says which descriptor, cursor or counter a tracked frame's launches
+    // use: the tracking call hands them over in a FrameIo, for B lanes a LaneFrameIo, per frame)
     // the captured graphs, a cache per tracking call:
     // GC_FRAME: one tracked frame (refine + pso_evolve + cal_cost), replayed per frame
     // GC_PIPE: a pipelined frame, per buffer parity and whether it prepares a next frame
@@ -277,7 +312,6 @@ struct hpe_ctx {
     } live;
     hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
-    bool pipe_counting = false;  // set while a pipelined frame is enqueued (k_pso_final args)
     unsigned epoch = 1;  // bumped whenever a buffer a captured graph uses is reallocated
     int pso_form = 0;    // 0 auto, 1 workgroup per particle, 2 wave per particle
     static constexpr int wave_form_min_p = 1024;
@@ -320,10 +354,6 @@ struct hpe_ctx {
         int nranks = 0, rank = 0;
         bool on = false;
         double *d_gath = nullptr;  // [nranks][27]: row `rank` is this rank's frame result
-        // inside a sequence chunk: this frame's pick is left to the next frame's refine
-        // launch (defer, set by the chunk loops), which takes `pick` (pending)
-        bool defer = false, pending = false;
-        DevPick pick{};
         // the exchange inside captured graphs (1), or direct launches while it is on (0): set
         // by hpe_subswarm_enable(ctx, 2), or when a capture holding the collective fails
         bool graphs = true;
@@ -665,6 +695,33 @@ static int upload_bounds(hpe_ctx *c) {
     return HPE_OK;
 }
 
+// The lanes' descriptors, cursors and refine evaluation counters (every batch call counts in
+// d_bevals).
+static int ensure_batch_lanes(hpe_ctx *c) {
+    if (!c->d_bobs) {
+        HIPCHK(c, dalloc(&c->d_bobs, HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&c->d_bcur, 2 * HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&c->d_bevals, HPE_BATCH_MAX * HPE_EVALS_N));
+        HIPCHK(c, hipMemset(c->d_bevals, 0, sizeof(int) * HPE_BATCH_MAX * HPE_EVALS_N));
+    }
+    return HPE_OK;
+}
+
+static int generations(const hpe_ctx *c) {  // PSO.cpp:778 runs maxiter-1 times
+    return c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
+}
+
+// What every tracking call allocates before any capture, for swarms of P particles and `lanes`
+// lanes (0: a single sequence): the refine's match buffer or the lanes' tables, the swarm, the
+// bounds.  Returns G >= 0, or the error code (< 0).
+static int ensure_tracking(hpe_ctx *c, int P, int lanes) {
+    const int G = generations(c);
+    int rc = lanes ? ensure_batch_lanes(c) : ensure_match(c, (size_t)HPE_IMG_H * HPE_IMG_W);
+    if (!rc) rc = ensure_swarm(c, P, G, lanes);
+    if (!rc) rc = upload_bounds(c);
+    return rc ? rc : G;
+}
+
 // The per-generation exchange (hpe_set_exchange) after generation g of G: this swarm's
 // best into the caller's buffer, then the caller's collective on the context stream.
 static int exchange_after(hpe_ctx *c, const DevSwarm &d, int g, int G) {
@@ -681,8 +738,9 @@ static int exchange_after(hpe_ctx *c, const DevSwarm &d, int g, int G) {
 // row `rank` of the gather buffer (subswarm_out); the all-gather is in place (no local copy:
 // at one rank RCCL has nothing to move), then d_state <- the best row (k_pick_best; ties to
 // the lowest rank), on the context stream.  In a sequence, the frame's history row (row
-// *cur - 1) gets the picked state too.  ss.defer (a refine launch follows in the same chunk):
-// the pick rides in that launch instead (DevPick), one launch fewer per frame.  While
+// io.cur[1] - 1) gets the picked state too.  io.defer_pick (a refine launch follows in the same
+// chunk): the pick is handed to the caller instead (*pick) and rides in that launch, one launch
+// fewer per frame; the chunk loop carries it from this frame to the next as a local.  While
 // profiling, an event pair brackets the exchange (HPE_PROF_EXCHANGE).
 // With the scripted transport a one-wave kernel stands where the all-gather does: it copies
 // the peers' rows of the script frame the device exchange counter names (k_script_rows).
@@ -690,8 +748,9 @@ static bool subswarm_active(const hpe_ctx *c) { return c->ss.transport() && c->s
 static double *subswarm_out(hpe_ctx *c, double *d_state) {
     return subswarm_active(c) ? c->ss.d_gath + (size_t)c->ss.rank * (HPE_DOF + 1) : d_state;
 }
-static int subswarm_exchange(hpe_ctx *c, double *d_state, double *hist, const int *cur) {
+static int subswarm_exchange(hpe_ctx *c, const FrameIo &io, DevPick *pick) {
     if (!subswarm_active(c)) return HPE_OK;
+    const int *cur = io.cur ? io.cur + 1 : nullptr;  // the history row cursor
     hpe_ctx::Pool &pl = c->pools[HPE_PROF_EXCHANGE];
     const bool timed = c->prof && pl.used + 2 <= pl.ev.size();
     if (timed) HIPCHK(c, hipEventRecord(pl.ev[pl.used], c->stream));
@@ -708,12 +767,11 @@ static int subswarm_exchange(hpe_ctx *c, double *d_state, double *hist, const in
                            c->ss.rank, c->ss.d_script_k, c->ss.d_gath);
         HIPCHK(c, hipGetLastError());
     }
-    if (c->ss.defer) {
-        c->ss.pick = DevPick{c->ss.d_gath, hist, cur, c->ss.nranks};
-        c->ss.pending = true;
+    if (io.defer_pick) {
+        *pick = DevPick{c->ss.d_gath, io.hist, cur, c->ss.nranks};
     } else {
         hipLaunchKernelGGL(k_pick_best, dim3(1), dim3(64), 0, c->stream, (const double *)c->ss.d_gath,
-                           c->ss.nranks, d_state, hist, cur);
+                           c->ss.nranks, io.state, io.hist, cur);
         HIPCHK(c, hipGetLastError());
     }
     if (timed) {
@@ -749,7 +807,6 @@ static int end_capture(hpe_ctx *c, int rc, hipGraphExec_t *exec, bool *direct) {
         std::fprintf(stderr, "hpe: %s\n", c->ss.note);
         (void)hipGetLastError();
         c->ss.graphs = false;
-        c->ss.pending = false;
         *exec = nullptr;
         *direct = true;
         return HPE_OK;
@@ -803,19 +860,18 @@ static int run_graphed(hpe_ctx *c, GraphCache &gc, const GraphKey &key, Enq enqu
 }
 
 // pso_evolve on the device: x0 and the result live in d_state (27 doubles).
-// tail: fuse cal_cost(bestp) (and the descriptor hand-back) into the final kernel.
-// hist (tail only): the frame's {bestp, cost} also stored there (offline sequences).
-static int launch_pso(hpe_ctx *c, int P, double *d_state, const DevObs &o, bool tail = false,
-                      double *hist = nullptr) {
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;  // PSO.cpp:778 runs maxiter-1 times
-    int rc = ensure_swarm(c, P, G);
-    if (rc) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+// The swarm of P particles is the caller's to have built (ensure_swarm, upload_bounds).
+// tail: fuse cal_cost(bestp) and the rest of io (the hand-back, the cursor, the frame counter,
+// the history row) into the final kernel, then the subswarm exchange (*pick: see there).
+static int launch_pso(hpe_ctx *c, int P, const FrameIo &io, bool tail, DevPick *pick = nullptr) {
+    int rc;
+    double *d_state = io.state;
     DevSwarm d = dev_swarm(c);
+    const int G = d.G;
     const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // :772-774
     // clouds of more than HPE_NT / 2 points (a bound): the workgroup form's cal_cost by the
     // filter search (eval_block FILT), the same choice for every kernel of the frame
-    const bool filt = o.n > HPE_NT / 2;
+    const bool filt = io.n_max > HPE_NT / 2;
     if (pso_wave_form(c, P)) {  // one wave per particle (large swarms)
         const int wpp = pso_wpp(c, P);
         const int per_wg = PW_WPB / wpp;
@@ -824,17 +880,17 @@ static int launch_pso(hpe_ctx *c, int P, double *d_state, const DevObs &o, bool 
         auto ki = wpp == 2 ? (coop ? k_pso_init_w<2, true> : k_pso_init_w<2, false>)
                            : (coop ? k_pso_init_w<1, true> : k_pso_init_w<1, false>);
         launch(c, HPE_PROF_PSO_INIT, ki, grid, dim3(PW_NT), 0, d, (const double *)d_state,
-               c->obs_dev, (const DevHand *)c->d_hand);
+               io.obs, (const DevHand *)c->d_hand);
         const bool x = d.ext != nullptr, r16 = d.K <= 15;
         auto kw = wave_gen_kernel(wpp, coop, x, r16);
         for (int g = 1; g <= G; ++g) {
-            launch(c, HPE_PROF_PSO_GEN, kw, grid, dim3(PW_NT), 0, d, c->obs_dev,
+            launch(c, HPE_PROF_PSO_GEN, kw, grid, dim3(PW_NT), 0, d, io.obs,
                    (const DevHand *)c->d_hand, g, W1, C1, C2);
             if ((rc = exchange_after(c, d, g, G))) return rc;
         }
     } else {  // one workgroup per particle (latency form)
         launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init<true> : k_pso_init<false>, dim3(P), dim3(HPE_NT), 0, d,
-               (const double *)d_state, c->obs_dev, (const DevHand *)c->d_hand);
+               (const double *)d_state, io.obs, (const DevHand *)c->d_hand);
         static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
         for (int g = 1; g <= G; ++g) {
             const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
@@ -845,7 +901,7 @@ static int launch_pso(hpe_ctx *c, int P, double *d_state, const DevObs &o, bool 
                              : (r16 ? k_pso_gen<true, true> : k_pso_gen<false, true>))
                         : (x ? (r16 ? k_pso_gen_x<true, false> : k_pso_gen_x<false, false>)
                              : (r16 ? k_pso_gen<true, false> : k_pso_gen<false, false>)),
-                   dim3(P), dim3(HPE_NT), 0, d, c->obs_dev, (const DevHand *)c->d_hand, g,
+                   dim3(P), dim3(HPE_NT), 0, d, io.obs, (const DevHand *)c->d_hand, g,
                    W1, C1, C2, kg);
             if ((rc = exchange_after(c, d, g, G))) return rc;
         }
@@ -853,17 +909,11 @@ static int launch_pso(hpe_ctx *c, int P, double *d_state, const DevObs &o, bool 
     HIPCHK(c, hipGetLastError());
     if (tail) {
         launch(c, HPE_PROF_PSO_FINAL, filt ? k_pso_final<true, true> : k_pso_final<true, false>, dim3(1), dim3(HPE_NT), 0, d,
-               subswarm_out(c, d_state),
-               (const DevObs *)c->obs_dev, (const DevHand *)c->d_hand,
-               c->obs_dev == c->d_obs_active ? (DevObs *)nullptr : c->d_obs_active,
-               pso_wave_form(c, P) ? 0 : 1, c->pipe_counting ? c->pipe.d_seq : nullptr,
-               c->pipe_counting ? c->pipe.h_done_dev : nullptr, hist, (const int *)c->d_mw_err,
-               c->seq_mode ? (const DevObs *)c->d_obs : nullptr, c->seq_mode ? c->d_seq_obs : nullptr,
-               (c->seq_mode || c->raw_seq_mode) ? c->d_seq_cur : nullptr);
+               subswarm_out(c, d_state), io.obs, (const DevHand *)c->d_hand, io.hand_back,
+               pso_wave_form(c, P) ? 0 : 1, io.seq, io.done_host, io.hist,
+               (const int *)c->d_mw_err, io.slots, io.seq_obs, io.cur);
         HIPCHK(c, hipGetLastError());
-        if ((rc = subswarm_exchange(c, d_state, hist,
-                                    (c->seq_mode || c->raw_seq_mode) ? c->d_seq_cur + 1 : nullptr)))
-            return rc;
+        if ((rc = subswarm_exchange(c, io, pick))) return rc;
     } else {
         launch(c, HPE_PROF_PSO_FINAL, k_pso_final<false>, dim3(1), dim3(HPE_NT), 0, d, d_state,
                (const DevObs *)nullptr, (const DevHand *)nullptr, (DevObs *)nullptr, 0,
@@ -970,7 +1020,6 @@ int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
         return HPE_E_HIP;
     }
     c->slots.resize(1);
-    c->obs_dev = c->d_obs_active;
     if (const char *pf = std::getenv("HPE_PSO_FORM"))
         c->pso_form = std::strcmp(pf, "block") == 0 ? 1 : std::strcmp(pf, "wave") == 0 ? 2 : 0;
     if (const char *wp = std::getenv("HPE_PSO_WPP")) {
@@ -1450,7 +1499,8 @@ int hpe_pso_evolve(hpe_ctx *c, const double x0[26], int P, double bestp[26], dou
     if ((rc = need_frame(c, &o))) return rc;
     std::memcpy(c->h_pinned + 64, x0, sizeof(double) * HPE_DOF);
     HIPCHK(c, hipMemcpyAsync(c->d_state, c->h_pinned + 64, sizeof(double) * HPE_DOF, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_pso(c, P, c->d_state, o))) return rc;
+    if ((rc = ensure_swarm(c, P, generations(c))) || (rc = upload_bounds(c))) return rc;
+    if ((rc = launch_pso(c, P, FrameIo{c->d_obs_active, o.n, c->d_state}, false))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->d_state, sizeof(double) * 27, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(bestp, c->h_pinned, sizeof(double) * HPE_DOF);
@@ -1506,7 +1556,7 @@ int hpe_pso_optimise(hpe_ctx *c, const double x0[26], int P, double bestp[26],
     if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
     int rc = check_P(c, P);
     if (rc) return rc;
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;  // while (iter < maxiter), iter from 1
+    const int G = generations(c);  // while (iter < maxiter), iter from 1
     if (trace_len < 0 || trace_len > G || (trace_len > 0 && !gbest_trace))
         return fail(c, HPE_E_ARG, "trace length %d > maxiter-1 = %d", trace_len, G);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1542,15 +1592,15 @@ int hpe_pso_optimise(hpe_ctx *c, const double x0[26], int P, double bestp[26],
     const bool staged = o.n <= RF_STAGE_MAX;
     const unsigned lds = staged ? (unsigned)((size_t)o.n * (3 * sizeof(double) + sizeof(int32_t))) : 0u;
     launch(c, HPE_PROF_PSO_INIT, k_opt_init, dim3(P), dim3(HPE_NT), 0, d, (const double *)c->d_state,
-           c->obs_dev, (const DevHand *)c->d_hand);
+           c->d_obs_active, (const DevHand *)c->d_hand);
     for (int g = 1; g <= G; ++g) {
         if (staged)
             launch(c, HPE_PROF_OPT_DESCENT, k_opt_descent<true>, dim3(P), dim3(RF_NT), lds, d,
-                   c->obs_dev, (const DevHand *)c->d_hand, g);
+                   c->d_obs_active, (const DevHand *)c->d_hand, g);
         else
             launch(c, HPE_PROF_OPT_DESCENT, k_opt_descent<false>, dim3(P), dim3(RF_NT), lds, d,
-                   c->obs_dev, (const DevHand *)c->d_hand, g);
-        launch(c, HPE_PROF_OPT_MOVE, k_opt_move, dim3(P), dim3(HPE_NT), 0, d, c->obs_dev,
+                   c->d_obs_active, (const DevHand *)c->d_hand, g);
+        launch(c, HPE_PROF_OPT_MOVE, k_opt_move, dim3(P), dim3(HPE_NT), 0, d, c->d_obs_active,
                (const DevHand *)c->d_hand, g);
     }
     HIPCHK(c, hipGetLastError());
@@ -1582,30 +1632,29 @@ static bool mw_fits(hpe_ctx *c) {
     return c->mw_fits == 1;
 }
 
-// refine_init_pose on the selected frame (do_refine) and, when pa != NULL, the next
-// frame's preparation in the same launch (workgroups 1, 2).  n_hint bounds the cloud size.
-static int refine_launch(hpe_ctx *c, double *d_x0, int n_hint, int do_refine, const PrepArgs *pa,
-                         const PrepSplit *split = nullptr) {
-    int rc = ensure_match(c, (size_t)(n_hint > 0 ? n_hint : 1));
+// refine_init_pose on io's frame (do_refine) and, when pa != NULL, the next frame's
+// preparation in the same launch (workgroups 1, 2).  *pick: the previous frame's exchange
+// pick, which this launch takes (and empties: do_refine is the chunk loops' rule).
+static int refine_launch(hpe_ctx *c, const FrameIo &io, int do_refine, const PrepArgs *pa = nullptr,
+                         const PrepSplit *split = nullptr, DevPick *pick = nullptr) {
+    int rc = ensure_match(c, (size_t)(io.n_max > 0 ? io.n_max : 1));
     if (rc) return rc;
+    double *d_x0 = io.state;
     PrepArgs none;
     std::memset(&none, 0, sizeof(none));
     const PrepArgs a = pa ? *pa : none;
     const PrepSplit ps = (pa && split) ? *split : PrepSplit{};
     DevMw mw;
     std::memset(&mw, 0, sizeof(mw));
-    DevPick pk{};
-    if (c->ss.pending) {  // the previous frame's exchange pick (do_refine: the chunk loops' rule)
-        pk = c->ss.pick;
-        c->ss.pending = false;
-    }
-    if (n_hint <= RF_STAGE_MAX) {
+    const DevPick pk = pick ? *pick : DevPick{};
+    if (pick) *pick = DevPick{};
+    if (io.n_max <= RF_STAGE_MAX) {
         // The dynamic LDS is padded to (almost) the whole CU: no other workgroup can share
         // the CU of this single-workgroup, latency-bound kernel.  Fixed size: the launch is
         // identical for every frame.
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<true> : k_refine<true, false, true>,
-               grid, dim3(RF_NT), RF_DYN_LDS, d_x0, c->obs_dev, (const DevHand *)c->d_hand,
+               grid, dim3(RF_NT), RF_DYN_LDS, d_x0, io.obs, (const DevHand *)c->d_hand,
                c->d_match, c->d_evals, do_refine, a, mw, pk, ps);
     } else if (c->refine_mw && mw_fits(c)) {  // multi-workgroup form: MW_MAX_Q helpers own cloud slices
         mw.job = c->d_mw_job;
@@ -1618,13 +1667,13 @@ static int refine_launch(hpe_ctx *c, double *d_x0, int n_hint, int do_refine, co
         const dim3 grid(1 + MW_MAX_Q + (pa ? PREP_WG : 0));
         launch(c, HPE_PROF_REFINE,
                c->refine_exact ? k_refine<false, true> : k_refine<false, true, true>, grid,
-               dim3(RF_NT), (unsigned)prep_lds_bytes(), d_x0, c->obs_dev, (const DevHand *)c->d_hand,
+               dim3(RF_NT), (unsigned)prep_lds_bytes(), d_x0, io.obs, (const DevHand *)c->d_hand,
                c->d_match, c->d_evals, do_refine, a, mw, pk, ps);
     } else {
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<false> : k_refine<false, false, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0,
-               c->obs_dev, (const DevHand *)c->d_hand, c->d_match, c->d_evals, do_refine, a,
+               io.obs, (const DevHand *)c->d_hand, c->d_match, c->d_evals, do_refine, a,
                mw, pk, ps);
     }
     HIPCHK(c, hipGetLastError());
@@ -1654,8 +1703,17 @@ static int mw_check_async(hpe_ctx *c) {
     return HPE_OK;
 }
 
-static int refine_dev(hpe_ctx *c, double *d_x0, const DevObs &o) {
-    return refine_launch(c, d_x0, o.n, 1, nullptr);
+// One tracked frame of a single sequence (testmodel.cpp:126-132), the frame every single-sequence
+// tracking call enqueues: refine_init_pose (:126) with, when next != NULL, the following
+// frame's preparation (next_frame of the next iteration) in the same launch; then pso_evolve
+// (:130) and c = cal_cost(bestp) (:132) over the gbest cost in one final kernel, and the
+// subswarm exchange.  *pick: the exchange's deferred pick, carried from frame to frame of a chunk.
+static int track_frame(hpe_ctx *c, int P, int refine, const FrameIo &io,
+                       const PrepArgs *next = nullptr, const PrepSplit *split = nullptr,
+                       DevPick *pick = nullptr) {
+    if (refine || next)
+        if (int rc = refine_launch(c, io, refine, next, split, pick)) return rc;
+    return launch_pso(c, P, io, true, pick);
 }
 
 // What the four chunked tracking calls (sequence, raw sequence and their batches) check first.
@@ -1780,7 +1838,6 @@ int hpe_subswarm_init_scripted(hpe_ctx *c, int nranks, int rank, const double *s
         c->ss.note[0] = 0;
         ++c->epoch;
     }
-    c->ss.pending = false;
     HIPCHK(c, hipMemcpy(c->ss.d_script, script, sizeof(double) * n, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(c->ss.d_script_k, 0, sizeof(int)));  // rewound
     HIPCHK(c, hipMemset(c->ss.d_gath, 0xFF, sizeof(double) * rows));  // NaN
@@ -1895,22 +1952,13 @@ int hpe_refine_init_pose(hpe_ctx *c, double x0[26], int32_t *evals_out) {
     if (rc) return rc;
     std::memcpy(c->h_pinned + 64, x0, sizeof(double) * HPE_DOF);
     HIPCHK(c, hipMemcpyAsync(c->d_state, c->h_pinned + 64, sizeof(double) * HPE_DOF, hipMemcpyHostToDevice, c->stream));
-    if ((rc = refine_dev(c, c->d_state, o))) return rc;
+    if ((rc = refine_launch(c, FrameIo{c->d_obs_active, o.n, c->d_state}, 1))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->d_state, sizeof(double) * HPE_DOF, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_pinned + 32, c->d_evals, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((rc = mw_check(c))) return rc;
     std::memcpy(x0, c->h_pinned, sizeof(double) * HPE_DOF);
     if (evals_out) std::memcpy(evals_out, c->h_pinned + 32, sizeof(int));
-    return HPE_OK;
-}
-
-// The launches of one tracked frame (testmodel.cpp:126-132).
-static int enqueue_frame(hpe_ctx *c, int P, int refine, double *d_state, const DevObs &o) {
-    int rc;
-    if (refine && (rc = refine_dev(c, d_state, o))) return rc;  // testmodel.cpp:126
-    // pso_evolve (:130), then c = cal_cost(bestp) (:132) over the gbest cost, one kernel
-    if ((rc = launch_pso(c, P, d_state, o, true))) return rc;
     return HPE_OK;
 }
 
@@ -1926,17 +1974,14 @@ int hpe_track_frame_dev(hpe_ctx *c, int P, int refine, double *d_state) {
         return fail(c, HPE_E_STATE, "no frame selected (hpe_set_frame / hpe_select_frame)");
     // host-side launch decisions need only a bound on n (no readback of a device-prepared
     // frame): the staged refine for clouds that fit LDS
-    DevObs o = make_obs(c->slots[c->cur]);
-    o.n = c->slots[c->cur].n_max;
+    const FrameIo io{c->d_obs_active, c->slots[c->cur].n_max, d_state};
     // allocate everything the frame touches before any capture
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
-    if ((rc = ensure_match(c, (size_t)HPE_IMG_H * HPE_IMG_W))) return rc;
-    if ((rc = ensure_swarm(c, P, G))) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+    const int G = ensure_tracking(c, P, 0);
+    if (G < 0) return G;
     GraphKey key = graph_key(P, G, refine, d_state);
-    key.staged = o.n <= RF_STAGE_MAX;
+    key.staged = io.n_max <= RF_STAGE_MAX;
     return run_graphed(c, c->graphs[hpe_ctx::GC_FRAME], key,
-                       [&] { return enqueue_frame(c, P, refine, d_state, o); });
+                       [&] { return track_frame(c, P, refine, io); });
 }
 
 int hpe_track_frame(hpe_ctx *c, int P, int refine, double x0[26], double *cost_out) {
@@ -2037,30 +2082,13 @@ int hpe_pipeline_begin(hpe_ctx *c, const float *depth_mm, int to_cm, int downsam
     return HPE_OK;
 }
 
-// One tracked frame of the pipeline: select its descriptor, [H2D of the next raw frame],
-// refine (+ the next frame's preparation in the same launch), pso_evolve, cal_cost(bestp).
-static int enqueue_pipe_frame(hpe_ctx *c, int P, int refine, double *d_state, int next) {
-    hpe_ctx::Pipe &pp = c->pipe;
-    const int cur = pp.cur, nxt = cur ^ 1;
-    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
-    PrepArgs pa;
-    if (next) {  // raw frame in its pinned host buffer (zero copy) or uploaded to d_raw[nxt]
-        pa = prep_args(c, pp.fr[nxt], pp.zero_copy ? pp.h_raw_dev[nxt] : pp.d_raw + nxt * npix,
-                       pp.to_cm, pp.downsample, pp.focal,
-                       pp.d_obs + nxt,
-                       pp.d_info + nxt);
-    }
-    // the kernels read this buffer's descriptor directly (the graph is per parity); the
-    // final kernel hands it back to d_obs_active for the API's later calls
-    c->obs_dev = pp.d_obs + cur;
-    int rc = HPE_OK;
-    if (refine || next)  // testmodel.cpp:126 (+ next_frame of the following iteration)
-        rc = refine_launch(c, d_state, pp.fr[cur].n_max, refine, next ? &pa : nullptr);
-    DevObs on{};
-    on.n = pp.fr[cur].n_max;  // a bound on n decides the kernel forms
-    if (!rc) rc = launch_pso(c, P, d_state, on, true);  // :130, :132
-    c->obs_dev = c->d_obs_active;
-    return rc;
+// A tracked frame in the pipeline's prepared buffer `cur` (the pipelined loop, a raw sequence):
+// the kernels read that buffer's descriptor directly (a graph is per parity), and the final
+// kernel hands it back to d_obs_active for the API's later calls.
+static FrameIo pipe_frame_io(hpe_ctx *c, int cur, double *d_state, double *hist = nullptr) {
+    FrameIo io{c->pipe.d_obs + cur, c->pipe.fr[cur].n_max, d_state, hist};
+    io.hand_back = c->d_obs_active;
+    return io;
 }
 
 // k frames of an offline sequence, one after the other on the tracking stream: each
@@ -2071,22 +2099,18 @@ static int enqueue_pipe_frame(hpe_ctx *c, int P, int refine, double *d_state, in
 // every chunk of the same shape, whatever its slots.
 static int enqueue_seq_chunk(hpe_ctx *c, int P, int refine, double *d_state, int slot0, int k,
                              double *hist) {
-    int rc = HPE_OK;
-    c->obs_dev = c->d_seq_obs;  // k_pso_final hands each frame back to d_obs_active
-    c->seq_mode = true;
-    for (int i = 0; i < k && !rc; ++i) {
-        Slot &s = c->slots[slot0 + i];
-        DevObs o = make_obs(s);
-        o.n = s.n_max;  // host-side launch decisions need only a bound on n
-        if (refine) rc = refine_launch(c, d_state, o.n, 1, nullptr);  // testmodel.cpp:126
-        c->ss.defer = refine && i + 1 < k;  // the next frame's refine takes the exchange's pick
-        if (!rc) rc = launch_pso(c, P, d_state, o, true, hist);       // :130, :132
-        c->ss.defer = false;
+    DevPick pick{};  // the exchange's, from a frame to the next one's refine launch
+    for (int i = 0; i < k; ++i) {
+        // host-side launch decisions need only a bound on n
+        FrameIo io{c->d_seq_obs, c->slots[slot0 + i].n_max, d_state, hist};
+        io.hand_back = c->d_obs_active;  // each frame, for the API's later calls
+        io.slots = c->d_obs;
+        io.seq_obs = c->d_seq_obs;
+        io.cur = c->d_seq_cur;
+        io.defer_pick = refine && i + 1 < k;
+        if (int rc = track_frame(c, P, refine, io, nullptr, nullptr, &pick)) return rc;
     }
-    c->ss.pending = false;
-    c->seq_mode = false;
-    c->obs_dev = c->d_obs_active;
-    return rc;
+    return HPE_OK;
 }
 
 int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int first_slot,
@@ -2102,10 +2126,8 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
         if (!c->slots[first_slot + f].valid)
             return fail(c, HPE_E_ARG, "slot %d holds no frame", first_slot + f);
     HIPCHK(c, hipSetDevice(c->device));
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
-    if ((rc = ensure_match(c, (size_t)HPE_IMG_H * HPE_IMG_W))) return rc;
-    if ((rc = ensure_swarm(c, P, G))) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+    const int G = ensure_tracking(c, P, 0);
+    if (G < 0) return G;
     // frames prepared on the preprocessing stream: the tracking stream waits for the ones
     // still running, once, before the first chunk (no markers between chunks)
     for (int f = 0; f < n; ++f) {
@@ -2138,78 +2160,59 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
     return mark_seq_done(c);
 }
 
-// (defined below its first caller: the _b kernels are emitted in the order the host code first
-// names them, and the code object stays byte for byte what it was with k_refine_b first)
-typedef void (*LaneFinalFn)(DevSwarm, size_t, double *, DevObs *, const DevHand *, DevObs *, int,
-                            unsigned long long *, unsigned long long *, double *, const int *,
-                            const DevObs *, int *);
-static int launch_pso_lanes(hpe_ctx *c, int P, int B, const DevSwarm &d, double *d_states,
-                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur,
-                            LaneFinalFn live_final = nullptr, unsigned long long *seq = nullptr,
-                            unsigned long long *done_host = nullptr);
-
-// k frames of B lanes, one after the other on the tracking stream: per frame the launches of
-// enqueue_seq_chunk with a lane dimension -- refine on grid (1, B), then launch_pso_lanes --
-// each lane on its own descriptor d_bobs[b], cursor d_bcur[2 b] and arena.  filt: bit i = frame
-// i takes the FILT kernels (all lanes agree).
-static int enqueue_batch_chunk(hpe_ctx *c, int P, int refine, int B, double *d_states, unsigned filt,
-                               int k, double *hist) {
-    const DevSwarm d = batch_swarm(c);
-    for (int i = 0; i < k; ++i) {
-        if (refine)  // testmodel.cpp:126; the CU-filling LDS size puts the lanes on B CUs
-            launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
-                   dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)c->d_bobs,
-                   (const DevHand *)c->d_hand, c->d_bevals);
-        if (int rc = launch_pso_lanes(c, P, B, d, d_states, c->d_bobs, (filt >> i) & 1u, hist,
-                                      c->d_obs, c->d_bcur))
-            return rc;
-    }
-    return HPE_OK;
-}
-
 // pso_evolve and cal_cost(bestp) of one frame for B lanes: launch_pso's workgroup form with a
 // lane dimension -- init and the generations on (P, B), the final kernel on (1, B) -- lane b on
-// descriptor obs[b], arena b of d (batch_swarm) and cursor cur[2 b].  filt: the FILT kernels.
-// slots: the descriptor table the final kernel stages lane b's next frame from (null: the raw
-// lanes' preparation does that, and the cursor's slot word counts frames).  live_final (the live
-// batch): that final kernel in k_pso_final_b's place, with the batch's frame counter seq and the
-// host word done_host it publishes to.
-static int launch_pso_lanes(hpe_ctx *c, int P, int B, const DevSwarm &d, double *d_states,
-                            DevObs *obs, bool filt, double *hist, const DevObs *slots, int *cur,
-                            LaneFinalFn live_final, unsigned long long *seq,
-                            unsigned long long *done_host) {
+// descriptor io.obs[b], arena b of the swarm (batch_swarm) and cursor io.cur[2 b].  With a frame
+// counter (the live batch), k_pso_final_live_b stands in k_pso_final_b's place.
+static int launch_pso_lanes(hpe_ctx *c, int P, int B, double *d_states, const LaneFrameIo &io) {
+    const DevSwarm d = batch_swarm(c);
     const size_t stride = c->sw.stride;
     const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
     static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
-    const bool r16 = d.K <= 15;
+    const bool r16 = d.K <= 15, filt = io.filt;
     const DevHand *hand = c->d_hand;
     launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init_b<true> : k_pso_init_b<false>, dim3(P, B),
-           dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)obs, hand);
+           dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)io.obs, hand);
     for (int g = 1; g <= d.G; ++g) {
         const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
         launch(c, HPE_PROF_PSO_GEN,
                filt ? (r16 ? k_pso_gen_b<true, true> : k_pso_gen_b<false, true>)
                     : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
-               dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)obs, hand, g, W1, C1, C2, kg);
+               dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)io.obs, hand, g, W1, C1, C2, kg);
     }
-    const LaneFinalFn final_k =
-        live_final ? live_final : (filt ? k_pso_final_b<true> : k_pso_final_b<false>);
-    launch(c, HPE_PROF_PSO_FINAL, final_k, dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states, obs,
-           hand, (DevObs *)nullptr, 1, seq, done_host, hist, (const int *)nullptr, slots, cur);
+    // every live cloud is bounded by 250 points: the non-FILT kernel
+    auto final_k = io.seq ? k_pso_final_live_b<false>
+                          : (filt ? k_pso_final_b<true> : k_pso_final_b<false>);
+    launch(c, HPE_PROF_PSO_FINAL, final_k, dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states, io.obs,
+           hand, (DevObs *)nullptr, 1, io.seq, io.done_host, io.hist, (const int *)nullptr, io.slots,
+           io.cur);
     HIPCHK(c, hipGetLastError());
     return HPE_OK;
 }
 
-// The lanes' descriptors, cursors and refine evaluation counters (both batch calls count in
-// d_bevals).
-static int ensure_batch_lanes(hpe_ctx *c) {
-    if (!c->d_bobs) {
-        HIPCHK(c, dalloc(&c->d_bobs, HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&c->d_bcur, 2 * HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&c->d_bevals, HPE_BATCH_MAX * HPE_EVALS_N));
-        HIPCHK(c, hipMemset(c->d_bevals, 0, sizeof(int) * HPE_BATCH_MAX * HPE_EVALS_N));
-    }
-    return HPE_OK;
+// One tracked frame of B lanes, the frame every batch call enqueues: track_frame's launches with a
+// lane dimension, each lane on its own descriptor, cursor and arena.  The refine launch (the
+// CU-filling LDS size puts the lanes on B CUs) is on grid (1, B), or with io.prep on
+// (1 + PREP_WG, B): it then carries every lane's next preparation, read through the raw cursor or
+// from the pinned ring, as a raw sequence's and the pipelined loop's do.  Then launch_pso_lanes.
+// (The _b kernels are emitted in the order the host code first names them: k_pso_init_b first.)
+static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                            const LaneFrameIo &io) {
+    const DevObs *obs = io.obs;
+    const DevHand *hand = c->d_hand;
+    const dim3 prep_grid(1 + PREP_WG, B);
+    if (io.prep && io.raw)  // testmodel.cpp:126 + next_frame of the following iteration
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_prep_b<false> : k_refine_prep_b<true>,
+               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals,
+               refine ? 1 : 0, io.prep, io.raw, (const int *)io.cur);
+    else if (io.prep)
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_ring_b<false> : k_refine_ring_b<true>,
+               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals,
+               refine ? 1 : 0, io.prep);
+    else if (refine)  // testmodel.cpp:126
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
+               dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals);
+    return launch_pso_lanes(c, P, B, d_states, io);
 }
 
 int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
@@ -2236,10 +2239,8 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
         }
     }
     HIPCHK(c, hipSetDevice(c->device));
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
-    if ((rc = ensure_batch_lanes(c))) return rc;
-    if ((rc = ensure_swarm(c, P, G, B))) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+    const int G = ensure_tracking(c, P, B);
+    if (G < 0) return G;
     // frames prepared on the preprocessing stream: the tracking stream waits for the ones
     // still running, once, before the first chunk
     for (int b = 0; b < B; ++b)
@@ -2261,8 +2262,16 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
         key.B = B;
         for (int i = 0; i < k; ++i)
             if (c->slots[first_slots[0] + f0 + i].n_max > HPE_NT / 2) key.filt |= 1u << i;
+        // k frames of B lanes, one after the other on the tracking stream: each lane on its own
+        // descriptor d_bobs[b] and cursor d_bcur[2 b], its next frame staged from the slot table
         if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_BATCH], key, [&] {
-                 return enqueue_batch_chunk(c, P, refine, B, d_states, key.filt, k, d_hist);
+                 int erc = HPE_OK;
+                 for (int i = 0; i < k && !erc; ++i) {
+                     const bool filt = (key.filt >> i) & 1u;
+                     erc = track_lane_frame(c, P, refine, B, d_states,
+                                            LaneFrameIo{c->d_bobs, filt, d_hist, c->d_obs, c->d_bcur});
+                 }
+                 return erc;
              })))
             return rc;
     }
@@ -2312,20 +2321,23 @@ int hpe_track_pipelined(hpe_ctx *c, int P, int refine, double *d_state, const fl
             HIPCHK(c, hipStreamWaitEvent(c->stream, pp.raw_ready[nxt], 0));
         }
     }
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
-    if ((rc = ensure_match(c, npix))) return rc;
-    if ((rc = ensure_swarm(c, P, G))) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+    const int G = ensure_tracking(c, P, 0);
+    if (G < 0) return G;
     GraphKey key = graph_key(P, G, refine, d_state);
     key.staged = pp.fr[cur].n_max <= RF_STAGE_MAX;
     key.next = next;
     key.cur = cur;
-    rc = run_graphed(c, c->graphs[hpe_ctx::GC_PIPE], key, [&] {
-        c->pipe_counting = pp.zero_copy;  // the final kernel publishes the frame's number
-        const int erc = enqueue_pipe_frame(c, P, refine, d_state, next);
-        c->pipe_counting = false;
-        return erc;
-    });
+    FrameIo io = pipe_frame_io(c, cur, d_state);
+    if (pp.zero_copy) {  // the final kernel publishes the frame's number
+        io.seq = pp.d_seq;
+        io.done_host = pp.h_done_dev;
+    }
+    // the next raw frame: in its pinned host buffer (zero copy) or uploaded to d_raw[nxt]
+    const float *raw = pp.zero_copy ? pp.h_raw_dev[nxt] : pp.d_raw + nxt * npix;
+    const PrepArgs pa = prep_args(c, pp.fr[nxt], raw, pp.to_cm, pp.downsample, pp.focal,
+                                  pp.d_obs + nxt, pp.d_info + nxt);
+    rc = run_graphed(c, c->graphs[hpe_ctx::GC_PIPE], key,
+                     [&] { return track_frame(c, P, refine, io, next ? &pa : nullptr); });
     if (rc) return rc;
     ++pp.enq;  // this frame's number; its final kernel publishes it to h_done
     if (next) {
@@ -2351,9 +2363,8 @@ static int enqueue_raw_chunk(hpe_ctx *c, int P, int refine, double *d_state, con
                              int parity, int k, bool tail_next, double *hist) {
     hpe_ctx::Pipe &pp = c->pipe;
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
-    int rc = HPE_OK;
-    c->raw_seq_mode = true;
-    for (int i = 0; i < k && !rc; ++i) {
+    DevPick pick{};  // the exchange's, from a frame to the next one's refine launch
+    for (int i = 0; i < k; ++i) {
         const int cur = (parity + i) & 1, nxt = cur ^ 1;
         const bool next = i + 1 < k || tail_next;
         PrepArgs pa = prep_args(c, pp.fr[nxt], raw, pp.to_cm, pp.downsample, pp.focal,
@@ -2371,19 +2382,12 @@ static int enqueue_raw_chunk(hpe_ctx *c, int P, int refine, double *d_state, con
             ps.r0_next = pp.d_split + cur;
             ps.seq_n = pp.d_split + 2;
         }
-        c->obs_dev = pp.d_obs + cur;
-        if (refine || next)  // testmodel.cpp:126 (+ next_frame of the following iteration)
-            rc = refine_launch(c, d_state, pp.fr[cur].n_max, refine, next ? &pa : nullptr, &ps);
-        DevObs on{};
-        on.n = pp.fr[cur].n_max;  // a bound on n decides the kernel forms
-        c->ss.defer = refine && i + 1 < k;  // the next frame's refine takes the exchange's pick
-        if (!rc) rc = launch_pso(c, P, d_state, on, true, hist);  // :130, :132
-        c->ss.defer = false;
+        FrameIo io = pipe_frame_io(c, cur, d_state, hist);
+        io.cur = c->d_seq_cur;  // the row cursor alone
+        io.defer_pick = refine && i + 1 < k;
+        if (int rc = track_frame(c, P, refine, io, next ? &pa : nullptr, &ps, &pick)) return rc;
     }
-    c->ss.pending = false;
-    c->raw_seq_mode = false;
-    c->obs_dev = c->d_obs_active;
-    return rc;
+    return HPE_OK;
 }
 
 int hpe_track_raw_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state,
@@ -2407,10 +2411,8 @@ int hpe_track_raw_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state,
     pp.downsample = downsample ? 1 : 0;
     pp.focal = focal;
     pp.cur = -1;  // a pipelined sequence in progress ends here
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
-    if ((rc = ensure_match(c, npix))) return rc;
-    if ((rc = ensure_swarm(c, P, G))) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+    const int G = ensure_tracking(c, P, 0);
+    if (G < 0) return G;
     // frame 0 prepared on the tracking stream, the row cursor at 0
     HIPCHK(c, hipMemsetAsync(c->d_seq_cur, 0, 2 * sizeof(int), c->stream));
     PrepArgs p0 = prep_args(c, pp.fr[0], d_raw_mm, pp.to_cm, pp.downsample, focal, pp.d_obs,
@@ -2539,32 +2541,19 @@ static int ensure_raw_batch(hpe_ctx *c, int B, int to_cm, double focal) {
 }
 
 // k frames of B raw lanes, the first in the lanes' prepared buffers `parity`: per frame the
-// launches of enqueue_batch_chunk on the parity's descriptors, the refine launch carrying every
-// lane's next preparation (grid (1 + PREP_WG, B)) whenever a next frame exists, as
-// enqueue_raw_chunk's does for one sequence.  Every cloud is bounded by 250 points: the staged
-// refine and the non-FILT kernels.
+// launches of a prepared batch's on the parity's descriptors, the refine launch carrying every
+// lane's next preparation whenever a next frame exists, as enqueue_raw_chunk's does for one
+// sequence.  Every cloud is bounded by 250 points: the staged refine and the non-FILT kernels.
 static int enqueue_raw_batch_chunk(hpe_ctx *c, int P, int refine, int B, double *d_states,
                                    int parity, int k, bool tail_next, double *hist) {
     hpe_ctx::RawBatch &rb = c->rb;
-    const DevSwarm d = batch_swarm(c);
-    const DevHand *hand = c->d_hand;
     for (int i = 0; i < k; ++i) {
         const int cur = (parity + i) & 1, nxt = cur ^ 1;
-        const bool next = i + 1 < k || tail_next;
-        DevObs *obs = rb.d_obs + cur * HPE_BATCH_MAX;
-        if (next)  // testmodel.cpp:126 + next_frame of the following iteration
-            launch(c, HPE_PROF_REFINE,
-                   c->refine_exact ? k_refine_prep_b<false> : k_refine_prep_b<true>,
-                   dim3(1 + PREP_WG, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
-                   c->d_bevals, refine ? 1 : 0, (const PrepArgs *)(rb.d_tab + nxt * HPE_BATCH_MAX),
-                   (const float *const *)rb.d_raw, (const int *)rb.d_cur);
-        else if (refine)
-            launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
-                   dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
-                   c->d_bevals);
         // no slot table: the cursor's slot word counts the lane's frames (the preparation's)
-        if (int rc = launch_pso_lanes(c, P, B, d, d_states, obs, false, hist, nullptr, rb.d_cur))
-            return rc;
+        LaneFrameIo io{rb.d_obs + cur * HPE_BATCH_MAX, false, hist, nullptr, rb.d_cur};
+        if (i + 1 < k || tail_next) io.prep = rb.d_tab + nxt * HPE_BATCH_MAX;
+        io.raw = rb.d_raw;
+        if (int rc = track_lane_frame(c, P, refine, B, d_states, io)) return rc;
     }
     return HPE_OK;
 }
@@ -2584,12 +2573,10 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
         return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
                     "the single-workgroup refine (<= %d)", HPE_IMG_H * HPE_IMG_W, RF_STAGE_MAX);
     HIPCHK(c, hipSetDevice(c->device));
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
     to_cm = to_cm ? 1 : 0;
-    if ((rc = ensure_batch_lanes(c))) return rc;
     if ((rc = ensure_raw_batch(c, B, to_cm, focal))) return rc;
-    if ((rc = ensure_swarm(c, P, G, B))) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+    const int G = ensure_tracking(c, P, B);
+    if (G < 0) return G;
     c->live.cur = -1;  // a live batch in progress (the same lane buffers) ends here
     hpe_ctx::RawBatch &rb = c->rb;
     // the lanes' raw bases and cursors, then frame 0 of every lane into buffer parity 0
@@ -2707,27 +2694,6 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     return HPE_OK;
 }
 
-// One tracked frame of the live batch, the current frames in the lanes' buffers `cur`: a frame of
-// enqueue_raw_batch_chunk with the ring's preparation (the next frames read from the pinned
-// buffers of parity cur ^ 1) and the final launch that publishes the batch's frame number.
-static int enqueue_live_batch_frame(hpe_ctx *c, int P, int refine, int B, double *d_states, int cur,
-                                    int next) {
-    hpe_ctx::LiveBatch &lv = c->live;
-    const DevSwarm d = batch_swarm(c);
-    const DevHand *hand = c->d_hand;
-    DevObs *obs = c->rb.d_obs + cur * HPE_BATCH_MAX;
-    if (next)  // testmodel.cpp:126 + next_frame of the following iteration
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_ring_b<false> : k_refine_ring_b<true>,
-               dim3(1 + PREP_WG, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
-               c->d_bevals, refine ? 1 : 0, (const PrepArgs *)(lv.d_tab + (cur ^ 1) * HPE_BATCH_MAX));
-    else if (refine)
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
-               dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, (const DevObs *)obs, hand,
-               c->d_bevals);
-    return launch_pso_lanes(c, P, B, d, d_states, obs, false, nullptr, nullptr, nullptr,
-                            k_pso_final_live_b<false>, lv.d_seq, lv.h_done_dev);
-}
-
 int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_states,
                               const float *const *next_depth_mm) {
     if (!c) return HPE_E_ARG;
@@ -2756,9 +2722,8 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
         for (int b = 0; b < B; ++b)
             std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], sizeof(float) * npix);
     }
-    const int G = c->maxiter - 1 > 0 ? c->maxiter - 1 : 0;
-    if ((rc = ensure_swarm(c, P, G, B))) return rc;
-    if ((rc = upload_bounds(c))) return rc;
+    const int G = ensure_tracking(c, P, B);  // (the lanes' tables are the begin's)
+    if (G < 0) return G;
     GraphKey key = graph_key(P, G, refine, d_states);  // the shape: never a host pointer
     key.B = B;
     key.cur = cur;
@@ -2766,9 +2731,15 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     key.to_cm = lv.to_cm;
     key.downsample = 1;
     key.focal = lv.focal;
-    if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_LIVE_BATCH], key, [&] {
-             return enqueue_live_batch_frame(c, P, refine, B, d_states, cur, next);
-         })))
+    // a frame of a raw batch's on the descriptors of parity cur, with the ring's preparation (the
+    // next frames read from the pinned buffers of parity nxt), no history or cursor, and the final
+    // launch that publishes the batch's frame number
+    LaneFrameIo io{c->rb.d_obs + cur * HPE_BATCH_MAX, false, nullptr, nullptr, nullptr};
+    if (next) io.prep = lv.d_tab + nxt * HPE_BATCH_MAX;
+    io.seq = lv.d_seq;
+    io.done_host = lv.h_done_dev;
+    if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_LIVE_BATCH], key,
+                          [&] { return track_lane_frame(c, P, refine, B, d_states, io); })))
         return rc;
     ++lv.enq;  // this frame's number; lane 0's final workgroup publishes it to h_done
     if (next) lv.used_seq[nxt] = lv.enq;  // its refine launch reads h_raw[nxt]
