@@ -49,11 +49,12 @@ struct Swarm {
     Sig *sig = nullptr;
     int *outl = nullptr;
     std::vector<InboxCounts> kin;  // per generation 0..G (P <= KIN_MAX)
-    // hpe_track_batch_dev: the mutable arrays (xh, pch, pb, v, inbox, gmin, sig, gpos) of
-    // `lanes` lanes, one arena per lane `stride` bytes apart; off[]: the arrays within an arena.
+    // hpe_track_batch_dev: the mutable arrays (xh, pch, pb, v, inbox, gmin, sig, gpos, and last
+    // ibtc, which only wave-form lanes touch) of `lanes` lanes, one arena per lane `stride` bytes
+    // apart; off[]: the arrays within an arena.
     // The arrays above stay the single-sequence calls' own (their cached graphs keep them).
     char *arena = nullptr;
-    size_t stride = 0, off[8] = {0};
+    size_t stride = 0, off[9] = {0};
     int lanes = 0;
 };
 
@@ -112,13 +113,14 @@ struct GraphKey {
     // kernels (n_max > HPE_NT / 2, launch_pso's choice)
     unsigned staged, filt;
     int parity, tail_next, next, cur, B, to_cm, downsample;
+    int wave;  // a batch in the wave form (hpe_set_batch_form): its waves per particle; else 0
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
     bool operator==(const GraphKey &o) const {  // written out: the struct has padding
         return P == o.P && G == o.G && refine == o.refine && k == o.k && staged == o.staged &&
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
-               next == o.next && cur == o.cur && B == o.B && to_cm == o.to_cm &&
+               next == o.next && cur == o.cur && B == o.B && wave == o.wave && to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -313,6 +315,7 @@ struct hpe_ctx {
     hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
     unsigned epoch = 1;  // bumped whenever a buffer a captured graph uses is reallocated
+    int batch_form = HPE_BATCH_FORM_AUTO;  // the batch calls' pso_evolve form (hpe_set_batch_form)
     int pso_form = 0;    // 0 auto, 1 workgroup per particle, 2 wave per particle
     static constexpr int wave_form_min_p = 1024;
     int pso_wpp = 0;      // waves per particle of the wave form (0: auto)
@@ -529,23 +532,24 @@ static int ensure_lanes(hpe_ctx *c, int lanes) {
     dfree(s.arena);
     s.lanes = 0;
     const size_t n = (size_t)s.P * HPE_DOF, G1 = (size_t)s.G + 1;
-    const size_t bytes[8] = {sizeof(double) * G1 * n,                                      // xh
+    const size_t bytes[9] = {sizeof(double) * G1 * n,                                      // xh
                              sizeof(double) * G1 * s.P,                                    // pch
                              sizeof(double) * n,                                           // pb
                              sizeof(double) * n,                                           // v
                              sizeof(double) * 4 * s.P * s.K * IB_STRIDE,                   // inbox
                              sizeof(unsigned long long) * G1 * GMIN_SHARDS * GMIN_STRIDE,  // gmin
                              sizeof(Sig) * G1,                                             // sig
-                             sizeof(double) * HPE_DOF};                                    // gpos
+                             sizeof(double) * HPE_DOF,                                     // gpos
+                             sizeof(double) * 8 * s.P * s.K};                              // ibtc
     size_t at = 0;
-    for (int k = 0; k < 8; ++k) {  // every array on a 256-byte boundary, as hipMalloc gives
+    for (int k = 0; k < 9; ++k) {  // every array on a 256-byte boundary, as hipMalloc gives
         s.off[k] = at;
         at += (bytes[k] + 255) & ~(size_t)255;
     }
     s.stride = at;
     HIPCHK(c, dalloc(&s.arena, s.stride * lanes));
-    // empty inbox slots (tag -1) and unwritten gmin cells are all-ones; the rest is written
-    // before it is read
+    // empty inbox and ibtc slots (tag -1) and unwritten gmin cells are all-ones; the rest is
+    // written before it is read
     HIPCHK(c, hipMemset(s.arena, 0xFF, s.stride * lanes));
     s.lanes = lanes;
     return HPE_OK;
@@ -646,6 +650,7 @@ static DevSwarm batch_swarm(hpe_ctx *c) {
     d.gmin = (unsigned long long *)(s.arena + s.off[5]);
     d.sig = (Sig *)(s.arena + s.off[6]);
     d.gpos = (double *)(s.arena + s.off[7]);
+    d.ibtc = (double *)(s.arena + s.off[8]);
     d.trace_g = nullptr;
     d.trace_count = d.trace_topo = nullptr;
     d.ext = nullptr;
@@ -672,6 +677,17 @@ static WaveGenFn wave_gen_kernel(int wpp, bool coop, bool x, bool r16) {
     if (wpp == 2) return coop ? wave_gen_kernel_t<2, true>(x, r16) : wave_gen_kernel_t<2, false>(x, r16);
     return coop ? wave_gen_kernel_t<1, true>(x, r16) : wave_gen_kernel_t<1, false>(x, r16);
 }
+// ... and its lane form's (no exchange)
+typedef void (*WaveLaneGenFn)(DevSwarm, size_t, const DevObs *, const DevHand *, int, double, double,
+                              double);
+template <int WPP, bool COOP>
+static WaveLaneGenFn wave_lane_gen_kernel_t(bool r16) {
+    return r16 ? k_pso_gen_wb<true, WPP, COOP> : k_pso_gen_wb<false, WPP, COOP>;
+}
+static WaveLaneGenFn wave_lane_gen_kernel(int wpp, bool coop, bool r16) {
+    if (wpp == 2) return coop ? wave_lane_gen_kernel_t<2, true>(r16) : wave_lane_gen_kernel_t<2, false>(r16);
+    return coop ? wave_lane_gen_kernel_t<1, true>(r16) : wave_lane_gen_kernel_t<1, false>(r16);
+}
 
 // Waves per particle of the wave form: two while the swarm leaves SIMDs idle at one (the
 // search's latency halves), one beyond (the duplicated FK would cost throughput).
@@ -679,6 +695,11 @@ static WaveGenFn wave_gen_kernel(int wpp, bool coop, bool x, bool r16) {
 static int pso_wpp(hpe_ctx *c, int P) {
     if (c->pso_wpp) return c->pso_wpp;
     return P <= c->wpp2_max_p ? 2 : 1;
+}
+// ... of a wave-form batch (hpe_set_batch_form): the rule on the launch's B * P particles, and
+// zero for a batch in the workgroup form (the batch graphs' key field).
+static int batch_wave_wpp(hpe_ctx *c, int P, int B) {
+    return c->batch_form == HPE_BATCH_FORM_WAVE ? pso_wpp(c, B * P) : 0;
 }
 
 // PSO bounds / std to HBM when they changed (synchronous: never inside a graph capture).
@@ -1731,7 +1752,7 @@ static int check_chunked_call(hpe_ctx *c, int P, int frames_per_graph) {
 static int check_batch_call(hpe_ctx *c, int P, int B) {
     if (B < 1 || B > HPE_BATCH_MAX)
         return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
-    if (pso_wave_form(c, P))
+    if (c->batch_form == HPE_BATCH_FORM_AUTO && pso_wave_form(c, P))
         return fail(c, HPE_E_ARG, "num_p %d takes the wave form: a batch needs the workgroup form "
                     "(num_p < %d)", P, c->wave_form_min_p);
     if (c->ss.transport())
@@ -2164,6 +2185,9 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
 // lane dimension -- init and the generations on (P, B), the final kernel on (1, B) -- lane b on
 // descriptor io.obs[b], arena b of the swarm (batch_swarm) and cursor io.cur[2 b].  With a frame
 // counter (the live batch), k_pso_final_live_b stands in k_pso_final_b's place.
+// HPE_BATCH_FORM_WAVE: launch_pso's wave form with the lane dimension instead -- init and the
+// generations on (ceil(P / particles per workgroup), B) at pso_wpp(B * P) waves per particle, no
+// inbox counts -- and the same final kernels with same_eval = 0: they evaluate cal_cost(bestp).
 static int launch_pso_lanes(hpe_ctx *c, int P, int B, double *d_states, const LaneFrameIo &io) {
     const DevSwarm d = batch_swarm(c);
     const size_t stride = c->sw.stride;
@@ -2171,21 +2195,37 @@ static int launch_pso_lanes(hpe_ctx *c, int P, int B, double *d_states, const La
     static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
     const bool r16 = d.K <= 15, filt = io.filt;
     const DevHand *hand = c->d_hand;
-    launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init_b<true> : k_pso_init_b<false>, dim3(P, B),
-           dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)io.obs, hand);
-    for (int g = 1; g <= d.G; ++g) {
-        const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
-        launch(c, HPE_PROF_PSO_GEN,
-               filt ? (r16 ? k_pso_gen_b<true, true> : k_pso_gen_b<false, true>)
-                    : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
-               dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)io.obs, hand, g, W1, C1, C2, kg);
+    const int wpp = batch_wave_wpp(c, P, B);
+    if (wpp) {  // one or two waves per particle
+        const int per_wg = PW_WPB / wpp;
+        const dim3 grid((P + per_wg - 1) / per_wg, B);
+        const bool coop = c->fk_coop;
+        auto ki = wpp == 2 ? (coop ? k_pso_init_wb<2, true> : k_pso_init_wb<2, false>)
+                           : (coop ? k_pso_init_wb<1, true> : k_pso_init_wb<1, false>);
+        launch(c, HPE_PROF_PSO_INIT, ki, grid, dim3(PW_NT), 0, d, stride, (const double *)d_states,
+               (const DevObs *)io.obs, hand);
+        auto kw = wave_lane_gen_kernel(wpp, coop, r16);
+        for (int g = 1; g <= d.G; ++g)
+            launch(c, HPE_PROF_PSO_GEN, kw, grid, dim3(PW_NT), 0, d, stride, (const DevObs *)io.obs,
+                   hand, g, W1, C1, C2);
+    } else {
+        launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init_b<true> : k_pso_init_b<false>, dim3(P, B),
+               dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)io.obs, hand);
+        for (int g = 1; g <= d.G; ++g) {
+            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
+            launch(c, HPE_PROF_PSO_GEN,
+                   filt ? (r16 ? k_pso_gen_b<true, true> : k_pso_gen_b<false, true>)
+                        : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
+                   dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)io.obs, hand, g, W1, C1, C2,
+                   kg);
+        }
     }
     // every live cloud is bounded by 250 points: the non-FILT kernel
     auto final_k = io.seq ? k_pso_final_live_b<false>
                           : (filt ? k_pso_final_b<true> : k_pso_final_b<false>);
     launch(c, HPE_PROF_PSO_FINAL, final_k, dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states, io.obs,
-           hand, (DevObs *)nullptr, 1, io.seq, io.done_host, io.hist, (const int *)nullptr, io.slots,
-           io.cur);
+           hand, (DevObs *)nullptr, wpp ? 0 : 1, io.seq, io.done_host, io.hist, (const int *)nullptr,
+           io.slots, io.cur);
     HIPCHK(c, hipGetLastError());
     return HPE_OK;
 }
@@ -2213,6 +2253,27 @@ static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_stat
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
                dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals);
     return launch_pso_lanes(c, P, B, d_states, io);
+}
+
+int hpe_set_batch_form(hpe_ctx *c, int form) {
+    if (!c) return HPE_E_ARG;
+    if (form != HPE_BATCH_FORM_AUTO && form != HPE_BATCH_FORM_WAVE)
+        return fail(c, HPE_E_ARG, "batch form %d is neither HPE_BATCH_FORM_AUTO nor _WAVE", form);
+    // a live batch keeps the form it began with (every frame of a stream from one form, as in the
+    // single loop it is checked against)
+    if (c->live.cur >= 0 && form != c->batch_form)
+        return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the form it began with "
+                    "(end it first)");
+    c->batch_form = form;  // no epoch bump: the batch graphs are keyed by the form (GraphKey::wave)
+    return HPE_OK;
+}
+
+int hpe_batch_wave_wpp(hpe_ctx *c, int P, int B) {
+    if (!c) return HPE_E_ARG;
+    if (int rc = check_P(c, P)) return rc;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    return pso_wpp(c, B * P);
 }
 
 int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
@@ -2260,6 +2321,7 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
         GraphKey key = graph_key(P, G, refine, d_states, d_hist);  // the shape, not the slots
         key.k = k;
         key.B = B;
+        key.wave = batch_wave_wpp(c, P, B);
         for (int i = 0; i < k; ++i)
             if (c->slots[first_slots[0] + f0 + i].n_max > HPE_NT / 2) key.filt |= 1u << i;
         // k frames of B lanes, one after the other on the tracking stream: each lane on its own
@@ -2595,6 +2657,7 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
         key.parity = parity;
         key.tail_next = tail_next;
         key.B = B;
+        key.wave = batch_wave_wpp(c, P, B);
         key.to_cm = to_cm;
         key.downsample = 1;
         key.focal = focal;
@@ -2726,6 +2789,7 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     if (G < 0) return G;
     GraphKey key = graph_key(P, G, refine, d_states);  // the shape: never a host pointer
     key.B = B;
+    key.wave = batch_wave_wpp(c, P, B);
     key.cur = cur;
     key.next = next;
     key.to_cm = lv.to_cm;

@@ -42,6 +42,9 @@ def reference_bounds():
     return ub, lb, sd
 
 
+BATCH_FORMS = {"auto": _lib.BATCH_FORM_AUTO, "wave": _lib.BATCH_FORM_WAVE}
+
+
 def _check(lib, ctx, rc):
     if rc != 0:
         msg = lib.hpe_last_error(ctx).decode() if ctx else ""
@@ -219,6 +222,27 @@ class Context:
             B = len(fr)
         self.check(self.lib.hpe_track_batch_pipelined(self._h, int(num_p), int(refine), B,
                                                       C.c_void_p(d_states_ptr), arr))
+
+    def set_batch_form(self, form):
+        """The form of pso_evolve in track_batch, track_raw_batch and the live batch
+        (hpe_set_batch_form): "auto" / 0 (default: a workgroup per particle, num_p in the wave
+        form refused) or "wave" / 1 (every lane in the wave-per-particle form, at any num_p; lane
+        b is then the single-sequence call on a context created under HPE_PSO_FORM=wave and
+        HPE_PSO_WPP=batch_wave_wpp(num_p, B), bit for bit).  A live batch in progress keeps its
+        form: a different one raises (HPE_E_STATE)."""
+        if isinstance(form, str):
+            if form not in BATCH_FORMS:
+                raise ValueError(f"batch form {form!r} is not one of {sorted(BATCH_FORMS)}")
+            form = BATCH_FORMS[form]
+        self.check(self.lib.hpe_set_batch_form(self._h, int(form)))
+
+    def batch_wave_wpp(self, num_p, B) -> int:
+        """Waves per particle (1 or 2) of a wave-form batch of B lanes of num_p particles: the
+        forced HPE_PSO_WPP of the context, else 2 while B * num_p <= 1024 and 1 beyond."""
+        rc = self.lib.hpe_batch_wave_wpp(self._h, int(num_p), int(B))
+        if rc < 0:
+            self.check(rc)
+        return rc
 
     # ---- multi-GPU subswarms: the library's own per-frame exchange (hpe_subswarm_init)
     def subswarm_init(self, uid: bytes, nranks: int, rank: int):

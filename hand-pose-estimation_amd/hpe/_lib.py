@@ -18,6 +18,7 @@ PROF_PSO_GEN, PROF_REFINE, PROF_PSO_INIT, PROF_PSO_FINAL, PROF_PREP = 0, 1, 2, 3
 PROF_OPT_DESCENT, PROF_OPT_MOVE, PROF_SWARM_BEST, PROF_EXCHANGE = 5, 6, 7, 8
 SUBSWARM_ID_BYTES = 128
 BATCH_MAX = 16  # HPE_BATCH_MAX
+BATCH_FORM_AUTO, BATCH_FORM_WAVE = 0, 1  # HPE_BATCH_FORM_*
 HPE_OK, HPE_E_ARG, HPE_E_HIP, HPE_E_STATE, HPE_E_NOMEM, HPE_E_NODEVICE = 0, -1, -2, -3, -4, -5
 
 dp = C.POINTER(C.c_double)
@@ -65,7 +66,9 @@ SIGNATURES = {
                                            C.c_int, C.c_double]),
     "hpe_track_batch_pipelined": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.POINTER(C.c_void_p)]),
-    "hpe_build_spheres": (C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
+    "hpe_set_batch_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "hpe_batch_wave_wpp": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hpe_build_spheres":(C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),
     "hpe_eval_spheres": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, ip, dp]),

@@ -384,6 +384,34 @@ int hpe_batch_pipeline_begin(hpe_ctx *ctx, int B, const float *const *depth_mm,
 int hpe_track_batch_pipelined(hpe_ctx *ctx, int num_p, int refine, int B, double *d_states,
                               const float *const *next_depth_mm);
 
+/* The form of pso_evolve in the three batch calls above (hpe_track_batch_dev,
+ * hpe_track_raw_batch_dev, hpe_batch_pipeline_begin / hpe_track_batch_pipelined).
+ * HPE_BATCH_FORM_AUTO (default): as described there -- a workgroup per particle, and num_p in the
+ * wave form refused.  HPE_BATCH_FORM_WAVE: every lane's pso_evolve in the wave-per-particle form
+ * (k_pso_init_wb / k_pso_gen_wb on grid (workgroups of one lane, B), then the batch's final kernel
+ * evaluating cal_cost(bestp) itself), whatever num_p is -- 1024 and more included -- and whatever
+ * HPE_PSO_FORM says; the refine launches, the preparation and the hand-offs are the same, and so
+ * is every other refusal.  Waves per particle: hpe_batch_wave_wpp(ctx, num_p, B), the single
+ * call's rule applied to the LAUNCH's particle count -- the forced HPE_PSO_WPP if set at
+ * hpe_create, otherwise 2 while B * num_p <= 1024 and 1 beyond.  Lane b then computes, bit for
+ * bit, what the batch call's single-sequence counterpart (hpe_track_sequence_dev,
+ * hpe_track_raw_sequence_dev, hpe_pipeline_begin + hpe_track_pipelined) computes on a context
+ * created under HPE_PSO_FORM=wave and HPE_PSO_WPP=<that value> -- the yardstick; the two
+ * waves-per-particle forms are not bit-identical to each other, nor to the workgroup form.
+ * The batch graphs are keyed by the form and its waves per particle: switching back and forth
+ * replays, it captures nothing again.  Any other value of form: HPE_E_ARG.  A live batch keeps
+ * the form it began with: while one is in progress a different form is refused with HPE_E_STATE
+ * and nothing changes (setting the form it has is HPE_OK); end the batch first.
+ * When to set it: from two lanes up.  Measured on one MI355X at 256 particles per lane against
+ * the default form (DESIGN.md §4.7 "Wave-form lanes"): 1.12x the tracked frames at 2 lanes, 1.5x
+ * at 4, 2.0x at 8, 2.8x at 16 -- and 0.82x at one lane, which is better left on AUTO.
+ * hpe_batch_wave_wpp returns 1 or 2 whatever the current form is; num_p outside 1..8192 or B
+ * outside 1..HPE_BATCH_MAX: HPE_E_ARG. */
+#define HPE_BATCH_FORM_AUTO 0
+#define HPE_BATCH_FORM_WAVE 1
+int hpe_set_batch_form(hpe_ctx *ctx, int form);
+int hpe_batch_wave_wpp(hpe_ctx *ctx, int num_p, int B);
+
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through
  * hipExtLaunchKernel with a start/stop event pair (dispatch-packet timestamps: the

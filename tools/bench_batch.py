@@ -13,12 +13,17 @@ frame per lane and call from host memory (hpe_batch_pipeline_begin / hpe_track_b
 one graph per frame, the next frames read from pinned host buffers inside the refine launch);
 the check is then against the single pipelined loop (track_pipelined) alone.  --profile adds the mean device time of the
 refine, init, generation and final kernels of one more pass (HPE_PROF_*, direct launches).
-Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--profile] [--lanes 1,2,4,8,16]
-                                             [--frames 48] [--reps 3]
+--form wave (with any mode): the lanes' pso_evolve in the wave-per-particle form
+(hpe_set_batch_form); every line then carries the form and the waves per particle its launches
+used (hpe_batch_wave_wpp), and the check is against the single call on a second context created
+under HPE_PSO_FORM=wave and HPE_PSO_WPP=<the checked batch's>.
+Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
+                                             [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
 import ctypes as C
 import json
+import os
 import sys
 import time
 from pathlib import Path
@@ -58,13 +63,31 @@ def start_states(torch, x0, B):
     return torch.from_numpy(x).to("cuda:0")
 
 
-def check_against_alone(ctx, torch, x0, B, n_frames, n=6):
+def wave_yardstick_context(hpe, pso, wpp):
+    """A second context for the single calls a wave-form batch is checked against: the wave form
+    at the batch's waves per particle (both read from the environment at hpe_create)."""
+    saved = {k: os.environ.get(k) for k in ("HPE_PSO_FORM", "HPE_PSO_WPP")}
+    os.environ.update(HPE_PSO_FORM="wave", HPE_PSO_WPP=str(wpp))
+    try:
+        hand = hpe.reference_hand(device=0)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+    pso._push(hand.ctx)
+    return hand
+
+
+def check_against_alone(ctx, torch, x0, B, n_frames, n=6, alone=None):
     st = start_states(torch, x0, B)
     hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0")
     ctx.track_batch(P, 1, st.data_ptr(), [b * n_frames for b in range(B)], n, FPG, hist.data_ptr())
     ctx.check(ctx.lib.hpe_sync(ctx.h))
     s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
     h1 = torch.empty((n, 27), dtype=torch.float64, device="cuda:0")
+    ctx = alone or ctx
     for b in range(B):
         s1.copy_(start_states(torch, x0, 1)[0])
         ctx.track_sequence(P, 1, s1.data_ptr(), b * n_frames, n, FPG, h1.data_ptr())
@@ -74,7 +97,7 @@ def check_against_alone(ctx, torch, x0, B, n_frames, n=6):
             raise AssertionError(f"lane {b} of the batch differs from the lane tracked alone")
 
 
-def check_raw_against_alone(ctx, torch, x0, raws, n=6):
+def check_raw_against_alone(ctx, torch, x0, raws, n=6, alone=None):
     B = len(raws)
     st = start_states(torch, x0, B)
     hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0")
@@ -83,6 +106,7 @@ def check_raw_against_alone(ctx, torch, x0, raws, n=6):
     ctx.check(ctx.lib.hpe_sync(ctx.h))
     s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
     h1 = torch.empty((n, 27), dtype=torch.float64, device="cuda:0")
+    ctx = alone or ctx
     for b in range(B):
         s1.copy_(start_states(torch, x0, 1)[0])
         ctx.track_raw_sequence(P, 1, s1.data_ptr(), raws[b].data_ptr(), n, frames_per_graph=FPG,
@@ -108,7 +132,7 @@ def run_live(ctx, st, host, n):
                                   [fr[f + 1] for fr in host] if f + 1 < n else None)
 
 
-def check_live_against_alone(ctx, torch, x0, host, n=6):
+def check_live_against_alone(ctx, torch, x0, host, n=6, alone=None):
     B = len(host)
     st = start_states(torch, x0, B)
     hist = []
@@ -119,6 +143,7 @@ def check_live_against_alone(ctx, torch, x0, host, n=6):
         ctx.check(ctx.lib.hpe_sync(ctx.h))
         hist.append(st.cpu().numpy().copy())
     s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
+    ctx = alone or ctx
     for b in range(B):
         s1.copy_(start_states(torch, x0, 1)[0])
         ctx.pipeline_begin(host[b][0])
@@ -154,6 +179,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--raw", action="store_true")
     ap.add_argument("--live", action="store_true")
+    ap.add_argument("--form", choices=("auto", "wave"), default="auto")
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
     if a.raw and a.live:
@@ -169,15 +195,23 @@ def main():
     pso = hpe.PSO()
     pso.set_pso_params(ub, lb, sd, 0.7298, 1.49618, 1.49618, G + 1, 1e-8, 1e-8)
     pso._push(ctx)
+    ctx.set_batch_form(a.form)
+    nb = min(3, max(counts))  # lanes of the check
+    yard = wave_yardstick_context(hpe, pso, ctx.batch_wave_wpp(P, nb)) if a.form == "wave" else None
+    alone = yard.ctx if yard else None
     if a.live:
         host = make_host_lanes(ctx, max(counts), n)
-        check_live_against_alone(ctx, torch, hpe.X0, host[:min(3, max(counts))])
+        check_live_against_alone(ctx, torch, hpe.X0, host[:nb], alone=alone)
     elif a.raw:
         raws = make_raw_lanes(ctx, torch, max(counts), n)
-        check_raw_against_alone(ctx, torch, hpe.X0, raws[:min(3, max(counts))])
+        check_raw_against_alone(ctx, torch, hpe.X0, raws[:nb], alone=alone)
     else:
         make_lanes(ctx, max(counts), n)
-        check_against_alone(ctx, torch, hpe.X0, min(3, max(counts)), n)
+        if alone:
+            make_lanes(alone, nb, n)
+        check_against_alone(ctx, torch, hpe.X0, nb, n, alone=alone)
+    if alone:
+        alone.close()
     for B in counts:
         slots = [b * n for b in range(B)]
         if a.raw:
@@ -213,6 +247,9 @@ def main():
                             + ", one context, seeds 0..B-1"}
         if a.live:
             line["mode"] = "live"
+        if a.form == "wave":
+            line["form"] = "wave"
+            line["wpp"] = ctx.batch_wave_wpp(P, B)
         if a.profile:
             st.copy_(x0)
             torch.cuda.synchronize()
