@@ -1,6 +1,7 @@
 // hpe_api.inc -- host implementation of include/hpe.h (included at the end of
 // hpe_kernels.hip so the launches see the kernel templates).
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -114,13 +115,15 @@ struct GraphKey {
     unsigned staged, filt;
     int parity, tail_next, next, cur, B, to_cm, downsample;
     int wave;  // a batch in the wave form (hpe_set_batch_form): its waves per particle; else 0
+    int win;   // the lane windows' mode (hpe_set_batch_window): other kernels, one more launch
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
     bool operator==(const GraphKey &o) const {  // written out: the struct has padding
         return P == o.P && G == o.G && refine == o.refine && k == o.k && staged == o.staged &&
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
-               next == o.next && cur == o.cur && B == o.B && wave == o.wave && to_cm == o.to_cm &&
+               next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
+               to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -187,6 +190,10 @@ struct LaneFrameIo {
     const float *const *raw = nullptr;
     // the live batch: its final kernel bumps *seq and publishes it to the host word
     unsigned long long *seq = nullptr, *done_host = nullptr;
+    // lane windows (hpe_set_batch_window): the window table of the parity `prep` prepares into
+    // (null: no windows); follow: k_window_b rewrites it from the lanes' states first
+    DevWindow *win = nullptr;
+    bool follow = false;
 };
 
 }  // namespace
@@ -312,6 +319,21 @@ struct hpe_ctx {
         int B = 0, cur = -1, to_cm = 1;  // cur: the current frames' parity, -1: no batch
         double focal = 0;
     } live;
+    // lane windows (hpe_set_batch_window): the mode, and what the next raw batch call or live
+    // begin writes to the device -- init into both parities of the window table d_tab (next to
+    // rb.d_tab, allocated with it), the margins and the call's focal into d_par -- after the
+    // stream has drained.  Device memory, not the graphs, holds them: the graphs key the mode.
+    struct LaneWin {
+        int mode = HPE_WINDOW_OFF, B = 0;
+        double margin_xy = 0, margin_z = 0;
+        std::vector<DevWindow> init;
+        DevWindow *d_tab = nullptr;  // [2][HPE_BATCH_MAX]
+        WinPar *d_par = nullptr;
+        // hpe_window_from_pose's own pose, parameters and result
+        double *d_one_state = nullptr;
+        WinPar *d_one_par = nullptr;
+        DevWindow *d_one = nullptr;
+    } win;
     hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
     unsigned epoch = 1;  // bumped whenever a buffer a captured graph uses is reallocated
@@ -1118,6 +1140,11 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->rb.d_ctr);
     dfree(c->rb.d_raw);
     dfree(c->rb.d_cur);
+    dfree(c->win.d_tab);
+    dfree(c->win.d_par);
+    dfree(c->win.d_one_state);
+    dfree(c->win.d_one_par);
+    dfree(c->win.d_one);
     for (auto &par : c->live.h_raw)
         for (float *h : par)
             if (h) (void)hipHostFree(h);
@@ -2241,7 +2268,23 @@ static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_stat
     const DevObs *obs = io.obs;
     const DevHand *hand = c->d_hand;
     const dim3 prep_grid(1 + PREP_WG, B);
-    if (io.prep && io.raw)  // testmodel.cpp:126 + next_frame of the following iteration
+    if (io.prep && io.win) {
+        // the windowed forms; FOLLOW: first every lane's window from the pose its state holds
+        // now -- this launch's refine workgroup overwrites it -- into the parity being prepared
+        if (io.follow)
+            hipLaunchKernelGGL(k_window_b, dim3(B), dim3(64), 0, c->stream, (const double *)d_states,
+                               hand, (const WinPar *)c->win.d_par, io.win);
+        if (io.raw)
+            launch(c, HPE_PROF_REFINE,
+                   c->refine_exact ? k_refine_prep_wb<false> : k_refine_prep_wb<true>, prep_grid,
+                   dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep,
+                   io.raw, (const int *)io.cur, (const DevWindow *)io.win);
+        else
+            launch(c, HPE_PROF_REFINE,
+                   c->refine_exact ? k_refine_ring_wb<false> : k_refine_ring_wb<true>, prep_grid,
+                   dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep,
+                   (const DevWindow *)io.win);
+    } else if (io.prep && io.raw)  // testmodel.cpp:126 + next_frame of the following iteration
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_prep_b<false> : k_refine_prep_b<true>,
                prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals,
                refine ? 1 : 0, io.prep, io.raw, (const int *)io.cur);
@@ -2265,6 +2308,108 @@ int hpe_set_batch_form(hpe_ctx *c, int form) {
         return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the form it began with "
                     "(end it first)");
     c->batch_form = form;  // no epoch bump: the batch graphs are keyed by the form (GraphKey::wave)
+    return HPE_OK;
+}
+
+int hpe_set_batch_window(hpe_ctx *c, int mode, int B, const hpe_window *init, double margin_xy,
+                         double margin_z) {
+    if (!c) return HPE_E_ARG;
+    if (mode != HPE_WINDOW_OFF && mode != HPE_WINDOW_FIXED && mode != HPE_WINDOW_FOLLOW)
+        return fail(c, HPE_E_ARG, "window mode %d is none of HPE_WINDOW_OFF, _FIXED, _FOLLOW", mode);
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "windows for %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (mode != HPE_WINDOW_OFF && !init) return fail(c, HPE_E_ARG, "null init windows");
+    if (!(margin_xy >= 0) || !(margin_z >= 0) || std::isinf(margin_xy) || std::isinf(margin_z))
+        return fail(c, HPE_E_ARG, "margins %g, %g: negative or not finite", margin_xy, margin_z);
+    if (c->live.cur >= 0)
+        return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the windows it began "
+                    "with (end it first)");
+    hpe_ctx::LaneWin &w = c->win;
+    w.mode = mode;  // no epoch bump: the batch graphs are keyed by the mode (GraphKey::win)
+    w.B = B;
+    w.margin_xy = margin_xy;
+    w.margin_z = margin_z;
+    w.init.clear();
+    if (mode != HPE_WINDOW_OFF)
+        for (int b = 0; b < B; ++b)
+            w.init.push_back(DevWindow{init[b].row_lo, init[b].row_hi, init[b].col_lo,
+                                       init[b].col_hi, init[b].z_lo, init[b].z_hi, 0.f, 0.f, {0, 0}});
+    return HPE_OK;
+}
+
+// A batch call's or begin's lane count against the windows' (no windows: any).
+static int check_window_lanes(hpe_ctx *c, int B) {
+    if (c->win.mode != HPE_WINDOW_OFF && B != c->win.B)
+        return fail(c, HPE_E_ARG, "%d lanes, the windows were set for %d (hpe_set_batch_window)", B,
+                    c->win.B);
+    return HPE_OK;
+}
+
+// Frame 0 of a windowed batch: init into both parities of the window table, the margins and
+// the call's focal and unit conversion beside it; every entry with its depth bounds in raw units
+// (win_raw_bounds).  The stream drains first: launches in flight read the table, and under
+// FOLLOW they write it.  (ensure_raw_batch allocated the table.)
+static int write_windows(hpe_ctx *c, double focal, int to_cm) {
+    hpe_ctx::LaneWin &w = c->win;
+    if (w.mode == HPE_WINDOW_OFF) return HPE_OK;
+    DevWindow tab[2 * HPE_BATCH_MAX] = {};
+    for (int p = 0; p < 2; ++p)
+        for (int b = 0; b < w.B; ++b) {
+            DevWindow &e = tab[p * HPE_BATCH_MAX + b];
+            e = w.init[b];
+            win_raw_bounds(e, to_cm);
+        }
+    const WinPar par{w.margin_xy, w.margin_z, focal, to_cm, 0};
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(w.d_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(w.d_par, &par, sizeof(par), hipMemcpyHostToDevice));
+    return HPE_OK;
+}
+
+int hpe_window_from_pose(hpe_ctx *c, const double *theta, double focal, double margin_xy,
+                         double margin_z, hpe_window *out) {
+    if (!c) return HPE_E_ARG;
+    if (!theta || !out) return fail(c, HPE_E_ARG, "null pose or window");
+    if (!(focal > 0)) return fail(c, HPE_E_ARG, "focal %g is not positive", focal);
+    if (!(margin_xy >= 0) || !(margin_z >= 0) || std::isinf(margin_xy) || std::isinf(margin_z))
+        return fail(c, HPE_E_ARG, "margins %g, %g: negative or not finite", margin_xy, margin_z);
+    HIPCHK(c, hipSetDevice(c->device));
+    hpe_ctx::LaneWin &w = c->win;
+    if (!w.d_one) {
+        HIPCHK(c, dalloc(&w.d_one_state, (size_t)HPE_STATE_N));
+        HIPCHK(c, dalloc(&w.d_one_par, 1));
+        HIPCHK(c, dalloc(&w.d_one, 1));
+    }
+    const WinPar par{margin_xy, margin_z, focal, 1, 0};
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(w.d_one_state, theta, sizeof(double) * HPE_DOF, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(w.d_one_par, &par, sizeof(par), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_window_b, dim3(1), dim3(64), 0, c->stream, (const double *)w.d_one_state,
+                       (const DevHand *)c->d_hand, (const WinPar *)w.d_one_par, w.d_one);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    DevWindow r;
+    HIPCHK(c, hipMemcpy(&r, w.d_one, sizeof(r), hipMemcpyDeviceToHost));
+    *out = hpe_window{r.row_lo, r.row_hi, r.col_lo, r.col_hi, r.z_lo, r.z_hi};
+    return HPE_OK;
+}
+
+int hpe_batch_windows_readback(hpe_ctx *c, int parity, int B, hpe_window *out) {
+    if (!c) return HPE_E_ARG;
+    if (parity < 0 || parity > 1) return fail(c, HPE_E_ARG, "buffer parity %d", parity);
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "windows of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!out) return fail(c, HPE_E_ARG, "null windows");
+    if (!c->win.d_tab)
+        return fail(c, HPE_E_STATE, "no window table: no raw or live batch has run yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    DevWindow tab[HPE_BATCH_MAX];
+    HIPCHK(c, hipMemcpy(tab, c->win.d_tab + parity * HPE_BATCH_MAX, sizeof(DevWindow) * B,
+                        hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b)
+        out[b] = hpe_window{tab[b].row_lo, tab[b].row_hi, tab[b].col_lo, tab[b].col_hi, tab[b].z_lo,
+                            tab[b].z_hi};
     return HPE_OK;
 }
 
@@ -2557,6 +2702,15 @@ static int ensure_raw_batch(hpe_ctx *c, int B, int to_cm, double focal) {
         HIPCHK(c, hipMemset(rb.d_ctr, 0, sizeof(unsigned) * 32 * M));
         HIPCHK(c, dalloc(&rb.d_raw, M));
         HIPCHK(c, dalloc(&rb.d_cur, 2 * M));
+        // the lane windows' table, by [parity][lane] like d_tab, and their parameters; until a
+        // windowed call writes them, whole-frame windows
+        HIPCHK(c, dalloc(&c->win.d_tab, 2 * M));
+        HIPCHK(c, dalloc(&c->win.d_par, 1));
+        std::vector<DevWindow> whole(2 * M, DevWindow{0, HPE_IMG_H - 1, 0, HPE_IMG_W - 1, -HUGE_VAL,
+                                                      HUGE_VAL, -HUGE_VALF, HUGE_VALF, {0, 0}});
+        HIPCHK(c, hipMemcpy(c->win.d_tab, whole.data(), sizeof(DevWindow) * whole.size(),
+                            hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemset(c->win.d_par, 0, sizeof(WinPar)));
     }
     if (B <= rb.lanes && to_cm == rb.to_cm && focal == rb.focal) return HPE_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2615,6 +2769,8 @@ static int enqueue_raw_batch_chunk(hpe_ctx *c, int P, int refine, int B, double 
         LaneFrameIo io{rb.d_obs + cur * HPE_BATCH_MAX, false, hist, nullptr, rb.d_cur};
         if (i + 1 < k || tail_next) io.prep = rb.d_tab + nxt * HPE_BATCH_MAX;
         io.raw = rb.d_raw;
+        if (c->win.mode != HPE_WINDOW_OFF) io.win = c->win.d_tab + nxt * HPE_BATCH_MAX;
+        io.follow = c->win.mode == HPE_WINDOW_FOLLOW;
         if (int rc = track_lane_frame(c, P, refine, B, d_states, io)) return rc;
     }
     return HPE_OK;
@@ -2634,20 +2790,27 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
     if (!downsample)
         return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
                     "the single-workgroup refine (<= %d)", HPE_IMG_H * HPE_IMG_W, RF_STAGE_MAX);
+    if ((rc = check_window_lanes(c, B))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     to_cm = to_cm ? 1 : 0;
     if ((rc = ensure_raw_batch(c, B, to_cm, focal))) return rc;
     const int G = ensure_tracking(c, P, B);
     if (G < 0) return G;
     c->live.cur = -1;  // a live batch in progress (the same lane buffers) ends here
+    if ((rc = write_windows(c, focal, to_cm))) return rc;
     hpe_ctx::RawBatch &rb = c->rb;
     // the lanes' raw bases and cursors, then frame 0 of every lane into buffer parity 0
     BatchRaw first{};
     for (int b = 0; b < B; ++b) first.raw[b] = d_raw_mm[b];
     hipLaunchKernelGGL(k_raw_begin_b, dim3(1, B), dim3(64), 0, c->stream, first, n, rb.d_raw, rb.d_cur);
-    hipLaunchKernelGGL(k_prepare_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                       (const PrepArgs *)rb.d_tab, (const float *const *)rb.d_raw,
-                       (const int *)rb.d_cur);
+    if (c->win.mode != HPE_WINDOW_OFF)
+        hipLaunchKernelGGL(k_prepare_wb, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                           (const PrepArgs *)rb.d_tab, (const float *const *)rb.d_raw,
+                           (const int *)rb.d_cur, (const DevWindow *)c->win.d_tab);
+    else
+        hipLaunchKernelGGL(k_prepare_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                           (const PrepArgs *)rb.d_tab, (const float *const *)rb.d_raw,
+                           (const int *)rb.d_cur);
     HIPCHK(c, hipGetLastError());
     const int K = frames_per_graph ? frames_per_graph : HPE_SEQ_CHUNK;
     for (int f0 = 0; f0 < n; f0 += K) {
@@ -2658,6 +2821,7 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
         key.tail_next = tail_next;
         key.B = B;
         key.wave = batch_wave_wpp(c, P, B);
+        key.win = c->win.mode;
         key.to_cm = to_cm;
         key.downsample = 1;
         key.focal = focal;
@@ -2731,6 +2895,7 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
         if (u[0] == '1')
             return fail(c, HPE_E_STATE, "HPE_PIPE_UPLOAD=1: the upload form is not built for lanes "
                         "(a live batch reads its pinned buffers in place)");
+    if (int wrc = check_window_lanes(c, B)) return wrc;
     HIPCHK(c, hipSetDevice(c->device));
     // the frames of a batch in progress are done with: its pinned buffers are free to refill
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2739,6 +2904,7 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     to_cm = to_cm ? 1 : 0;
     int rc = ensure_batch_lanes(c);
     if (rc || (rc = ensure_raw_batch(c, B, to_cm, focal)) || (rc = ensure_live_batch(c, B))) return rc;
+    if ((rc = write_windows(c, focal, to_cm))) return rc;
     HIPCHK(c, hipMemsetAsync(lv.d_seq, 0, sizeof(unsigned long long), c->stream));
     __atomic_store_n(lv.h_done, 0ull, __ATOMIC_RELEASE);
     lv.enq = 0;
@@ -2746,8 +2912,12 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     // frame 0 of every lane: into its pinned buffer of parity 0, prepared from there
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
     for (int b = 0; b < B; ++b) std::memcpy(lv.h_raw[0][b], depth_mm[b], sizeof(float) * npix);
-    hipLaunchKernelGGL(k_prepare_ring_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                       (const PrepArgs *)lv.d_tab);
+    if (c->win.mode != HPE_WINDOW_OFF)
+        hipLaunchKernelGGL(k_prepare_ring_wb, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                           (const PrepArgs *)lv.d_tab, (const DevWindow *)c->win.d_tab);
+    else
+        hipLaunchKernelGGL(k_prepare_ring_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                           (const PrepArgs *)lv.d_tab);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     lv.B = B;
@@ -2790,6 +2960,7 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     GraphKey key = graph_key(P, G, refine, d_states);  // the shape: never a host pointer
     key.B = B;
     key.wave = batch_wave_wpp(c, P, B);
+    key.win = c->win.mode;  // the begin's: it cannot change while the batch lives
     key.cur = cur;
     key.next = next;
     key.to_cm = lv.to_cm;
@@ -2800,6 +2971,8 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     // launch that publishes the batch's frame number
     LaneFrameIo io{c->rb.d_obs + cur * HPE_BATCH_MAX, false, nullptr, nullptr, nullptr};
     if (next) io.prep = lv.d_tab + nxt * HPE_BATCH_MAX;
+    if (c->win.mode != HPE_WINDOW_OFF) io.win = c->win.d_tab + nxt * HPE_BATCH_MAX;
+    io.follow = c->win.mode == HPE_WINDOW_FOLLOW;
     io.seq = lv.d_seq;
     io.done_host = lv.h_done_dev;
     if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_LIVE_BATCH], key,

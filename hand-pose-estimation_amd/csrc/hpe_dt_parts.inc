@@ -3,7 +3,8 @@
 // prep_dt_split), so all compile the same statements.  DT_PART selects the piece; names expected
 // in scope: W, H, msk, t, l and
 //   0  mask + first hand row: DT_RAW (the raw frame), optionally DT_HINT (word the band
-//      workgroups wait for); defines r0.  Every wave of the workgroup; two barriers.
+//      workgroups wait for) and DT_WIN(pix, v) (the raw value v of pixel pix as the lane's
+//      window leaves it); defines r0.  Every wave of the workgroup; two barriers.
 //   1  forward scan by one wave: r0, DT_FWD (the forward values, written)
 //   2  backward scan by one wave: r0, DT_FWD (read), DT_OUT (the float transform); defines mx,
 //      the wave's largest distance
@@ -21,8 +22,12 @@
     auto fold = [&](const float (&v)[B], int k0) {
 #pragma unroll
         for (int q = 0; q < B; ++q) {
-            const unsigned long long bm = __ballot(v[q] != 0.f);
             const int pix = (k0 + q) * PREP_NT + t;
+#ifdef DT_WIN
+            const unsigned long long bm = __ballot(DT_WIN(pix, v[q]) != 0.f);
+#else
+            const unsigned long long bm = __ballot(v[q] != 0.f);
+#endif
             if ((l & 31) == 0) msk[pix >> 5] = (unsigned)(bm >> (l & 32));
         }
     };

@@ -1164,6 +1164,8 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
                                                   int32_t *__restrict__ match_g,
                                                   int *__restrict__ evals_out, int do_refine,
                                                   PrepArgs pa, DevMw mw, DevPick pk, PrepSplit ps) {
+    constexpr bool WIN = false;
+    const DevWindow pw{};
 #include "hpe_refine_body.inc"
 }
 
@@ -1250,6 +1252,8 @@ __global__ __launch_bounds__(RF_NT) void k_refine_b(double *__restrict__ states,
     const DevMw mw{};
     const DevPick pk{};
     const PrepSplit ps{};
+    constexpr bool WIN = false;
+    const DevWindow pw{};
 #include "hpe_refine_body.inc"
 }
 
@@ -1332,6 +1336,8 @@ __global__ __launch_bounds__(RF_NT) void k_refine_prep_b(double *__restrict__ st
     const DevMw mw{};
     const DevPick pk{};
     const PrepSplit ps{};
+    constexpr bool WIN = false;
+    const DevWindow pw{};
 #include "hpe_refine_body.inc"
 }
 static_assert(PREP_NT == RF_NT, "the preparation workgroups ride in the refine launch");
@@ -1367,6 +1373,8 @@ __global__ __launch_bounds__(RF_NT) void k_refine_ring_b(double *__restrict__ st
     const DevMw mw{};
     const DevPick pk{};
     const PrepSplit ps{};
+    constexpr bool WIN = false;
+    const DevWindow pw{};
 #include "hpe_refine_body.inc"
 }
 
@@ -1394,6 +1402,145 @@ __global__ __launch_bounds__(HPE_NT) void k_pso_final_live_b(DevSwarm sw, size_t
     int *__restrict__ const seq_cur = cur ? cur + 2 * blockIdx.y : nullptr;
     unsigned long long *__restrict__ const seq_dev = blockIdx.y == 0 ? seq_b : nullptr;
 #include "hpe_final_body.inc"
+}
+
+// ------------------------------------------------------------------ lane windows
+// hpe_set_batch_window: the four lane preparation kernels above with every lane's frame read
+// through its window -- wtab + parity * HPE_BATCH_MAX, the DevWindow table next to the PrepArgs
+// table, entry blockIdx.y -- in the band workgroups and in the distance transform's mask alike
+// (prep_workgroup<true>): the preparation of the frame masked on the host.  The window is one
+// more independent load of the preparation workgroups; the refine workgroup (0, b) reads what
+// it reads in the kernel it mirrors.
+__global__ __launch_bounds__(PREP_NT) void k_prepare_wb(const PrepArgs *__restrict__ tab,
+                                                        const float *const *__restrict__ raw_base,
+                                                        const int *__restrict__ cur,
+                                                        const DevWindow *__restrict__ wtab) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    const DevWindow pw = wtab[blockIdx.y];
+    prep_workgroup<true>(lane_prep(tab, raw_base, cur, 0), blockIdx.x, lds, nullptr, &pw);
+}
+
+__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_wb(const PrepArgs *__restrict__ tab,
+                                                             const DevWindow *__restrict__ wtab) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    const DevWindow pw = wtab[blockIdx.y];
+    prep_workgroup<true>(tab[blockIdx.y], blockIdx.x, lds, nullptr, &pw);
+}
+
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_prep_wb(double *__restrict__ states,
+                                                          const DevObs *__restrict__ obs,
+                                                          const DevHand *__restrict__ Hg,
+                                                          int *__restrict__ evals_b, int do_refine,
+                                                          const PrepArgs *__restrict__ tab,
+                                                          const float *const *__restrict__ raw_base,
+                                                          const int *__restrict__ cur,
+                                                          const DevWindow *__restrict__ wtab) {
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    PrepArgs pa{};
+    DevWindow pw{};
+    if (blockIdx.x >= 1) {
+        pa = lane_prep(tab, raw_base, cur, 1);
+        pw = wtab[blockIdx.y];
+    }
+    const DevMw mw{};
+    const DevPick pk{};
+    const PrepSplit ps{};
+    constexpr bool WIN = true;
+#include "hpe_refine_body.inc"
+}
+
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_ring_wb(double *__restrict__ states,
+                                                          const DevObs *__restrict__ obs,
+                                                          const DevHand *__restrict__ Hg,
+                                                          int *__restrict__ evals_b, int do_refine,
+                                                          const PrepArgs *__restrict__ tab,
+                                                          const DevWindow *__restrict__ wtab) {
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    PrepArgs pa{};
+    DevWindow pw{};
+    if (blockIdx.x >= 1) {
+        pa = tab[blockIdx.y];
+        pw = wtab[blockIdx.y];
+    }
+    const DevMw mw{};
+    const DevPick pk{};
+    const PrepSplit ps{};
+    constexpr bool WIN = true;
+#include "hpe_refine_body.inc"
+}
+
+// The pose rule (include/hpe.h): the window of the context hand at pose th[0..25], by one wave.
+// FK is fk_wave, as k_build runs it, so the centres are hpe_build_spheres' bit for bit; lane
+// j < 48 takes sphere j in camera coordinates (y and z un-negated), every product rounded
+// before its add, and the wave takes minima and maxima, which are order-free.  Any non-finite
+// coordinate or z <= 0: the whole frame.  Lane 0 adds the depth bounds in raw units
+// (win_raw_bounds) and stores the window (plain vector stores).
+struct WinPar {
+    double margin_xy, margin_z, focal;
+    int to_cm, pad;  // the frames' unit conversion: the window's depth bounds in raw units
+};
+__device__ __forceinline__ double wave_min_f64(double v) {
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ void window_wave(FkSm &f, const DevHand *__restrict__ H,
+                                            const WinPar &par, DevWindow *__restrict__ out) {
+    const int l = threadIdx.x & 63;
+    fk_wave(f, H);
+    const int j = l < HPE_NS ? l : HPE_NS - 1;  // lanes >= 48 repeat sphere 47: no effect on min / max
+    const double x = f.S[j][0], y = f.S[j][1] * -1, z = f.S[j][2] * -1, R = H->radii[j];
+    const bool ok = isfinite(x) && isfinite(y) && isfinite(z) && z > 0;
+    const bool open = __ballot(!ok) != 0ull;
+    const double e = R + par.margin_xy, ez = R + par.margin_z;
+    const double cl = floor((par.focal * (x - e) + 160.0 * z) / z);
+    const double ch = floor((par.focal * (x + e) + 160.0 * z) / z);
+    const double rl = floor((par.focal * (y - e) + 120.0 * z) / z);
+    const double rh = floor((par.focal * (y + e) + 120.0 * z) / z);
+    const double cmin = wave_min_f64(cl), cmax = wave_max_f64(ch);
+    const double rmin = wave_min_f64(rl), rmax = wave_max_f64(rh);
+    const double zmin = wave_min_f64(z - ez), zmax = wave_max_f64(z + ez);
+    if (l == 0) {
+        DevWindow w{};
+        w.row_lo = open ? 0 : (int)fmin(fmax(rmin, 0.0), (double)HPE_IMG_H);
+        w.row_hi = open ? HPE_IMG_H - 1 : (int)fmin(fmax(rmax, -1.0), (double)(HPE_IMG_H - 1));
+        w.col_lo = open ? 0 : (int)fmin(fmax(cmin, 0.0), (double)HPE_IMG_W);
+        w.col_hi = open ? HPE_IMG_W - 1 : (int)fmin(fmax(cmax, -1.0), (double)(HPE_IMG_W - 1));
+        w.z_lo = open ? -__builtin_inf() : zmin;
+        w.z_hi = open ? __builtin_inf() : zmax;
+        win_raw_bounds(w, par.to_cm);
+        *out = w;
+    }
+}
+
+// HPE_WINDOW_FOLLOW: lane blockIdx.x's window from the pose its state holds now, into entry
+// blockIdx.x of wout (the table of the parity the NEXT refine launch prepares into).  One wave
+// per lane, a launch of its own before that refine launch: its refine workgroup overwrites the
+// state at its end, so the preparation workgroups riding in it cannot read the pose themselves;
+// the hand-off is the kernel boundary.  hpe_window_from_pose runs it on one pose.
+__global__ __launch_bounds__(64) void k_window_b(const double *__restrict__ states,
+                                                 const DevHand *__restrict__ Hg,
+                                                 const WinPar *__restrict__ par,
+                                                 DevWindow *__restrict__ wout) {
+    __shared__ DevHand hs;
+    __shared__ FkSm fk;
+    const int l = threadIdx.x;
+    for (int q = l; q < (int)(sizeof(DevHand) / 8); q += 64) ((double *)&hs)[q] = gp((const double *)Hg)[q];
+    if (l < HPE_DOF) fk.th[l] = states[(size_t)HPE_STATE_N * blockIdx.x + l];
+    const WinPar p = *par;
+    __syncthreads();
+    window_wave(fk, &hs, p, wout + blockIdx.x);
 }
 
 // ------------------------------------------------------------------ wave-form lanes

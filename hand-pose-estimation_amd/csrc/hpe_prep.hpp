@@ -66,6 +66,58 @@ struct PrepSplit {
     int *seq_n;         // frames in the sequence (the call's prologue stores it)
 };
 
+// A lane's window (hpe_window, include/hpe.h: every bound inclusive) as the device table holds
+// it, and the masking rule of the windowed preparation: pixel `pix` with raw value rv is kept iff
+// its row, its column and its converted depth Z = to_cm ? (double)rv / 10. : (double)rv --
+// prep_band's own expression -- lie inside; every other pixel reads as 0.0f.  Z is monotone in
+// rv, so z_lo <= Z <= z_hi is raw_lo <= rv <= raw_hi for the smallest / largest float whose Z
+// passes (win_raw_bounds, computed once when the entry is written, by the host or k_window_b):
+// the same pixels exactly, without a fp64 division per pixel.  A select on a value already
+// loaded: no load becomes conditional.  lo > hi or a NaN bound keeps nothing.
+struct DevWindow {
+    int row_lo, row_hi, col_lo, col_hi;
+    double z_lo, z_hi;
+    float raw_lo, raw_hi;  // z_lo, z_hi in the raw frame's unit (NaN: keeps nothing)
+    int pad[2];
+};
+static_assert(sizeof(DevWindow) == 48, "a 16-byte multiple");
+__host__ __device__ inline double win_depth(int to_cm, float rv) {
+    return to_cm ? (double)rv / 10. : (double)rv;
+}
+// raw_lo = the smallest float f with win_depth(f) >= z_lo, raw_hi = the largest with
+// win_depth(f) <= z_hi: the float nearest the bound in raw units, walked to the exact threshold
+// (a step or two: the conversion is monotone, and -inf / +inf are floats like the others).
+__host__ __device__ inline void win_raw_bounds(DevWindow &w, int to_cm) {
+    const float inf = __builtin_inff();
+    float lo = __builtin_nanf(""), hi = __builtin_nanf("");
+    if (w.z_lo == w.z_lo) {
+        lo = (float)(to_cm ? w.z_lo * 10.0 : w.z_lo);
+        for (int k = 0; k < 8; ++k) {
+            const float p = nextafterf(lo, -inf);
+            if (p == lo || !(win_depth(to_cm, p) >= w.z_lo)) break;
+            lo = p;
+        }
+        for (int k = 0; k < 8 && !(win_depth(to_cm, lo) >= w.z_lo); ++k) lo = nextafterf(lo, inf);
+    }
+    if (w.z_hi == w.z_hi) {
+        hi = (float)(to_cm ? w.z_hi * 10.0 : w.z_hi);
+        for (int k = 0; k < 8; ++k) {
+            const float n = nextafterf(hi, inf);
+            if (n == hi || !(win_depth(to_cm, n) <= w.z_hi)) break;
+            hi = n;
+        }
+        for (int k = 0; k < 8 && !(win_depth(to_cm, hi) <= w.z_hi); ++k) hi = nextafterf(hi, -inf);
+    }
+    w.raw_lo = lo;
+    w.raw_hi = hi;
+}
+__device__ __forceinline__ float win_raw(const DevWindow &w, int pix, float rv) {
+    const int r = pix / HPE_IMG_W, c = pix - HPE_IMG_W * r;
+    const bool keep = r >= w.row_lo && r <= w.row_hi && c >= w.col_lo && c <= w.col_hi &&
+                      rv >= w.raw_lo && rv <= w.raw_hi;
+    return keep ? rv : 0.0f;
+}
+
 // LDS layout: chunk[PREP_CH] doubles | acc1, flag (64 B) | wcnt, hcnt | mask bits | wmax
 constexpr int prep_lds_bytes() {
     return PREP_CH * 8 + 64 + 2 * (PREP_NT / 64) * 4 + HPE_IMG_W * HPE_IMG_H / 32 * 4 + 64;
@@ -151,8 +203,11 @@ __device__ __forceinline__ bool arrive_last_sharded(unsigned *ctr, unsigned part
     return __builtin_amdgcn_readfirstlane(*flag) != 0;  // decides exits and barriers (§7)
 }
 
-// ---- band workgroup b: rows [30b, 30b + 30)
-__device__ __forceinline__ void prep_band(const PrepArgs &a, int b, unsigned char *lds) {
+// ---- band workgroup b: rows [30b, 30b + 30).  WIN: the raw values pass the lane's window *wn
+// first (the batch calls' windowed kernels); the other forms compile as before.
+template <bool WIN = false>
+__device__ __forceinline__ void prep_band(const PrepArgs &a, int b, unsigned char *lds,
+                                          const DevWindow *wn = nullptr) {
     constexpr int W = HPE_IMG_W, NWV = PREP_NT / 64;
     int *wcnt = (int *)(lds + PREP_CH * 8 + 64), *hcnt = wcnt + NWV;
     const int t = threadIdx.x, w = t >> 6, l = t & 63;
@@ -179,7 +234,7 @@ __device__ __forceinline__ void prep_band(const PrepArgs &a, int b, unsigned cha
         const int p0 = k * PREP_NT;
         const int q = p0 + t, pix = pbase + q;
         const bool in = q < PREP_BAND_PIX;
-        const float rv = rvs[k];
+        const float rv = WIN ? win_raw(*wn, pix, rvs[k]) : rvs[k];
         const double Z = a.to_cm ? (double)rv / 10. : (double)rv;
         if (in) a.depth_cm[pix] = Z;
         const bool nz = in && Z != 0;
@@ -304,8 +359,11 @@ __device__ __forceinline__ void prep_merge(const PrepArgs &a, unsigned char *lds
     }
 }
 
-// ---- DT workgroup: mask bits by all waves, the raster scans by wave 0
-__device__ __forceinline__ void prep_dt(const PrepArgs &a, unsigned char *lds) {
+// ---- DT workgroup: mask bits by all waves, the raster scans by wave 0.  WIN: the mask is of
+// the raw values behind the lane's window *wn, the ones the bands read.
+template <bool WIN = false>
+__device__ __forceinline__ void prep_dt(const PrepArgs &a, unsigned char *lds,
+                                        const DevWindow *wn = nullptr) {
     constexpr int W = HPE_IMG_W, H = HPE_IMG_H;
     unsigned *msk = (unsigned *)(lds + PREP_CH * 8 + 64 + 2 * (PREP_NT / 64) * 4);
     float *wmaxp = (float *)(msk + W * H / 32);
@@ -314,6 +372,7 @@ __device__ __forceinline__ void prep_dt(const PrepArgs &a, unsigned char *lds) {
 #define DT_HINT &a.ctr[2]
 #define DT_FWD a.dtf
 #define DT_OUT a.dt
+#define DT_WIN(pix, v) (WIN ? win_raw(*wn, pix, v) : (v))
 #define DT_PART 0
 #include "hpe_dt_parts.inc"
     if (t < 64) {
@@ -332,6 +391,7 @@ __device__ __forceinline__ void prep_dt(const PrepArgs &a, unsigned char *lds) {
 #undef DT_HINT
 #undef DT_FWD
 #undef DT_OUT
+#undef DT_WIN
 
 // ---- the transform split over two launches (resident raw sequences).  The
 // backward scan starts where the forward scan ends, so one frame's transform cannot be
@@ -424,19 +484,23 @@ __device__ __forceinline__ void prep_write_descriptor(const PrepArgs &a) {
 
 // One preparing workgroup (index g in [0, PREP_WG)); the last to finish writes the
 // descriptor.  With a split (ps and ps->dtf_next) the DT workgroup runs prep_dt_split.
+// WIN: the bands and the transform's mask both read the frame through the window *wn (the
+// split transform has no windowed form: the batch calls, which alone have windows, never split).
+template <bool WIN = false>
 __device__ __forceinline__ void prep_workgroup(const PrepArgs &a0, int g, unsigned char *lds,
-                                               const PrepSplit *ps = nullptr) {
+                                               const PrepSplit *ps = nullptr,
+                                               const DevWindow *wn = nullptr) {
     int *flag = (int *)(lds + PREP_CH * 8 + 8);
     PrepArgs a = a0;
     if (a0.raw_row) a.raw = a0.raw + (size_t)(*a0.raw_row + 1) * a0.raw_stride;
     if (g < PREP_BANDS) {
-        prep_band(a, g, lds);
+        prep_band<WIN>(a, g, lds, wn);
         if (!prep_arrive_last(a.ctr, PREP_BANDS, flag)) return;
         prep_merge(a, lds);
-    } else if (ps && ps->dtf_next) {
+    } else if (!WIN && ps && ps->dtf_next) {
         prep_dt_split(a, *ps, lds);
     } else {
-        prep_dt(a, lds);
+        prep_dt<WIN>(a, lds, wn);
     }
     if (prep_arrive_last(a.ctr + 1, 2, flag) && threadIdx.x == 0) {
         prep_write_descriptor(a);

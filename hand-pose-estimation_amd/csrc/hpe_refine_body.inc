@@ -1,7 +1,9 @@
 // hpe_refine_body.inc -- the body of k_refine, included as text by k_refine and by its batched
 // form k_refine_b (hpe_kernels.hip), so both compile the same statements.  Names it expects in
 // scope: STAGED, MW, RIGID (compile-time), x0g, og, Hg, match_g, evals_out, do_refine, pa, mw,
-// pk, ps (k_refine's parameters).
+// pk, ps (k_refine's parameters), and WIN (compile-time) with pw, the window the preparation
+// workgroups read the next frame through (the batch calls' windowed kernels; elsewhere false
+// and an unread DevWindow).
     extern __shared__ __align__(16) unsigned char dyn[];  // staged cloud + matchId / prep
     const int nhelp = MW ? mw.Q : 0;
     if (MW && blockIdx.x >= 1 && (int)blockIdx.x <= nhelp) {
@@ -10,7 +12,7 @@
     }
     if (blockIdx.x >= 1) {
         const unsigned long long t0 = HPE_STAMPS ? __builtin_amdgcn_s_memtime() : 0;
-        prep_workgroup(pa, blockIdx.x - 1 - nhelp, dyn, &ps);
+        prep_workgroup<WIN>(pa, blockIdx.x - 1 - nhelp, dyn, &ps, &pw);
         if (HPE_STAMPS && threadIdx.x == 0) {  // diagnostic build: prep workgroup spans
             const int k = ((int)blockIdx.x - 1 - nhelp < PREP_BANDS) ? 24 : 25;
             atomicAdd(&hpe_stamps[k], __builtin_amdgcn_s_memtime() - t0);

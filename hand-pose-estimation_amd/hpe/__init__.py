@@ -14,7 +14,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _lib
+from . import _lib, window
 from ._lib import HpeError, ptr
 
 __all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "HpeError",
@@ -43,6 +43,7 @@ def reference_bounds():
 
 
 BATCH_FORMS = {"auto": _lib.BATCH_FORM_AUTO, "wave": _lib.BATCH_FORM_WAVE}
+WINDOW_MODES = {"off": _lib.WINDOW_OFF, "fixed": _lib.WINDOW_FIXED, "follow": _lib.WINDOW_FOLLOW}
 
 
 def _check(lib, ctx, rc):
@@ -235,6 +236,43 @@ class Context:
                 raise ValueError(f"batch form {form!r} is not one of {sorted(BATCH_FORMS)}")
             form = BATCH_FORMS[form]
         self.check(self.lib.hpe_set_batch_form(self._h, int(form)))
+
+    def set_batch_window(self, mode, init=None, margin_xy=0.0, margin_z=0.0):
+        """Segment every lane's depth by a window (hpe_set_batch_window) in track_raw_batch and
+        the live batch, from the next call or begin on: "off" / 0 (default), "fixed" / 1 (lane
+        b's every frame masked by init[b]) or "follow" / 2 (frame 0 by init[b], later frames by
+        the pose rule on the lane's own tracked pose, hpe.window.from_spheres, with the two
+        margins).  init: one window per lane (hpe.window.Window, any 6-sequence or
+        hpe._lib.Window); the batch calls then take exactly len(init) lanes.  A live batch in
+        progress keeps what it began with: the call raises (HPE_E_STATE)."""
+        if isinstance(mode, str):
+            if mode not in WINDOW_MODES:
+                raise ValueError(f"window mode {mode!r} is not one of {sorted(WINDOW_MODES)}")
+            mode = WINDOW_MODES[mode]
+        if init is None:
+            B, arr = 1, None
+        else:
+            ws = [window.as_window(w) for w in init]
+            B = len(ws)
+            arr = (_lib.Window * max(B, 1))(*[_lib.Window(*w) for w in ws])
+        self.check(self.lib.hpe_set_batch_window(self._h, int(mode), B, arr, float(margin_xy),
+                                                 float(margin_z)))
+
+    def window_from_pose(self, theta, focal=241.42, margin_xy=0.0, margin_z=0.0):
+        """The pose rule on the device (hpe_window_from_pose): the window of the context hand at
+        pose theta, as FOLLOW computes it.  Synchronises."""
+        th = _lib.as_f64(theta, (26,))
+        w = _lib.Window()
+        self.check(self.lib.hpe_window_from_pose(self._h, ptr(th, C.c_double), float(focal),
+                                                 float(margin_xy), float(margin_z), C.byref(w)))
+        return window.as_window(w)
+
+    def batch_windows_readback(self, parity, B):
+        """The B lane windows of one buffer parity (frame f of a call is prepared into parity
+        f & 1), as a list of hpe.window.Window.  Synchronises."""
+        arr = (_lib.Window * max(int(B), 1))()
+        self.check(self.lib.hpe_batch_windows_readback(self._h, int(parity), int(B), arr))
+        return [window.as_window(arr[b]) for b in range(int(B))]
 
     def batch_wave_wpp(self, num_p, B) -> int:
         """Waves per particle (1 or 2) of a wave-form batch of B lanes of num_p particles: the

@@ -19,6 +19,7 @@ PROF_OPT_DESCENT, PROF_OPT_MOVE, PROF_SWARM_BEST, PROF_EXCHANGE = 5, 6, 7, 8
 SUBSWARM_ID_BYTES = 128
 BATCH_MAX = 16  # HPE_BATCH_MAX
 BATCH_FORM_AUTO, BATCH_FORM_WAVE = 0, 1  # HPE_BATCH_FORM_*
+WINDOW_OFF, WINDOW_FIXED, WINDOW_FOLLOW = 0, 1, 2  # HPE_WINDOW_*
 HPE_OK, HPE_E_ARG, HPE_E_HIP, HPE_E_STATE, HPE_E_NOMEM, HPE_E_NODEVICE = 0, -1, -2, -3, -4, -5
 
 dp = C.POINTER(C.c_double)
@@ -35,6 +36,12 @@ class HandParams(C.Structure):
 class Frame(C.Structure):
     _fields_ = [("depth_cm", dp), ("dt", fp), ("cloud", dp), ("n", C.c_int32),
                 ("scale", C.c_double), ("dtmax", C.c_double), ("K", C.c_double * 9)]
+
+
+class Window(C.Structure):
+    """hpe_window: 32 bytes, every bound inclusive."""
+    _fields_ = [("row_lo", C.c_int32), ("row_hi", C.c_int32), ("col_lo", C.c_int32),
+                ("col_hi", C.c_int32), ("z_lo", C.c_double), ("z_hi", C.c_double)]
 
 
 # name -> (restype, argtypes); the list IS the exported C ABI (tests check it against
@@ -68,6 +75,11 @@ SIGNATURES = {
                                             C.POINTER(C.c_void_p)]),
     "hpe_set_batch_form": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_batch_wave_wpp": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hpe_set_batch_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Window),
+                                       C.c_double, C.c_double]),
+    "hpe_window_from_pose": (C.c_int, [C.c_void_p, dp, C.c_double, C.c_double, C.c_double,
+                                       C.POINTER(Window)]),
+    "hpe_batch_windows_readback": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Window)]),
     "hpe_build_spheres":(C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),

@@ -291,7 +291,8 @@ int hpe_track_sequence_dev(hpe_ctx *ctx, int num_p, int refine, double *d_state,
  * in the workgroup-per-particle form (below 1024 by default); every frame at most 2048 cloud
  * points (the single-workgroup refine); for each frame index all lanes on the same side of 256
  * cloud points (one kernel form per launch) -- HPE_E_ARG; no live subswarm transport and no
- * hpe_set_exchange -- HPE_E_STATE. */
+ * hpe_set_exchange -- HPE_E_STATE.  The slots are prepared already: this call prepares nothing
+ * and ignores the lane windows' mode (hpe_set_batch_window). */
 #define HPE_BATCH_MAX 16
 int hpe_track_batch_dev(hpe_ctx *ctx, int num_p, int refine, int B, double *d_states,
                         const int32_t *first_slots, int n, int frames_per_graph, double *d_hist);
@@ -411,6 +412,74 @@ int hpe_track_batch_pipelined(hpe_ctx *ctx, int num_p, int refine, int B, double
 #define HPE_BATCH_FORM_WAVE 1
 int hpe_set_batch_form(hpe_ctx *ctx, int form);
 int hpe_batch_wave_wpp(hpe_ctx *ctx, int num_p, int B);
+
+/* Lane windows: every lane of hpe_track_raw_batch_dev and of the live batch
+ * (hpe_batch_pipeline_begin / hpe_track_batch_pipelined) segments its depth frames by a window of
+ * its own -- an image rectangle and a depth range -- applied inside the lanes' preparation (the
+ * one that rides in the refine launch), so a live camera's forearm, body and table, or the other
+ * hand of a two-hand stream, never reach the cloud or the distance transform.  Two lanes that
+ * name the same raw buffer then see one hand each.
+ *
+ * Masking rule.  Pixel (r, c) with raw value rv is kept iff row_lo <= r <= row_hi,
+ * col_lo <= c <= col_hi and z_lo <= Z <= z_hi, where Z is the preparation's converted depth,
+ * exactly to_cm ? (double)rv / 10. : (double)rv.  Every other pixel is read as if its raw value
+ * were 0.0f, by the cloud's band workgroups and by the distance transform's mask alike.  So
+ * lo > hi or a NaN bound keeps nothing, {0, 239, 0, 319, -inf, +inf} keeps everything, and the
+ * windowed preparation of a frame is the plain preparation of that frame masked on the host
+ * (hpe/window.py: apply) -- bit for bit.
+ *
+ * Pose rule (hpe_window_from_pose, and on the device under HPE_WINDOW_FOLLOW).  S: the 48
+ * centres hpe_build_spheres returns for theta, bit for bit; R: the context hand's radii.  For
+ * sphere j: x = S[j][0], y = S[j][1] * -1, z = S[j][2] * -1 (camera coordinates),
+ *   e  = R[j] + margin_xy
+ *   cl = floor((focal*(x-e) + 160.0*z) / z),  ch the same with x+e
+ *   rl = floor((focal*(y-e) + 120.0*z) / z),  rh the same with y+e
+ *   zl = z - (R[j] + margin_z),               zh = z + (R[j] + margin_z)
+ * every product rounded before its add.  The window is
+ *   col_lo = (int)min(max(min_j cl, 0), 320)    col_hi = (int)min(max(max_j ch, -1), 319)
+ *   row_lo = (int)min(max(min_j rl, 0), 240)    row_hi = (int)min(max(max_j rh, -1), 239)
+ *   z_lo = min_j zl                             z_hi = max_j zh
+ * If any coordinate of any centre is not finite, or any z <= 0, the window is the whole frame
+ * {0, 239, 0, 319, -inf, +inf} (fail open: a NaN pose after a failed refine, a hand at or
+ * behind the camera).  hpe/window.py: from_spheres is the same rule in numpy.
+ *
+ * hpe_set_batch_window sets the mode of the context for B lanes, from the next
+ * hpe_track_raw_batch_dev call or hpe_batch_pipeline_begin on:
+ *   HPE_WINDOW_OFF (default)  everything as without windows; init and the margins are ignored.
+ *   HPE_WINDOW_FIXED   lane b's every frame is masked by init[b].
+ *   HPE_WINDOW_FOLLOW  frame 0 is masked by init[b] (hpe_window_from_pose on the lane's x0);
+ *       frame g >= 1 by the pose rule, with the call's focal and these margins, on what
+ *       d_states + 27 b holds when frame g-1's refine launch starts: the x0 the caller passed
+ *       for g = 1, frame g-2's bestp for g >= 2 -- the newest pose there is when frame g is
+ *       prepared, which happens inside frame g-1's refine launch.  A one-wave kernel per lane
+ *       (k_window_b) runs before that launch, on the stream, with no synchronisation.
+ * init (host, B windows) and the margins (cm) are copied; they live in device memory, so a
+ * change between two calls takes effect and the tracking graphs, keyed by the mode alone,
+ * replay: OFF -> FOLLOW -> OFF captures nothing the third time.  Windows work under both batch
+ * forms (hpe_set_batch_form).  hpe_track_batch_dev (prepared slots) prepares nothing and ignores
+ * the mode, as do the single-sequence calls.
+ * hpe_window_from_pose: the pose rule on the device for one pose (host theta) with the given
+ * focal and margins; synchronises.  hpe_batch_windows_readback: synchronises and copies the B
+ * lane windows of one buffer parity (frame f of a call is prepared into parity f & 1, through the
+ * window of that parity) to out.
+ * Refused, never run another way: a mode outside 0..2, B outside 1..HPE_BATCH_MAX, a null init
+ * with a mode other than OFF, a negative or non-finite margin (focal <= 0, null pointers, a
+ * parity outside 0..1 in the other two calls), and a batch call or begin whose B differs from
+ * the B the windows were set for -- HPE_E_ARG; hpe_set_batch_window while a live batch is in
+ * progress -- HPE_E_STATE: the batch keeps the mode, windows and margins it began with, as it
+ * keeps its form; hpe_batch_windows_readback before any raw or live batch -- HPE_E_STATE. */
+typedef struct hpe_window {      /* 32 bytes; every bound inclusive */
+    int32_t row_lo, row_hi, col_lo, col_hi;   /* rows 0..239, columns 0..319 */
+    double z_lo, z_hi;           /* in the converted depth's unit (cm with to_cm) */
+} hpe_window;
+#define HPE_WINDOW_OFF 0
+#define HPE_WINDOW_FIXED 1
+#define HPE_WINDOW_FOLLOW 2
+int hpe_set_batch_window(hpe_ctx *ctx, int mode, int B, const hpe_window *init,
+                         double margin_xy, double margin_z);
+int hpe_window_from_pose(hpe_ctx *ctx, const double theta[26], double focal,
+                         double margin_xy, double margin_z, hpe_window *out);
+int hpe_batch_windows_readback(hpe_ctx *ctx, int parity, int B, hpe_window *out);
 
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through

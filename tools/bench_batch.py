@@ -17,7 +17,15 @@ refine, init, generation and final kernels of one more pass (HPE_PROF_*, direct 
 (hpe_set_batch_form); every line then carries the form and the waves per particle its launches
 used (hpe_batch_wave_wpp), and the check is against the single call on a second context created
 under HPE_PSO_FORM=wave and HPE_PSO_WPP=<the checked batch's>.
+--window fixed|follow (with --raw or --live): the lanes' frames read through lane windows
+(hpe_set_batch_window).  fixed: whole-frame windows, so the line prices the masking alone;
+follow: windows re-centred on the device from every lane's tracked pose, with margins (8 cm) wide
+enough that nothing is cut on the synthetic streams, so the line prices the masking and the
+window launch per frame.  The check against the lanes alone runs without windows; every line then
+records whether the timed run's results (raw: the histories; live: the final states) equalled a
+run of the same lanes without windows ("equals_off": informational, not asserted).
 Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
+                                             [--window off|fixed|follow]
                                              [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
@@ -34,6 +42,7 @@ sys.path[:0] = [str(ROOT), str(ROOT / "hand-pose-estimation_amd")]
 import numpy as np  # noqa: E402
 
 P, G, FPG = 256, 30, 8
+WIN_MARGIN = 8.0  # cm, --window follow: nothing of the synthetic hands is cut
 
 
 def make_lanes(ctx, B, n):
@@ -181,9 +190,12 @@ def main():
     ap.add_argument("--live", action="store_true")
     ap.add_argument("--form", choices=("auto", "wave"), default="auto")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--window", choices=("off", "fixed", "follow"), default="off")
     a = ap.parse_args()
     if a.raw and a.live:
         ap.error("--raw and --live are two modes")
+    if a.window != "off" and not (a.raw or a.live):
+        ap.error("--window needs --raw or --live: prepared slots have no preparation to window")
     import torch
     torch.cuda.is_available()
     import hpe
@@ -217,17 +229,33 @@ def main():
         if a.raw:
             ptrs = [r.data_ptr() for r in raws[:B]]
 
+        hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0") if a.raw else None
+
         def run():
             if a.live:
                 run_live(ctx, st, host[:B], n)
             elif a.raw:
-                ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG)
+                ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG,
+                                    d_hist_ptr=hist.data_ptr())
             else:
                 ctx.track_batch(P, 1, st.data_ptr(), slots, n, FPG)
             ctx.check(ctx.lib.hpe_sync(ctx.h))
 
         st = start_states(torch, hpe.X0, B)
         x0 = st.clone()
+
+        def results():
+            return (hist if a.raw else st).cpu().numpy().copy()
+
+        off = None
+        if a.window != "off":  # the same lanes without windows, then the windows for B lanes
+            run()
+            off = results()
+            if a.window == "fixed":
+                ctx.set_batch_window("fixed", [hpe.window.WHOLE] * B)
+            else:
+                w0 = ctx.window_from_pose(hpe.X0, margin_xy=WIN_MARGIN, margin_z=WIN_MARGIN)
+                ctx.set_batch_window("follow", [w0] * B, WIN_MARGIN, WIN_MARGIN)
         times = []
         for rep in range(a.reps + 1):  # the first call captures the graphs
             st.copy_(x0)
@@ -250,11 +278,19 @@ def main():
         if a.form == "wave":
             line["form"] = "wave"
             line["wpp"] = ctx.batch_wave_wpp(P, B)
+        if a.raw:
+            line["mode"] = "raw"
+        if a.raw or a.live:
+            line["window"] = a.window
+        if off is not None:
+            line["equals_off"] = bool(np.array_equal(results(), off))
         if a.profile:
             st.copy_(x0)
             torch.cuda.synchronize()
             line["kernels"] = kernel_means_us(ctx, run)
         print(json.dumps(line), flush=True)
+        if a.window != "off":
+            ctx.set_batch_window("off")
     ctx.close()
     return 0
 
