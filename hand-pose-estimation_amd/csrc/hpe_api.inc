@@ -116,6 +116,7 @@ struct GraphKey {
     int parity, tail_next, next, cur, B, to_cm, downsample;
     int wave;  // a batch in the wave form (hpe_set_batch_form): its waves per particle; else 0
     int win;   // the lane windows' mode (hpe_set_batch_window): other kernels, one more launch
+    int hands; // lane hands are set (hpe_set_batch_hands): the lane kernels that index the table
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
@@ -123,7 +124,7 @@ struct GraphKey {
         return P == o.P && G == o.G && refine == o.refine && k == o.k && staged == o.staged &&
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
                next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
-               to_cm == o.to_cm &&
+               hands == o.hands && to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -204,6 +205,13 @@ struct hpe_ctx {
     char err[512] = {0};
     DevHand hand;
     DevHand *d_hand = nullptr;
+    // the batch lanes' hands (hpe_set_batch_hands): one flat table, entry b lane b's, which the
+    // lane kernels' HANDS forms index by their lane; the context's hand in every entry while
+    // lane_hands_B == 0, when the !HANDS forms run (they read entry 0).  The graphs hold its
+    // address alone, and key whether hands are set (GraphKey::hands): rewriting the table (the
+    // stream drained) captures nothing.
+    DevHand *d_lane_hands = nullptr;  // [HPE_BATCH_MAX]
+    int lane_hands_B = 0;             // the B the lane hands were set for, 0: none
     std::vector<Slot> slots;
     int cur = -1;
     // scratch
@@ -702,13 +710,15 @@ static WaveGenFn wave_gen_kernel(int wpp, bool coop, bool x, bool r16) {
 // ... and its lane form's (no exchange)
 typedef void (*WaveLaneGenFn)(DevSwarm, size_t, const DevObs *, const DevHand *, int, double, double,
                               double);
-template <int WPP, bool COOP>
+template <int WPP, bool COOP, bool HANDS>
 static WaveLaneGenFn wave_lane_gen_kernel_t(bool r16) {
-    return r16 ? k_pso_gen_wb<true, WPP, COOP> : k_pso_gen_wb<false, WPP, COOP>;
+    return r16 ? k_pso_gen_wb<true, WPP, COOP, HANDS> : k_pso_gen_wb<false, WPP, COOP, HANDS>;
 }
+template <bool HANDS>
 static WaveLaneGenFn wave_lane_gen_kernel(int wpp, bool coop, bool r16) {
-    if (wpp == 2) return coop ? wave_lane_gen_kernel_t<2, true>(r16) : wave_lane_gen_kernel_t<2, false>(r16);
-    return coop ? wave_lane_gen_kernel_t<1, true>(r16) : wave_lane_gen_kernel_t<1, false>(r16);
+    if (wpp == 2)
+        return coop ? wave_lane_gen_kernel_t<2, true, HANDS>(r16) : wave_lane_gen_kernel_t<2, false, HANDS>(r16);
+    return coop ? wave_lane_gen_kernel_t<1, true, HANDS>(r16) : wave_lane_gen_kernel_t<1, false, HANDS>(r16);
 }
 
 // Waves per particle of the wave form: two while the swarm leaves SIMDs idle at one (the
@@ -1003,6 +1013,33 @@ static PrepArgs prep_args(hpe_ctx *c, Slot &s, const float *raw, int to_cm, int 
     return a;
 }
 
+// hpe_create's and hpe_set_batch_hands' check of one hand: the sphere counts the kernels are
+// built for.
+static bool hand_counts_ok(const hpe_hand_params &h) {
+    const int tb[4] = {2, 2, 2, 2}, fg[4] = {4, 2, 2, 2};
+    for (int k = 0; k < 4; ++k)
+        if (h.tb_spheres[k] != tb[k] || h.fg_spheres[k] != fg[k]) return false;
+    return true;
+}
+// ... and every value finite (a lane hand: one lane's NaN would otherwise pass for a failed track)
+static bool hand_values_finite(const hpe_hand_params &h) {
+    for (double v : h.geo_cm)
+        if (!std::isfinite(v)) return false;
+    for (double v : h.radii_cm)
+        if (!std::isfinite(v)) return false;
+    for (double v : h.cmc_deg)
+        if (!std::isfinite(v)) return false;
+    for (double v : h.spacing_cm)
+        if (!std::isfinite(v)) return false;
+    return true;
+}
+
+// Every entry of the lane hand table <- the context's hand (hpe_create; hands == NULL).
+static hipError_t reset_lane_hands(hpe_ctx *c) {
+    std::vector<DevHand> tab(HPE_BATCH_MAX, c->hand);
+    return hipMemcpy(c->d_lane_hands, tab.data(), sizeof(DevHand) * tab.size(), hipMemcpyHostToDevice);
+}
+
 static int check_P(hpe_ctx *c, int P) {
     if (P < 1 || P > 8192) return fail(c, HPE_E_ARG, "num_p %d out of range [1, 8192]", P);
     return HPE_OK;
@@ -1028,9 +1065,7 @@ int hpe_preprocess_depth(const float *depth_mm, int to_cm, int downsample, doubl
 int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
     if (!out || !hand) return HPE_E_ARG;
     *out = nullptr;
-    const int tb[4] = {2, 2, 2, 2}, fg[4] = {4, 2, 2, 2};
-    for (int k = 0; k < 4; ++k)
-        if (hand->tb_spheres[k] != tb[k] || hand->fg_spheres[k] != fg[k]) return HPE_E_ARG;
+    if (!hand_counts_ok(*hand)) return HPE_E_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return HPE_E_NODEVICE;
@@ -1047,6 +1082,7 @@ int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
     hpe::build_dev_hand(*hand, c->hand);
     if (dalloc(&c->d_hand, 1) != hipSuccess ||
         hipMemcpy(c->d_hand, &c->hand, sizeof(DevHand), hipMemcpyHostToDevice) != hipSuccess ||
+        dalloc(&c->d_lane_hands, HPE_BATCH_MAX) != hipSuccess || reset_lane_hands(c) != hipSuccess ||
         dalloc(&c->d_state, 32) != hipSuccess || dalloc(&c->d_evals, 4) != hipSuccess ||
         hipMemset(c->d_evals, 0, 4 * sizeof(int)) != hipSuccess ||
         dalloc(&c->d_obs, HPE_MAX_SLOTS) != hipSuccess || dalloc(&c->d_obs_active, 1) != hipSuccess ||
@@ -1113,6 +1149,7 @@ int hpe_destroy(hpe_ctx *c) {
     free_swarm(c->sw);
     free_opt(c->opt);
     dfree(c->d_hand);
+    dfree(c->d_lane_hands);
     dfree(c->d_theta);
     dfree(c->d_cost);
     dfree(c->d_terms);
@@ -2215,41 +2252,44 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
 // HPE_BATCH_FORM_WAVE: launch_pso's wave form with the lane dimension instead -- init and the
 // generations on (ceil(P / particles per workgroup), B) at pso_wpp(B * P) waves per particle, no
 // inbox counts -- and the same final kernels with same_eval = 0: they evaluate cal_cost(bestp).
+extern "C++" {  // (templates: the two lane launch functions, by whether lane hands are set)
+template <bool HANDS>
 static int launch_pso_lanes(hpe_ctx *c, int P, int B, double *d_states, const LaneFrameIo &io) {
     const DevSwarm d = batch_swarm(c);
     const size_t stride = c->sw.stride;
     const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
     static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
     const bool r16 = d.K <= 15, filt = io.filt;
-    const DevHand *hand = c->d_hand;
+    const DevHand *hand = c->d_lane_hands;  // the table: lane b's kernels read entry b
     const int wpp = batch_wave_wpp(c, P, B);
     if (wpp) {  // one or two waves per particle
         const int per_wg = PW_WPB / wpp;
         const dim3 grid((P + per_wg - 1) / per_wg, B);
         const bool coop = c->fk_coop;
-        auto ki = wpp == 2 ? (coop ? k_pso_init_wb<2, true> : k_pso_init_wb<2, false>)
-                           : (coop ? k_pso_init_wb<1, true> : k_pso_init_wb<1, false>);
+        auto ki = wpp == 2 ? (coop ? k_pso_init_wb<2, true, HANDS> : k_pso_init_wb<2, false, HANDS>)
+                           : (coop ? k_pso_init_wb<1, true, HANDS> : k_pso_init_wb<1, false, HANDS>);
         launch(c, HPE_PROF_PSO_INIT, ki, grid, dim3(PW_NT), 0, d, stride, (const double *)d_states,
                (const DevObs *)io.obs, hand);
-        auto kw = wave_lane_gen_kernel(wpp, coop, r16);
+        auto kw = wave_lane_gen_kernel<HANDS>(wpp, coop, r16);
         for (int g = 1; g <= d.G; ++g)
             launch(c, HPE_PROF_PSO_GEN, kw, grid, dim3(PW_NT), 0, d, stride, (const DevObs *)io.obs,
                    hand, g, W1, C1, C2);
     } else {
-        launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init_b<true> : k_pso_init_b<false>, dim3(P, B),
-               dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)io.obs, hand);
+        launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init_b<true, HANDS> : k_pso_init_b<false, HANDS>,
+               dim3(P, B), dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)io.obs,
+               hand);
         for (int g = 1; g <= d.G; ++g) {
             const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
             launch(c, HPE_PROF_PSO_GEN,
-                   filt ? (r16 ? k_pso_gen_b<true, true> : k_pso_gen_b<false, true>)
-                        : (r16 ? k_pso_gen_b<true, false> : k_pso_gen_b<false, false>),
+                   filt ? (r16 ? k_pso_gen_b<true, true, HANDS> : k_pso_gen_b<false, true, HANDS>)
+                        : (r16 ? k_pso_gen_b<true, false, HANDS> : k_pso_gen_b<false, false, HANDS>),
                    dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)io.obs, hand, g, W1, C1, C2,
                    kg);
         }
     }
     // every live cloud is bounded by 250 points: the non-FILT kernel
-    auto final_k = io.seq ? k_pso_final_live_b<false>
-                          : (filt ? k_pso_final_b<true> : k_pso_final_b<false>);
+    auto final_k = io.seq ? k_pso_final_live_b<false, HANDS>
+                          : (filt ? k_pso_final_b<true, HANDS> : k_pso_final_b<false, HANDS>);
     launch(c, HPE_PROF_PSO_FINAL, final_k, dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states, io.obs,
            hand, (DevObs *)nullptr, wpp ? 0 : 1, io.seq, io.done_host, io.hist, (const int *)nullptr,
            io.slots, io.cur);
@@ -2263,39 +2303,49 @@ static int launch_pso_lanes(hpe_ctx *c, int P, int B, double *d_states, const La
 // (1 + PREP_WG, B): it then carries every lane's next preparation, read through the raw cursor or
 // from the pinned ring, as a raw sequence's and the pipelined loop's do.  Then launch_pso_lanes.
 // (The _b kernels are emitted in the order the host code first names them: k_pso_init_b first.)
-static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_states,
-                            const LaneFrameIo &io) {
+template <bool HANDS>
+static int track_lane_frame_t(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                              const LaneFrameIo &io) {
     const DevObs *obs = io.obs;
-    const DevHand *hand = c->d_hand;
+    const DevHand *hand = c->d_lane_hands;  // the table: lane b's kernels read entry b
     const dim3 prep_grid(1 + PREP_WG, B);
     if (io.prep && io.win) {
         // the windowed forms; FOLLOW: first every lane's window from the pose its state holds
         // now -- this launch's refine workgroup overwrites it -- into the parity being prepared
         if (io.follow)
-            hipLaunchKernelGGL(k_window_b, dim3(B), dim3(64), 0, c->stream, (const double *)d_states,
-                               hand, (const WinPar *)c->win.d_par, io.win);
+            hipLaunchKernelGGL(k_window_b<HANDS>, dim3(B), dim3(64), 0, c->stream,
+                               (const double *)d_states, hand, (const WinPar *)c->win.d_par, io.win);
         if (io.raw)
             launch(c, HPE_PROF_REFINE,
-                   c->refine_exact ? k_refine_prep_wb<false> : k_refine_prep_wb<true>, prep_grid,
+                   c->refine_exact ? k_refine_prep_wb<false, HANDS> : k_refine_prep_wb<true, HANDS>, prep_grid,
                    dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep,
                    io.raw, (const int *)io.cur, (const DevWindow *)io.win);
         else
             launch(c, HPE_PROF_REFINE,
-                   c->refine_exact ? k_refine_ring_wb<false> : k_refine_ring_wb<true>, prep_grid,
+                   c->refine_exact ? k_refine_ring_wb<false, HANDS> : k_refine_ring_wb<true, HANDS>, prep_grid,
                    dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep,
                    (const DevWindow *)io.win);
     } else if (io.prep && io.raw)  // testmodel.cpp:126 + next_frame of the following iteration
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_prep_b<false> : k_refine_prep_b<true>,
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_prep_b<false, HANDS> : k_refine_prep_b<true, HANDS>,
                prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals,
                refine ? 1 : 0, io.prep, io.raw, (const int *)io.cur);
     else if (io.prep)
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_ring_b<false> : k_refine_ring_b<true>,
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_ring_b<false, HANDS> : k_refine_ring_b<true, HANDS>,
                prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals,
                refine ? 1 : 0, io.prep);
     else if (refine)  // testmodel.cpp:126
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false> : k_refine_b<true>,
+        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false, HANDS> : k_refine_b<true, HANDS>,
                dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals);
-    return launch_pso_lanes(c, P, B, d_states, io);
+    return launch_pso_lanes<HANDS>(c, P, B, d_states, io);
+}
+}  // extern "C++"
+// ... in the kernels' HANDS forms while lane hands are set, else in the forms that read the
+// context's hand as they did before there were lane hands (the batch graphs' key field).
+static int lane_hands_set(const hpe_ctx *c) { return c->lane_hands_B ? 1 : 0; }
+static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                            const LaneFrameIo &io) {
+    return lane_hands_set(c) ? track_lane_frame_t<true>(c, P, refine, B, d_states, io)
+                             : track_lane_frame_t<false>(c, P, refine, B, d_states, io);
 }
 
 int hpe_set_batch_form(hpe_ctx *c, int form) {
@@ -2366,9 +2416,10 @@ static int write_windows(hpe_ctx *c, double focal, int to_cm) {
     return HPE_OK;
 }
 
-int hpe_window_from_pose(hpe_ctx *c, const double *theta, double focal, double margin_xy,
-                         double margin_z, hpe_window *out) {
-    if (!c) return HPE_E_ARG;
+// The pose rule for one host pose under one device hand: hpe_window_from_pose (the context's
+// hand) and hpe_lane_window_from_pose (a lane's entry of the table).
+static int window_from_pose(hpe_ctx *c, const DevHand *hand, const double *theta, double focal,
+                            double margin_xy, double margin_z, hpe_window *out) {
     if (!theta || !out) return fail(c, HPE_E_ARG, "null pose or window");
     if (!(focal > 0)) return fail(c, HPE_E_ARG, "focal %g is not positive", focal);
     if (!(margin_xy >= 0) || !(margin_z >= 0) || std::isinf(margin_xy) || std::isinf(margin_z))
@@ -2384,13 +2435,62 @@ int hpe_window_from_pose(hpe_ctx *c, const double *theta, double focal, double m
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(w.d_one_state, theta, sizeof(double) * HPE_DOF, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(w.d_one_par, &par, sizeof(par), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_window_b, dim3(1), dim3(64), 0, c->stream, (const double *)w.d_one_state,
-                       (const DevHand *)c->d_hand, (const WinPar *)w.d_one_par, w.d_one);
+    hipLaunchKernelGGL(k_window_b<false>, dim3(1), dim3(64), 0, c->stream,
+                       (const double *)w.d_one_state, hand, (const WinPar *)w.d_one_par, w.d_one);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     DevWindow r;
     HIPCHK(c, hipMemcpy(&r, w.d_one, sizeof(r), hipMemcpyDeviceToHost));
     *out = hpe_window{r.row_lo, r.row_hi, r.col_lo, r.col_hi, r.z_lo, r.z_hi};
+    return HPE_OK;
+}
+
+int hpe_window_from_pose(hpe_ctx *c, const double *theta, double focal, double margin_xy,
+                         double margin_z, hpe_window *out) {
+    if (!c) return HPE_E_ARG;
+    return window_from_pose(c, c->d_hand, theta, focal, margin_xy, margin_z, out);
+}
+
+int hpe_lane_window_from_pose(hpe_ctx *c, int lane, const double *theta, double focal,
+                              double margin_xy, double margin_z, hpe_window *out) {
+    if (!c) return HPE_E_ARG;
+    if (lane < 0 || lane >= HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "lane %d out of range [0, %d]", lane, HPE_BATCH_MAX - 1);
+    return window_from_pose(c, c->d_lane_hands + lane, theta, focal, margin_xy, margin_z, out);
+}
+
+int hpe_set_batch_hands(hpe_ctx *c, int B, const hpe_hand_params *hands) {
+    if (!c) return HPE_E_ARG;
+    if (hands) {
+        if (B < 1 || B > HPE_BATCH_MAX)
+            return fail(c, HPE_E_ARG, "hands for %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+        for (int b = 0; b < B; ++b) {
+            if (!hand_counts_ok(hands[b]))
+                return fail(c, HPE_E_ARG, "lane %d: sphere counts are not tb {2,2,2,2}, fg {4,2,2,2}", b);
+            if (!hand_values_finite(hands[b]))
+                return fail(c, HPE_E_ARG, "lane %d: a hand parameter is not finite", b);
+        }
+    }
+    if (c->live.cur >= 0)
+        return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the hands it began with "
+                    "(end it first)");
+    // lanes past B keep the context's hand: no batch call reads them while B is set
+    std::vector<DevHand> tab(HPE_BATCH_MAX, c->hand);
+    for (int b = 0; hands && b < B; ++b) hpe::build_dev_hand(hands[b], tab[b]);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight read the table
+    HIPCHK(c, hipMemcpy(c->d_lane_hands, tab.data(), sizeof(DevHand) * tab.size(),
+                        hipMemcpyHostToDevice));
+    c->lane_hands_B = hands ? B : 0;  // no epoch bump: the graphs hold the table's address and
+                                      // key whether hands are set (GraphKey::hands)
+    return HPE_OK;
+}
+
+// A batch call's or begin's lane count against the lane hands' (no lane hands: any).
+static int check_hand_lanes(hpe_ctx *c, int B) {
+    if (c->lane_hands_B && B != c->lane_hands_B)
+        return fail(c, HPE_E_ARG, "%d lanes, the hands were set for %d (hpe_set_batch_hands)", B,
+                    c->lane_hands_B);
     return HPE_OK;
 }
 
@@ -2425,7 +2525,7 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
                         const int32_t *first_slots, int n, int frames_per_graph, double *d_hist) {
     if (!c) return HPE_E_ARG;
     int rc = check_chunked_call(c, P, frames_per_graph);
-    if (rc || (rc = check_batch_call(c, P, B))) return rc;
+    if (rc || (rc = check_batch_call(c, P, B)) || (rc = check_hand_lanes(c, B))) return rc;
     if (!d_states || !first_slots) return fail(c, HPE_E_ARG, "null device states or first slots");
     if (n < 1) return fail(c, HPE_E_ARG, "n = %d frames", n);
     for (int b = 0; b < B; ++b) {
@@ -2467,6 +2567,7 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
         key.k = k;
         key.B = B;
         key.wave = batch_wave_wpp(c, P, B);
+        key.hands = lane_hands_set(c);
         for (int i = 0; i < k; ++i)
             if (c->slots[first_slots[0] + f0 + i].n_max > HPE_NT / 2) key.filt |= 1u << i;
         // k frames of B lanes, one after the other on the tracking stream: each lane on its own
@@ -2790,7 +2891,7 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
     if (!downsample)
         return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
                     "the single-workgroup refine (<= %d)", HPE_IMG_H * HPE_IMG_W, RF_STAGE_MAX);
-    if ((rc = check_window_lanes(c, B))) return rc;
+    if ((rc = check_window_lanes(c, B)) || (rc = check_hand_lanes(c, B))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     to_cm = to_cm ? 1 : 0;
     if ((rc = ensure_raw_batch(c, B, to_cm, focal))) return rc;
@@ -2822,6 +2923,7 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
         key.B = B;
         key.wave = batch_wave_wpp(c, P, B);
         key.win = c->win.mode;
+        key.hands = lane_hands_set(c);
         key.to_cm = to_cm;
         key.downsample = 1;
         key.focal = focal;
@@ -2896,6 +2998,7 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
             return fail(c, HPE_E_STATE, "HPE_PIPE_UPLOAD=1: the upload form is not built for lanes "
                         "(a live batch reads its pinned buffers in place)");
     if (int wrc = check_window_lanes(c, B)) return wrc;
+    if (int hrc = check_hand_lanes(c, B)) return hrc;
     HIPCHK(c, hipSetDevice(c->device));
     // the frames of a batch in progress are done with: its pinned buffers are free to refill
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2961,6 +3064,7 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     key.B = B;
     key.wave = batch_wave_wpp(c, P, B);
     key.win = c->win.mode;  // the begin's: it cannot change while the batch lives
+    key.hands = lane_hands_set(c);  // ... nor can the hands
     key.cur = cur;
     key.next = next;
     key.to_cm = lv.to_cm;

@@ -1176,7 +1176,8 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
 // the mutable arrays of all lanes are B identical arenas `stride` bytes apart, the argument
 // holds lane 0's pointers, and a lane rebases them with scalar adds on the entry batch's
 // words (no table of per-lane structs to load first).  normals, outl, bounds and the inbox
-// counts are shared: every lane draws under the context's seed.  Lanes never communicate.
+// counts are shared: every lane draws under the context's seed.  The hand is the context's, or
+// the lane's own (lane_hand below).  Lanes never communicate.
 __device__ __forceinline__ DevSwarm lane_swarm(DevSwarm sw, size_t stride) {
     const size_t off = stride * blockIdx.y;
     sw.xh = (double *)((char *)sw.xh + off);
@@ -1189,27 +1190,37 @@ __device__ __forceinline__ DevSwarm lane_swarm(DevSwarm sw, size_t stride) {
     sw.gpos = (double *)((char *)sw.gpos + off);
     return sw;
 }
+// The lane's hand (hpe_set_batch_hands).  HANDS: entry blockIdx.y of the flat table the kernel
+// receives where the kernel it mirrors receives the context's hand -- one scalar multiply-add on
+// the argument word, like the arenas above.  !HANDS (no lane hands set: every entry is the
+// context's hand): entry 0, the pointer as it came, and the kernel compiles as it did before
+// there were lane hands.  (Indexing always cost nothing in itself, but the four scalar
+// instructions at entry moved the compiler's schedule of the refine body: DESIGN.md 4.7.)
+template <bool HANDS>
+__device__ __forceinline__ const DevHand *lane_hand(const DevHand *__restrict__ tab) {
+    return HANDS ? tab + blockIdx.y : tab;
+}
 #define HPE_STATE_N (HPE_DOF + 1)  // {x0 -> bestp, cost} of one lane
 #define HPE_EVALS_N 4              // a lane's refine evaluation counter {last, -, total (u64)}
 
 // states: B x 27; obs: B descriptors, lane b's current frame (k_seq_begin_b / k_pso_final_b)
-template <bool FILT>
+template <bool FILT, bool HANDS>
 __global__ __launch_bounds__(HPE_NT) void k_pso_init_b(DevSwarm sw, size_t stride,
                                                        const double *__restrict__ states,
                                                        const DevObs *__restrict__ obs,
                                                        const DevHand *__restrict__ Hg) {
     pso_init_body<HPE_NT, FILT>(lane_swarm(sw, stride), states + (size_t)HPE_STATE_N * blockIdx.y,
-                                obs + blockIdx.y, Hg);
+                                obs + blockIdx.y, lane_hand<HANDS>(Hg));
 }
 
-template <bool ROW16, bool FILT>
+template <bool ROW16, bool FILT, bool HANDS>
 __global__ __launch_bounds__(HPE_NT) void k_pso_gen_b(DevSwarm sw, size_t stride,
                                                       const DevObs *__restrict__ obs,
                                                       const DevHand *__restrict__ Hg, int g,
                                                       double W1, double C1, double C2,
                                                       InboxCounts kin) {
-    pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, Hg, g, W1, C1,
-                                             C2, kin);
+    pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, lane_hand<HANDS>(Hg),
+                                             g, W1, C1, C2, kin);
 }
 
 // k_pso_final's TAIL form on the lane's cursor cur[2 b] = {slot, row}: the row indexes hist
@@ -1217,10 +1228,10 @@ __global__ __launch_bounds__(HPE_NT) void k_pso_gen_b(DevSwarm sw, size_t stride
 // obs[b].  The arguments are k_pso_final's own (the host passes same_eval = 1 and no
 // selected-frame hand-back, pipeline counter or refine failure flag), so the body compiles as
 // it does there.
-template <bool FILT, bool TAIL = true>
+template <bool FILT, bool HANDS, bool TAIL = true>
 __global__ __launch_bounds__(HPE_NT) void k_pso_final_b(DevSwarm sw, size_t stride,
                                                         double *__restrict__ states, DevObs *obs,
-                                                        const DevHand *__restrict__ Hg,
+                                                        const DevHand *__restrict__ hands,
                                                         DevObs *__restrict__ obs_out, int same_eval,
                                                         unsigned long long *__restrict__ seq_dev,
                                                         unsigned long long *done_host,
@@ -1228,6 +1239,7 @@ __global__ __launch_bounds__(HPE_NT) void k_pso_final_b(DevSwarm sw, size_t stri
                                                         const int *__restrict__ fail,
                                                         const DevObs *__restrict__ seq_table,
                                                         int *__restrict__ cur) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     sw = lane_swarm(sw, stride);
     double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
     DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
@@ -1238,11 +1250,12 @@ __global__ __launch_bounds__(HPE_NT) void k_pso_final_b(DevSwarm sw, size_t stri
 
 // The single-workgroup staged refine, one workgroup per lane (grid (1, B)): no preparation
 // workgroups, no exchange pick, no helpers.
-template <bool RIGID, bool STAGED = true, bool MW = false>
+template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
 __global__ __launch_bounds__(RF_NT) void k_refine_b(double *__restrict__ states,
                                                     const DevObs *__restrict__ obs,
-                                                    const DevHand *__restrict__ Hg,
+                                                    const DevHand *__restrict__ hands,
                                                     int *__restrict__ evals_b) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
     int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
@@ -1319,14 +1332,15 @@ __global__ __launch_bounds__(PREP_NT) void k_prepare_b(const PrepArgs *__restric
 // workgroup (0, b) is k_refine_b's (it reads what that one reads: tab, raw_base and cur are
 // touched by the preparation workgroups (1.., b) alone), the others run prep_workgroup into the
 // lane's other buffer, as k_refine's do.  do_refine = 0: the preparation only.
-template <bool RIGID, bool STAGED = true, bool MW = false>
+template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
 __global__ __launch_bounds__(RF_NT) void k_refine_prep_b(double *__restrict__ states,
                                                          const DevObs *__restrict__ obs,
-                                                         const DevHand *__restrict__ Hg,
+                                                         const DevHand *__restrict__ hands,
                                                          int *__restrict__ evals_b, int do_refine,
                                                          const PrepArgs *__restrict__ tab,
                                                          const float *const *__restrict__ raw_base,
                                                          const int *__restrict__ cur) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
     int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
@@ -1358,12 +1372,13 @@ __global__ __launch_bounds__(PREP_NT) void k_prepare_ring_b(const PrepArgs *__re
 
 // k_refine_prep_b on the ring, grid (1 + PREP_WG, B): workgroup (0, b) is k_refine_b's, the
 // others prepare the lane's next frame from tab[b].raw.  do_refine = 0: the preparation only.
-template <bool RIGID, bool STAGED = true, bool MW = false>
+template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
 __global__ __launch_bounds__(RF_NT) void k_refine_ring_b(double *__restrict__ states,
                                                          const DevObs *__restrict__ obs,
-                                                         const DevHand *__restrict__ Hg,
+                                                         const DevHand *__restrict__ hands,
                                                          int *__restrict__ evals_b, int do_refine,
                                                          const PrepArgs *__restrict__ tab) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
     int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
@@ -1384,10 +1399,10 @@ __global__ __launch_bounds__(RF_NT) void k_refine_ring_b(double *__restrict__ st
 // on one word.  One counter serves the batch: the refine launch of every lane, which read the
 // pinned buffers, has retired before any workgroup of this launch starts.  blockIdx.y is
 // uniform, and the body's counter branch reaches no barrier.
-template <bool FILT, bool TAIL = true>
+template <bool FILT, bool HANDS, bool TAIL = true>
 __global__ __launch_bounds__(HPE_NT) void k_pso_final_live_b(DevSwarm sw, size_t stride,
                                                              double *__restrict__ states, DevObs *obs,
-                                                             const DevHand *__restrict__ Hg,
+                                                             const DevHand *__restrict__ hands,
                                                              DevObs *__restrict__ obs_out, int same_eval,
                                                              unsigned long long *__restrict__ seq_b,
                                                              unsigned long long *done_host,
@@ -1395,6 +1410,7 @@ __global__ __launch_bounds__(HPE_NT) void k_pso_final_live_b(DevSwarm sw, size_t
                                                              const int *__restrict__ fail,
                                                              const DevObs *__restrict__ seq_table,
                                                              int *__restrict__ cur) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     sw = lane_swarm(sw, stride);
     double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
     DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
@@ -1427,15 +1443,16 @@ __global__ __launch_bounds__(PREP_NT) void k_prepare_ring_wb(const PrepArgs *__r
     prep_workgroup<true>(tab[blockIdx.y], blockIdx.x, lds, nullptr, &pw);
 }
 
-template <bool RIGID, bool STAGED = true, bool MW = false>
+template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
 __global__ __launch_bounds__(RF_NT) void k_refine_prep_wb(double *__restrict__ states,
                                                           const DevObs *__restrict__ obs,
-                                                          const DevHand *__restrict__ Hg,
+                                                          const DevHand *__restrict__ hands,
                                                           int *__restrict__ evals_b, int do_refine,
                                                           const PrepArgs *__restrict__ tab,
                                                           const float *const *__restrict__ raw_base,
                                                           const int *__restrict__ cur,
                                                           const DevWindow *__restrict__ wtab) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
     int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
@@ -1453,13 +1470,14 @@ __global__ __launch_bounds__(RF_NT) void k_refine_prep_wb(double *__restrict__ s
 #include "hpe_refine_body.inc"
 }
 
-template <bool RIGID, bool STAGED = true, bool MW = false>
+template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
 __global__ __launch_bounds__(RF_NT) void k_refine_ring_wb(double *__restrict__ states,
                                                           const DevObs *__restrict__ obs,
-                                                          const DevHand *__restrict__ Hg,
+                                                          const DevHand *__restrict__ hands,
                                                           int *__restrict__ evals_b, int do_refine,
                                                           const PrepArgs *__restrict__ tab,
                                                           const DevWindow *__restrict__ wtab) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
     int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
@@ -1528,7 +1546,9 @@ __device__ __forceinline__ void window_wave(FkSm &f, const DevHand *__restrict__
 // blockIdx.x of wout (the table of the parity the NEXT refine launch prepares into).  One wave
 // per lane, a launch of its own before that refine launch: its refine workgroup overwrites the
 // state at its end, so the preparation workgroups riding in it cannot read the pose themselves;
-// the hand-off is the kernel boundary.  hpe_window_from_pose runs it on one pose.
+// the hand-off is the kernel boundary.  hpe_window_from_pose and hpe_lane_window_from_pose run
+// the !HANDS form on one pose, with the hand they name as Hg.
+template <bool HANDS>
 __global__ __launch_bounds__(64) void k_window_b(const double *__restrict__ states,
                                                  const DevHand *__restrict__ Hg,
                                                  const WinPar *__restrict__ par,
@@ -1536,7 +1556,9 @@ __global__ __launch_bounds__(64) void k_window_b(const double *__restrict__ stat
     __shared__ DevHand hs;
     __shared__ FkSm fk;
     const int l = threadIdx.x;
-    for (int q = l; q < (int)(sizeof(DevHand) / 8); q += 64) ((double *)&hs)[q] = gp((const double *)Hg)[q];
+    // the lane's hand: entry blockIdx.x of the table (this kernel's lane dimension is x)
+    const double *__restrict__ const hw = (const double *)(HANDS ? Hg + blockIdx.x : Hg);
+    for (int q = l; q < (int)(sizeof(DevHand) / 8); q += 64) ((double *)&hs)[q] = gp(hw)[q];
     if (l < HPE_DOF) fk.th[l] = states[(size_t)HPE_STATE_N * blockIdx.x + l];
     const WinPar p = *par;
     __syncthreads();
@@ -1558,22 +1580,24 @@ __device__ __forceinline__ DevSwarm lane_swarm_w(DevSwarm sw, size_t stride) {
     return sw;
 }
 
-template <int WPP, bool COOP>
+template <int WPP, bool COOP, bool HANDS>
 __global__ __launch_bounds__(PW_NT) void k_pso_init_wb(DevSwarm sw, size_t stride,
                                                        const double *__restrict__ states,
                                                        const DevObs *__restrict__ obs,
-                                                       const DevHand *__restrict__ Hg) {
+                                                       const DevHand *__restrict__ hands) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     sw = lane_swarm_w(sw, stride);
     const double *__restrict__ const x0 = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
 #include "hpe_wave_init_body.inc"
 }
 
-template <bool ROW16, int WPP, bool COOP>
+template <bool ROW16, int WPP, bool COOP, bool HANDS>
 __global__ __launch_bounds__(PW_NT, WPP == 2 ? 2 : 4) void k_pso_gen_wb(DevSwarm sw, size_t stride,
                                                       const DevObs *__restrict__ obs,
-                                                      const DevHand *__restrict__ Hg, int g,
+                                                      const DevHand *__restrict__ hands, int g,
                                                       double W1, double C1, double C2) {
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     constexpr bool XCH = false;  // no exchange inside a batch
     sw = lane_swarm_w(sw, stride);
     const DevObs *__restrict__ const og = obs + blockIdx.y;

@@ -17,7 +17,8 @@ import numpy as np
 from . import _lib, window
 from ._lib import HpeError, ptr
 
-__all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "HpeError",
+__all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "scaled_hand",
+           "HpeError",
            "gnd_truth_err",
            "Context", "preprocess_depth", "reference_bounds", "X0"]
 
@@ -267,6 +268,33 @@ class Context:
                                                  float(margin_xy), float(margin_z), C.byref(w)))
         return window.as_window(w)
 
+    def set_batch_hands(self, hands):
+        """A hand model per lane (hpe_set_batch_hands) in track_batch, track_raw_batch and the
+        live batch, from the next call or begin on: hands is a list of handmodel or
+        hpe._lib.HandParams, one per lane -- lane b is then the single-sequence call on a context
+        created with hands[b], bit for bit -- and the batch calls take exactly len(hands) lanes;
+        None (default): every lane tracks with the context's hand.  The single-sequence calls
+        always use the context's hand.  A live batch in progress keeps the hands it began with:
+        the call raises (HPE_E_STATE)."""
+        if hands is None:
+            self.check(self.lib.hpe_set_batch_hands(self._h, 0, None))
+            return
+        ps = [getattr(h, "params", h) for h in hands]
+        if any(not isinstance(p, _lib.HandParams) for p in ps):
+            raise TypeError("set_batch_hands takes handmodel or HandParams entries")
+        arr = (_lib.HandParams * max(len(ps), 1))(*ps)
+        self.check(self.lib.hpe_set_batch_hands(self._h, len(ps), arr))
+
+    def lane_window_from_pose(self, lane, theta, focal=241.42, margin_xy=0.0, margin_z=0.0):
+        """window_from_pose under lane `lane`'s hand (hpe_lane_window_from_pose): init[lane] of a
+        "follow" batch with lane hands.  Synchronises."""
+        th = _lib.as_f64(theta, (26,))
+        w = _lib.Window()
+        self.check(self.lib.hpe_lane_window_from_pose(self._h, int(lane), ptr(th, C.c_double),
+                                                      float(focal), float(margin_xy),
+                                                      float(margin_z), C.byref(w)))
+        return window.as_window(w)
+
     def batch_windows_readback(self, parity, B):
         """The B lane windows of one buffer parity (frame f of a call is prepared into parity
         f & 1), as a list of hpe.window.Window.  Synchronises."""
@@ -425,12 +453,42 @@ class handmodel:
         return S, J
 
 
+def reference_geometry():
+    """(geo_cm (20,), radii_cm (48,)) of the reference hand, from the committed misc/*.dat
+    values."""
+    d = json.loads((Path(__file__).parent / "hand_subject1.json").read_text())
+    return np.array(d["hgeo_mm"]) / 10.0, np.array(d["rad_mm"]) / 10.0
+
+
 def reference_hand(device=0):
     """The hand of test_full (testmodel.cpp:33-52) from the committed misc/*.dat values."""
-    d = json.loads((Path(__file__).parent / "hand_subject1.json").read_text())
-    geo = np.array(d["hgeo_mm"]) / 10.0
-    rad = np.array(d["rad_mm"]) / 10.0
+    geo, rad = reference_geometry()
     return handmodel(geo, SPACING, TB_SPHERES, FG_SPHERES, CMC, rad, device=device)
+
+
+def scaled_hand_params(scale, radius_scale=None) -> _lib.HandParams:
+    """The reference hand's parameters with geo_cm times scale and radii_cm times radius_scale
+    (default: scale); CMC, spacing and the sphere counts are the reference's.  No context."""
+    geo, rad = reference_geometry()
+    rs = scale if radius_scale is None else radius_scale
+    p = _lib.HandParams()
+    p.geo_cm[:] = [float(x) for x in geo * float(scale)]
+    p.radii_cm[:] = [float(x) for x in rad * float(rs)]
+    p.cmc_deg[:] = CMC
+    p.spacing_cm[:] = SPACING
+    p.tb_spheres[:] = TB_SPHERES
+    p.fg_spheres[:] = FG_SPHERES
+    return p
+
+
+def scaled_hand(scale, radius_scale=None, device=0):
+    """The reference hand with its segment lengths scaled by `scale` and its sphere radii by
+    radius_scale (default: scale) -- another subject's hand size for Context.set_batch_hands.
+    Only geometry and radii change, so oracle_np.Hand(geo, rad) / oracle.hand(geo, rad) mirror
+    it."""
+    p = scaled_hand_params(scale, radius_scale)
+    return handmodel(np.array(p.geo_cm[:]), SPACING, TB_SPHERES, FG_SPHERES, CMC,
+                     np.array(p.radii_cm[:]), device=device)
 
 
 class observedmodel:

@@ -80,6 +80,9 @@ SIGNATURES = {
     "hpe_window_from_pose": (C.c_int, [C.c_void_p, dp, C.c_double, C.c_double, C.c_double,
                                        C.POINTER(Window)]),
     "hpe_batch_windows_readback": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Window)]),
+    "hpe_set_batch_hands": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(HandParams)]),
+    "hpe_lane_window_from_pose": (C.c_int, [C.c_void_p, C.c_int, dp, C.c_double, C.c_double,
+                                            C.c_double, C.POINTER(Window)]),
     "hpe_build_spheres":(C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),

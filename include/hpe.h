@@ -481,6 +481,32 @@ int hpe_window_from_pose(hpe_ctx *ctx, const double theta[26], double focal,
                          double margin_xy, double margin_z, hpe_window *out);
 int hpe_batch_windows_readback(hpe_ctx *ctx, int parity, int B, hpe_window *out);
 
+/* Lane hands: every lane of the three batch calls (hpe_track_batch_dev, hpe_track_raw_batch_dev,
+ * hpe_batch_pipeline_begin / hpe_track_batch_pipelined) tracks with a hand model of its own --
+ * several subjects of a dataset, several people in front of a rig, or one stream under several
+ * candidate hand sizes -- under both batch forms.
+ *
+ * hpe_set_batch_hands: hands is a host array of B entries, copied before return.  From the next
+ * batch call or hpe_batch_pipeline_begin on, lane b computes everything with hands[b] -- FK, the
+ * radii, the collision term, the hand-frame refine's centres and the FOLLOW window rule -- and
+ * equals the single-sequence call on a context created with hands[b], bit for bit.  hands == NULL
+ * (the default state): every lane uses the context's hand again; B is ignored.  The hands live in
+ * one device table the lane kernels index by their lane, so a change between two calls of one
+ * shape replays the tracking graphs and captures nothing.  The single-sequence calls,
+ * hpe_build_spheres, hpe_eval_costs, hpe_window_from_pose, hpe_render_depth and the optimiser
+ * always use the context's hand.
+ * hpe_lane_window_from_pose: hpe_window_from_pose with R and S of lane `lane`'s hand (the
+ * context's hand while none are set: then the two calls agree bit for bit) -- init[lane] of a
+ * FOLLOW batch with lane hands.  Synchronises.
+ * Refused, and nothing changes: with non-NULL hands, B outside 1..HPE_BATCH_MAX, an entry whose
+ * sphere counts are not tb {2,2,2,2} / fg {4,2,2,2} (hpe_create's check) or that holds a
+ * non-finite value -- HPE_E_ARG; a batch call or begin whose B differs from the B the hands were
+ * set for -- HPE_E_ARG; hpe_set_batch_hands while a live batch is in progress -- HPE_E_STATE: the
+ * batch keeps the hands it began with; a lane outside 0..HPE_BATCH_MAX-1 -- HPE_E_ARG. */
+int hpe_set_batch_hands(hpe_ctx *ctx, int B, const hpe_hand_params *hands);
+int hpe_lane_window_from_pose(hpe_ctx *ctx, int lane, const double theta[26], double focal,
+                              double margin_xy, double margin_z, hpe_window *out);
+
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through
  * hipExtLaunchKernel with a start/stop event pair (dispatch-packet timestamps: the

@@ -1,0 +1,143 @@
+"""CPU-side checks of the lane hands (hpe_set_batch_hands, hpe_lane_window_from_pose; no GPU):
+
+* the two entry points are declared in include/hpe.h, exported by libhpe.so and in the binding's
+  signature table with matching argument types; a null context is refused with HPE_E_ARG; the
+  Python wrappers check their arguments before any library call;
+* hpe.scaled_hand's parameters are the reference parameters times the factors, with CMC, spacing
+  and the sphere counts untouched;
+* hpe::build_dev_hand (a stand-alone host program over csrc/hpe_host.cpp) is linear where it
+  should be: a scale-2 hand has L, FLc, FLs and the radii exactly doubled (a power of two scales
+  exactly) and the angle constants and sphere weights unchanged; the table entry is 2016 bytes.
+"""
+import ctypes as C
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import hand_data
+
+NAMES = {"hpe_set_batch_hands": 3, "hpe_lane_window_from_pose": 7}
+PKG = hand_data.ROOT / "hand-pose-estimation_amd"
+
+
+def _header():
+    txt = (hand_data.ROOT / "include" / "hpe.h").read_text()
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+@pytest.mark.parametrize("name", sorted(NAMES))
+def test_declared_exported_and_in_the_signature_table(name):
+    from hpe import _lib
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", _header())
+    assert m, "no declaration"
+    assert len(m.group(1).split(",")) == NAMES[name]
+    nm = subprocess.run(["nm", "-D", "--defined-only", str(PKG / "libhpe.so")],
+                        capture_output=True, text=True, check=True).stdout
+    assert re.search(r"\bT " + name + r"$", nm, flags=re.M)
+    res, args = _lib.SIGNATURES[name]
+    assert res is C.c_int and len(args) == NAMES[name]
+    assert getattr(_lib.load(), name).argtypes == args
+
+
+def test_argument_types_match_the_header():
+    from hpe import _lib
+    txt = _header()
+    assert re.search(r"int\s+hpe_set_batch_hands\s*\(\s*hpe_ctx\s*\*\s*ctx\s*,\s*int\s+B\s*,\s*"
+                     r"const\s+hpe_hand_params\s*\*\s*hands\s*\)\s*;", txt)
+    assert _lib.SIGNATURES["hpe_set_batch_hands"][1] == [C.c_void_p, C.c_int, C.POINTER(_lib.HandParams)]
+    assert re.search(r"int\s+hpe_lane_window_from_pose\s*\(\s*hpe_ctx\s*\*\s*ctx\s*,\s*int\s+lane\s*,\s*"
+                     r"const\s+double\s+theta\[26\]\s*,\s*double\s+focal\s*,\s*double\s+margin_xy\s*,"
+                     r"\s*double\s+margin_z\s*,\s*hpe_window\s*\*\s*out\s*\)\s*;", txt)
+    assert _lib.SIGNATURES["hpe_lane_window_from_pose"][1] == [
+        C.c_void_p, C.c_int, _lib.dp, C.c_double, C.c_double, C.c_double, C.POINTER(_lib.Window)]
+    # the lane call is hpe_window_from_pose with a lane in front
+    assert _lib.SIGNATURES["hpe_lane_window_from_pose"][1][2:] == _lib.SIGNATURES["hpe_window_from_pose"][1][1:]
+    # hpe_hand_params as the binding lays it out: 78 doubles and 8 int32
+    assert C.sizeof(_lib.HandParams) == 78 * 8 + 8 * 4
+
+
+def test_null_context_is_refused():
+    from hpe import _lib
+    lib = _lib.load()
+    hands = (_lib.HandParams * 2)()
+    w = _lib.Window()
+    th = np.zeros(26)
+    assert lib.hpe_set_batch_hands(None, 2, hands) == _lib.HPE_E_ARG
+    assert lib.hpe_set_batch_hands(None, 0, None) == _lib.HPE_E_ARG
+    assert lib.hpe_lane_window_from_pose(None, 0, th.ctypes.data_as(_lib.dp), 241.42, 1.0, 1.0,
+                                         C.byref(w)) == _lib.HPE_E_ARG
+
+
+def test_python_side_argument_checks():
+    import hpe
+    ctx = object.__new__(hpe.Context)  # never reached hpe_create
+    with pytest.raises(TypeError):
+        ctx.set_batch_hands([1.0, 2.0])
+    with pytest.raises(TypeError):
+        ctx.set_batch_hands([hpe.scaled_hand_params(1.0), "a hand"])
+
+
+# ---- hpe.scaled_hand's parameters
+@pytest.mark.parametrize("scale,rscale", [(0.9, 0.85), (1.1, 1.2), (2.0, None), (1.0, None)])
+def test_scaled_hand_parameters(scale, rscale):
+    import hpe
+    geo, rad = hand_data.geometry_cm()
+    p = hpe.scaled_hand_params(scale, rscale)
+    assert isinstance(p, hpe._lib.HandParams)
+    assert np.array_equal(np.array(p.geo_cm[:]), geo * scale)
+    assert np.array_equal(np.array(p.radii_cm[:]), rad * (scale if rscale is None else rscale))
+    assert tuple(p.cmc_deg[:]) == hpe.CMC and tuple(p.spacing_cm[:]) == hpe.SPACING
+    assert tuple(p.tb_spheres[:]) == (2, 2, 2, 2) and tuple(p.fg_spheres[:]) == (4, 2, 2, 2)
+    g0, r0 = hpe.reference_geometry()
+    assert np.array_equal(g0, geo) and np.array_equal(r0, rad)
+
+
+# ---- build_dev_hand on the host
+DEV_HAND = np.dtype([("Fc", "f8", 5), ("Fs", "f8", 5), ("FLc", "f8", 5), ("FLs", "f8", 5),
+                     ("T10x", "f8", 5), ("T10y", "f8", 5), ("L", "f8", (5, 4)), ("twc", "f8", 5),
+                     ("tws", "f8", 5), ("radii", "f8", 48), ("wa", "f8", 48), ("wb", "f8", 48),
+                     ("dg", "i4", 48), ("ja", "i4", 48)])
+
+
+@pytest.fixture(scope="module")
+def dev_hands(tmp_path_factory):
+    """DevHand of the reference hand, its scale-2 and scale-0.5 forms and scaled_hand(0.9, 0.85)."""
+    import hpe
+    d = tmp_path_factory.mktemp("dh")
+    exe = d / "dev_hand_dump"
+    csrc = PKG / "csrc"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-o", str(exe),
+                    str(hand_data.ROOT / "tests" / "cpp" / "dev_hand_dump.cpp"),
+                    str(csrc / "hpe_host.cpp"), f"-I{csrc}"], check=True, timeout=120)
+    ps = [hpe.scaled_hand_params(1.0), hpe.scaled_hand_params(2.0), hpe.scaled_hand_params(0.5),
+          hpe.scaled_hand_params(0.9, 0.85)]
+    (d / "in.bin").write_bytes(b"".join(bytes(p) for p in ps))
+    out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True,
+                         text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "4 hands of 2016 bytes" in out.stdout  # the lane table's stride
+    assert DEV_HAND.itemsize == 2016
+    return np.fromfile(d / "out.bin", dtype=DEV_HAND)
+
+
+@pytest.mark.parametrize("k,f", [(1, 2.0), (2, 0.5)])
+def test_build_dev_hand_scales_exactly_by_powers_of_two(dev_hands, k, f):
+    a, b = dev_hands[0], dev_hands[k]
+    for name in ("L", "FLc", "FLs", "radii"):
+        assert np.array_equal(b[name], a[name] * f), name
+        assert np.all(a[name] != 0)
+    for name in ("Fc", "Fs", "twc", "tws", "wa", "wb", "dg", "ja"):
+        assert np.array_equal(b[name], a[name]), name
+    # the T10 translation is not linear in the lengths (the spacing is not scaled): it does move
+    assert not np.array_equal(b["T10x"], a["T10x"] * f)
+
+
+def test_build_dev_hand_of_a_scaled_hand(dev_hands):
+    geo, rad = hand_data.geometry_cm()
+    a, s = dev_hands[0], dev_hands[3]
+    assert np.array_equal(a["L"].ravel(), geo) and np.array_equal(a["radii"], rad)
+    assert np.array_equal(s["L"].ravel(), geo * 0.9) and np.array_equal(s["radii"], rad * 0.85)
+    assert np.array_equal(s["Fc"], a["Fc"]) and np.array_equal(s["Fs"], a["Fs"])
+    assert np.array_equal(s["FLc"], geo.reshape(5, 4)[:, 0] * 0.9 * a["Fc"])

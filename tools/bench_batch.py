@@ -24,8 +24,13 @@ enough that nothing is cut on the synthetic streams, so the line prices the mask
 window launch per frame.  The check against the lanes alone runs without windows; every line then
 records whether the timed run's results (raw: the histories; live: the final states) equalled a
 run of the same lanes without windows ("equals_off": informational, not asserted).
+--hands distinct (with any mode and form): a hand model per lane (hpe_set_batch_hands) -- lane b
+of a B-lane line tracks frames rendered with its own hpe.scaled_hand(0.9 + 0.2 b / max(B - 1, 1))
+under that hand; the default, shared, is every lane on the context's hand.  Each line is then
+checked first (6 frames, every lane against the single call on its own hand's context; under
+--form wave on the first line only, whose yardstick contexts are created in that form).
 Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
-                                             [--window off|fixed|follow]
+                                             [--window off|fixed|follow] [--hands shared|distinct]
                                              [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
@@ -45,23 +50,32 @@ P, G, FPG = 256, 30, 8
 WIN_MARGIN = 8.0  # cm, --window follow: nothing of the synthetic hands is cut
 
 
-def make_lanes(ctx, B, n):
-    """Lane b's n frames rendered and prepared into slots b n .. b n + n - 1."""
+def lane_scale(b, B):
+    """--hands distinct: the size of lane b's hand, 0.9 .. 1.1 over the lanes."""
+    return 0.9 + 0.2 * b / max(B - 1, 1)
+
+
+def make_lanes(ctx, B, n, render=None):
+    """Lane b's n frames rendered (by render[b], default ctx) and prepared into slots
+    b n .. b n + n - 1."""
     from hpe import synth
     for b in range(B):
         poses = synth.trajectory(n, b, revert=0.02)
+        r = render[b] if render else ctx
         for f, th in enumerate(poses):
-            ctx.prepare_frame(b * n + f, np.ascontiguousarray(ctx.render_depth(th)))
+            ctx.prepare_frame(b * n + f, np.ascontiguousarray(r.render_depth(th)))
     ctx.check(ctx.lib.hpe_sync(ctx.h))
 
 
-def make_raw_lanes(ctx, torch, B, n):
-    """Lane b's n frames rendered and uploaded as one raw device tensor (n x 240 x 320 float mm)."""
+def make_raw_lanes(ctx, torch, B, n, render=None):
+    """Lane b's n frames rendered (by render[b], default ctx) and uploaded as one raw device
+    tensor (n x 240 x 320 float mm)."""
     from hpe import synth
     out = []
     for b in range(B):
         poses = synth.trajectory(n, b, revert=0.02)
-        fr = np.stack([np.ascontiguousarray(ctx.render_depth(th)) for th in poses])
+        r = render[b] if render else ctx
+        fr = np.stack([np.ascontiguousarray(r.render_depth(th)) for th in poses])
         out.append(torch.from_numpy(fr.astype(np.float32)).to("cuda:0"))
     return out
 
@@ -72,13 +86,14 @@ def start_states(torch, x0, B):
     return torch.from_numpy(x).to("cuda:0")
 
 
-def wave_yardstick_context(hpe, pso, wpp):
+def wave_yardstick_context(hpe, pso, wpp, scale=None):
     """A second context for the single calls a wave-form batch is checked against: the wave form
-    at the batch's waves per particle (both read from the environment at hpe_create)."""
+    at the batch's waves per particle (both read from the environment at hpe_create); with the
+    reference hand, or scaled_hand(scale)."""
     saved = {k: os.environ.get(k) for k in ("HPE_PSO_FORM", "HPE_PSO_WPP")}
     os.environ.update(HPE_PSO_FORM="wave", HPE_PSO_WPP=str(wpp))
     try:
-        hand = hpe.reference_hand(device=0)
+        hand = hpe.reference_hand(device=0) if scale is None else hpe.scaled_hand(scale)
     finally:
         for k, v in saved.items():
             if v is None:
@@ -89,6 +104,11 @@ def wave_yardstick_context(hpe, pso, wpp):
     return hand
 
 
+def lane_alone(alone, b):
+    """The yardstick context of lane b: alone is one context for every lane, or one per lane."""
+    return alone[b] if isinstance(alone, (list, tuple)) else alone
+
+
 def check_against_alone(ctx, torch, x0, B, n_frames, n=6, alone=None):
     st = start_states(torch, x0, B)
     hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0")
@@ -96,8 +116,8 @@ def check_against_alone(ctx, torch, x0, B, n_frames, n=6, alone=None):
     ctx.check(ctx.lib.hpe_sync(ctx.h))
     s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
     h1 = torch.empty((n, 27), dtype=torch.float64, device="cuda:0")
-    ctx = alone or ctx
     for b in range(B):
+        ctx = lane_alone(alone, b) or ctx
         s1.copy_(start_states(torch, x0, 1)[0])
         ctx.track_sequence(P, 1, s1.data_ptr(), b * n_frames, n, FPG, h1.data_ptr())
         ctx.check(ctx.lib.hpe_sync(ctx.h))
@@ -115,8 +135,8 @@ def check_raw_against_alone(ctx, torch, x0, raws, n=6, alone=None):
     ctx.check(ctx.lib.hpe_sync(ctx.h))
     s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
     h1 = torch.empty((n, 27), dtype=torch.float64, device="cuda:0")
-    ctx = alone or ctx
     for b in range(B):
+        ctx = lane_alone(alone, b) or ctx
         s1.copy_(start_states(torch, x0, 1)[0])
         ctx.track_raw_sequence(P, 1, s1.data_ptr(), raws[b].data_ptr(), n, frames_per_graph=FPG,
                                d_hist_ptr=h1.data_ptr())
@@ -152,8 +172,8 @@ def check_live_against_alone(ctx, torch, x0, host, n=6, alone=None):
         ctx.check(ctx.lib.hpe_sync(ctx.h))
         hist.append(st.cpu().numpy().copy())
     s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
-    ctx = alone or ctx
     for b in range(B):
+        ctx = lane_alone(alone, b) or ctx
         s1.copy_(start_states(torch, x0, 1)[0])
         ctx.pipeline_begin(host[b][0])
         for f in range(n):
@@ -191,6 +211,7 @@ def main():
     ap.add_argument("--form", choices=("auto", "wave"), default="auto")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--window", choices=("off", "fixed", "follow"), default="off")
+    ap.add_argument("--hands", choices=("shared", "distinct"), default="shared")
     a = ap.parse_args()
     if a.raw and a.live:
         ap.error("--raw and --live are two modes")
@@ -199,6 +220,7 @@ def main():
     import torch
     torch.cuda.is_available()
     import hpe
+    from hpe import synth
     counts = [int(x) for x in a.lanes.split(",")]
     n = a.frames
     hand = hpe.reference_hand(device=0)
@@ -226,6 +248,38 @@ def main():
         alone.close()
     for B in counts:
         slots = [b * n for b in range(B)]
+        if a.hands == "distinct":
+            # lane b's own hand: its frames rendered by, and its yardstick run on, a context
+            # created with it (in the wave form where this line's check needs that)
+            scales = [lane_scale(b, B) for b in range(B)]
+            checked = a.form != "wave" or B == counts[0]
+            if a.form == "wave" and checked:
+                own = [wave_yardstick_context(hpe, pso, ctx.batch_wave_wpp(P, B), s) for s in scales]
+            else:
+                own = [hpe.scaled_hand(s) for s in scales]
+                for h in own:
+                    pso._push(h.ctx)
+            render = [h.ctx for h in own]
+            ctx.set_batch_hands(own)
+            if a.live:
+                host = [[np.ascontiguousarray(render[b].render_depth(th), dtype=np.float32)
+                         for th in synth.trajectory(n, b, revert=0.02)] for b in range(B)]
+                if checked:
+                    check_live_against_alone(ctx, torch, hpe.X0, host, alone=render)
+            elif a.raw:
+                raws = make_raw_lanes(ctx, torch, B, n, render)
+                if checked:
+                    check_raw_against_alone(ctx, torch, hpe.X0, raws, alone=render)
+            else:
+                make_lanes(ctx, B, n, render)
+                if checked:
+                    for b in range(B):  # the lane's first 6 frames in its own context's slots
+                        for f in range(6):
+                            render[b].prepare_frame(b * n + f, np.ascontiguousarray(
+                                render[b].render_depth(synth.trajectory(n, b, revert=0.02)[f])))
+                    check_against_alone(ctx, torch, hpe.X0, B, n, alone=render)
+            for h in own:
+                h.ctx.close()
         if a.raw:
             ptrs = [r.data_ptr() for r in raws[:B]]
 
@@ -254,8 +308,9 @@ def main():
             if a.window == "fixed":
                 ctx.set_batch_window("fixed", [hpe.window.WHOLE] * B)
             else:
-                w0 = ctx.window_from_pose(hpe.X0, margin_xy=WIN_MARGIN, margin_z=WIN_MARGIN)
-                ctx.set_batch_window("follow", [w0] * B, WIN_MARGIN, WIN_MARGIN)
+                w0 = [ctx.lane_window_from_pose(b, hpe.X0, margin_xy=WIN_MARGIN, margin_z=WIN_MARGIN)
+                      for b in range(B)]  # (the context's hand in every lane unless --hands distinct)
+                ctx.set_batch_window("follow", w0, WIN_MARGIN, WIN_MARGIN)
         times = []
         for rep in range(a.reps + 1):  # the first call captures the graphs
             st.copy_(x0)
@@ -282,6 +337,10 @@ def main():
             line["mode"] = "raw"
         if a.raw or a.live:
             line["window"] = a.window
+        if a.hands == "distinct":
+            line["hands"] = "distinct"
+            line["hand_scales"] = [round(s, 6) for s in scales]
+            line["checked_against_own_hand_contexts"] = checked
         if off is not None:
             line["equals_off"] = bool(np.array_equal(results(), off))
         if a.profile:
@@ -291,6 +350,8 @@ def main():
         print(json.dumps(line), flush=True)
         if a.window != "off":
             ctx.set_batch_window("off")
+        if a.hands == "distinct":
+            ctx.set_batch_hands(None)
     ctx.close()
     return 0
 
