@@ -117,6 +117,7 @@ struct GraphKey {
     int wave;  // a batch in the wave form (hpe_set_batch_form): its waves per particle; else 0
     int win;   // the lane windows' mode (hpe_set_batch_window): other kernels, one more launch
     int hands; // lane hands are set (hpe_set_batch_hands): the lane kernels that index the table
+    int pacing; // a live batch's pacing (hpe_set_batch_pacing): FREE takes the idle-aware kernels
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
@@ -124,7 +125,7 @@ struct GraphKey {
         return P == o.P && G == o.G && refine == o.refine && k == o.k && staged == o.staged &&
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
                next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
-               hands == o.hands && to_cm == o.to_cm &&
+               hands == o.hands && pacing == o.pacing && to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -195,6 +196,9 @@ struct LaneFrameIo {
     // (null: no windows); follow: k_window_b rewrites it from the lanes' states first
     DevWindow *win = nullptr;
     bool follow = false;
+    // lane pacing (hpe_set_batch_pacing, HPE_PACING_FREE): the lanes' activity words, which the
+    // idle-aware kernel forms test at entry (null: lockstep, the plain forms)
+    const int *act = nullptr;
 };
 
 }  // namespace
@@ -326,6 +330,17 @@ struct hpe_ctx {
         unsigned long long enq = 0, used_seq[2] = {0, 0};
         int B = 0, cur = -1, to_cm = 1;  // cur: the current frames' parity, -1: no batch
         double focal = 0;
+        // lane pacing: the mode the batch began with; bit b of pending: lane b holds a prepared
+        // frame the next call tracks (every lane under LOCKSTEP); the lanes' activity words in
+        // device memory, written on the stream ahead of a frame's graph (k_lane_act)
+        int pacing = HPE_PACING_LOCKSTEP;
+        uint32_t pending = 0;
+        int *d_act = nullptr;  // [HPE_BATCH_MAX]
+        // the words d_act holds once the stream reaches this point (act_known): a call whose
+        // words are these enqueues no write -- a batch whose lanes all have every frame writes
+        // them once
+        int act_words[HPE_BATCH_MAX] = {};
+        bool act_known = false;
     } live;
     // lane windows (hpe_set_batch_window): the mode, and what the next raw batch call or live
     // begin writes to the device -- init into both parities of the window table d_tab (next to
@@ -346,6 +361,7 @@ struct hpe_ctx {
     bool seq_done_valid = false;
     unsigned epoch = 1;  // bumped whenever a buffer a captured graph uses is reallocated
     int batch_form = HPE_BATCH_FORM_AUTO;  // the batch calls' pso_evolve form (hpe_set_batch_form)
+    int batch_pacing = HPE_PACING_LOCKSTEP;  // the next live batch's pacing (hpe_set_batch_pacing)
     int pso_form = 0;    // 0 auto, 1 workgroup per particle, 2 wave per particle
     static constexpr int wave_form_min_p = 1024;
     int pso_wpp = 0;      // waves per particle of the wave form (0: auto)
@@ -1187,6 +1203,7 @@ int hpe_destroy(hpe_ctx *c) {
             if (h) (void)hipHostFree(h);
     dfree(c->live.d_tab);
     dfree(c->live.d_seq);
+    dfree(c->live.d_act);
     if (c->live.h_done) (void)hipHostFree(c->live.h_done);
     dfree(c->d_raw);
     dfree(c->d_tmp);
@@ -2339,11 +2356,78 @@ static int track_lane_frame_t(hpe_ctx *c, int P, int refine, int B, double *d_st
     return launch_pso_lanes<HANDS>(c, P, B, d_states, io);
 }
 }  // extern "C++"
+
+// The same frame of a free-paced live batch (io.act, HPE_PACING_FREE): launch for launch what
+// track_lane_frame_t and launch_pso_lanes enqueue for a live frame, whatever the lanes' masks are,
+// in the idle-aware kernel forms -- each tests its lane's activity word at entry, so which lanes
+// track and which prepare is decided on the device, by the words the call wrote on the stream
+// before this graph.  The forms exist in the HANDS shape alone (the table holds the context's
+// hand in every entry while no lane hands are set).  No raw cursor, history or slot table: the
+// live batch has none.
+static int track_lane_frame_paced(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                                  const LaneFrameIo &io) {
+    const DevObs *obs = io.obs;
+    const DevHand *hand = c->d_lane_hands;
+    const int *act = io.act;
+    const dim3 prep_grid(1 + PREP_WG, B);
+    const bool rigid = !c->refine_exact;
+    if (io.prep && io.win) {
+        if (io.follow)
+            hipLaunchKernelGGL(k_window_bi, dim3(B), dim3(64), 0, c->stream, (const double *)d_states,
+                               hand, (const WinPar *)c->win.d_par, io.win, act);
+        launch(c, HPE_PROF_REFINE, rigid ? k_refine_ring_wbi<true> : k_refine_ring_wbi<false>,
+               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
+               io.prep, (const DevWindow *)io.win, act);
+    } else if (io.prep)
+        launch(c, HPE_PROF_REFINE, rigid ? k_refine_ring_bi<true> : k_refine_ring_bi<false>,
+               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
+               io.prep, act);
+    else if (refine)
+        launch(c, HPE_PROF_REFINE, rigid ? k_refine_bi<true> : k_refine_bi<false>, dim3(1, B),
+               dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, act);
+    const DevSwarm d = batch_swarm(c);
+    const size_t stride = c->sw.stride;
+    const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
+    static const InboxCounts all_k{};
+    const bool r16 = d.K <= 15;
+    const int wpp = batch_wave_wpp(c, P, B);
+    if (wpp) {
+        const int per_wg = PW_WPB / wpp;
+        const dim3 grid((P + per_wg - 1) / per_wg, B);
+        const bool coop = c->fk_coop;
+        auto ki = wpp == 2 ? (coop ? k_pso_init_wbi<2, true> : k_pso_init_wbi<2, false>)
+                           : (coop ? k_pso_init_wbi<1, true> : k_pso_init_wbi<1, false>);
+        launch(c, HPE_PROF_PSO_INIT, ki, grid, dim3(PW_NT), 0, d, stride, (const double *)d_states,
+               obs, hand, act);
+        auto kw = wpp == 2 ? (coop ? (r16 ? k_pso_gen_wbi<true, 2, true> : k_pso_gen_wbi<false, 2, true>)
+                                   : (r16 ? k_pso_gen_wbi<true, 2, false> : k_pso_gen_wbi<false, 2, false>))
+                           : (coop ? (r16 ? k_pso_gen_wbi<true, 1, true> : k_pso_gen_wbi<false, 1, true>)
+                                   : (r16 ? k_pso_gen_wbi<true, 1, false> : k_pso_gen_wbi<false, 1, false>));
+        for (int g = 1; g <= d.G; ++g)
+            launch(c, HPE_PROF_PSO_GEN, kw, grid, dim3(PW_NT), 0, d, stride, obs, hand, g, W1, C1, C2,
+                   act);
+    } else {
+        // every live cloud is bounded by 250 points: the non-FILT kernels
+        launch(c, HPE_PROF_PSO_INIT, k_pso_init_bi<false>, dim3(P, B), dim3(HPE_NT), 0, d, stride,
+               (const double *)d_states, obs, hand, act);
+        for (int g = 1; g <= d.G; ++g) {
+            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
+            launch(c, HPE_PROF_PSO_GEN, r16 ? k_pso_gen_bi<true, false> : k_pso_gen_bi<false, false>,
+                   dim3(P, B), dim3(HPE_NT), 0, d, stride, obs, hand, g, W1, C1, C2, kg, act);
+        }
+    }
+    launch(c, HPE_PROF_PSO_FINAL, k_pso_final_live_bi<false>, dim3(1, B), dim3(HPE_NT), 0, d, stride,
+           d_states, io.obs, hand, (DevObs *)nullptr, wpp ? 0 : 1, io.seq, io.done_host,
+           (double *)nullptr, (const int *)nullptr, (const DevObs *)nullptr, (int *)nullptr, act);
+    HIPCHK(c, hipGetLastError());
+    return HPE_OK;
+}
 // ... in the kernels' HANDS forms while lane hands are set, else in the forms that read the
 // context's hand as they did before there were lane hands (the batch graphs' key field).
 static int lane_hands_set(const hpe_ctx *c) { return c->lane_hands_B ? 1 : 0; }
 static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_states,
                             const LaneFrameIo &io) {
+    if (io.act) return track_lane_frame_paced(c, P, refine, B, d_states, io);
     return lane_hands_set(c) ? track_lane_frame_t<true>(c, P, refine, B, d_states, io)
                              : track_lane_frame_t<false>(c, P, refine, B, d_states, io);
 }
@@ -2358,6 +2442,28 @@ int hpe_set_batch_form(hpe_ctx *c, int form) {
         return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the form it began with "
                     "(end it first)");
     c->batch_form = form;  // no epoch bump: the batch graphs are keyed by the form (GraphKey::wave)
+    return HPE_OK;
+}
+
+int hpe_set_batch_pacing(hpe_ctx *c, int mode) {
+    if (!c) return HPE_E_ARG;
+    if (mode != HPE_PACING_LOCKSTEP && mode != HPE_PACING_FREE)
+        return fail(c, HPE_E_ARG, "batch pacing %d is neither HPE_PACING_LOCKSTEP nor _FREE", mode);
+    // read at the begin: a live batch keeps the pacing it began with
+    if (c->live.cur >= 0 && mode != c->live.pacing)
+        return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the pacing it began "
+                    "with (end it first)");
+    c->batch_pacing = mode;  // no epoch bump: the live graphs are keyed by it (GraphKey::pacing)
+    return HPE_OK;
+}
+
+int hpe_batch_pending(hpe_ctx *c, uint32_t *mask_out) {
+    if (!c) return HPE_E_ARG;
+    if (!mask_out) return fail(c, HPE_E_ARG, "null mask");
+    if (c->live.cur < 0)
+        return fail(c, HPE_E_STATE, "no live batch: hpe_batch_pipeline_begin not called, or the "
+                    "batch ended");
+    *mask_out = c->live.pending;
     return HPE_OK;
 }
 
@@ -2947,6 +3053,8 @@ static int ensure_live_batch(hpe_ctx *c, int B) {
     if (!lv.d_tab) {
         HIPCHK(c, dalloc(&lv.d_tab, 2 * M));
         HIPCHK(c, dalloc(&lv.d_seq, 1));
+        HIPCHK(c, dalloc(&lv.d_act, HPE_BATCH_MAX));  // the lanes' activity words (lane pacing)
+        HIPCHK(c, hipMemset(lv.d_act, 0, sizeof(int) * HPE_BATCH_MAX));
         HIPCHK(c, hipHostMalloc((void **)&lv.h_done, sizeof(unsigned long long),
                                 hipHostMallocMapped | hipHostMallocCoherent));
         HIPCHK(c, hipHostGetDevicePointer((void **)&lv.h_done_dev, lv.h_done, 0));
@@ -2976,14 +3084,41 @@ static int lane_frames(const float *const *frames, int B) {
     for (int b = 0; b < B; ++b) set += frames[b] != nullptr;
     return set == B ? 1 : set == 0 ? 0 : -1;
 }
+// Bit b: entry b is non-null.
+static uint32_t lane_mask(const float *const *frames, int B) {
+    uint32_t m = 0;
+    for (int b = 0; b < B; ++b) m |= (uint32_t)(frames[b] != nullptr) << b;
+    return m;
+}
+
+// One call's activity words of a free-paced batch (HPE_ACT_TRACK: the lane tracks its current
+// frame, HPE_ACT_PREP: it prepares a next one), written on the stream ahead of the frame's graph
+// -- outside it: a captured argument could not change between replays.  Stream order makes the
+// one table enough while earlier calls are still in flight, and lets a call whose words are the
+// ones the table already holds at that point of the stream skip the launch (measured: the launch
+// ahead of every graph was most of what free pacing cost a batch with full masks, DESIGN.md 4.7).
+static void write_lane_act(hpe_ctx *c, int B, uint32_t track, uint32_t prep) {
+    hpe_ctx::LiveBatch &lv = c->live;
+    LaneAct a{};
+    for (int b = 0; b < B; ++b)
+        a.word[b] = (track >> b & 1 ? HPE_ACT_TRACK : 0) | (prep >> b & 1 ? HPE_ACT_PREP : 0);
+    if (lv.act_known && !std::memcmp(a.word, lv.act_words, sizeof(a.word))) return;
+    hipLaunchKernelGGL(k_lane_act, dim3(1), dim3(64), 0, c->stream, a, lv.d_act);
+    std::memcpy(lv.act_words, a.word, sizeof(a.word));
+    lv.act_known = true;
+}
 
 int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, int to_cm,
                              int downsample, double focal) {
     if (!c) return HPE_E_ARG;
     if (B < 1 || B > HPE_BATCH_MAX)
         return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
-    if (!depth_mm || lane_frames(depth_mm, B) != 1)
+    const bool paced = c->batch_pacing == HPE_PACING_FREE;
+    if (!depth_mm || (!paced && lane_frames(depth_mm, B) != 1))
         return fail(c, HPE_E_ARG, "null frame array or lane frame");
+    const uint32_t given = lane_mask(depth_mm, B);
+    if (!given)
+        return fail(c, HPE_E_ARG, "no lane frame: a free-paced batch begins with at least one");
     if (!(focal > 0)) return fail(c, HPE_E_ARG, "focal %g is not positive", focal);
     if (!downsample)
         return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
@@ -3014,8 +3149,18 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     lv.used_seq[0] = lv.used_seq[1] = 0;
     // frame 0 of every lane: into its pinned buffer of parity 0, prepared from there
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
-    for (int b = 0; b < B; ++b) std::memcpy(lv.h_raw[0][b], depth_mm[b], sizeof(float) * npix);
-    if (c->win.mode != HPE_WINDOW_OFF)
+    for (int b = 0; b < B; ++b)
+        if (given >> b & 1) std::memcpy(lv.h_raw[0][b], depth_mm[b], sizeof(float) * npix);
+    if (paced) {  // only the lanes given a frame prepare one; the others start empty
+        write_lane_act(c, B, 0, given);
+        if (c->win.mode != HPE_WINDOW_OFF)
+            hipLaunchKernelGGL(k_prepare_ring_wbi, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                               (const PrepArgs *)lv.d_tab, (const DevWindow *)c->win.d_tab,
+                               (const int *)lv.d_act);
+        else
+            hipLaunchKernelGGL(k_prepare_ring_bi, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                               (const PrepArgs *)lv.d_tab, (const int *)lv.d_act);
+    } else if (c->win.mode != HPE_WINDOW_OFF)
         hipLaunchKernelGGL(k_prepare_ring_wb, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
                            (const PrepArgs *)lv.d_tab, (const DevWindow *)c->win.d_tab);
     else
@@ -3026,6 +3171,8 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     lv.B = B;
     lv.to_cm = to_cm;
     lv.focal = focal;
+    lv.pacing = c->batch_pacing;
+    lv.pending = given;
     lv.cur = 0;
     return HPE_OK;
 }
@@ -3038,10 +3185,13 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     int rc = check_P(c, P);
     if (rc || (rc = check_batch_call(c, P, B))) return rc;
     if (!d_states) return fail(c, HPE_E_ARG, "null device states");
-    const int next = next_depth_mm ? lane_frames(next_depth_mm, B) : 0;
+    hpe_ctx::LiveBatch &lv = c->live;
+    // a free-paced batch (it keeps the pacing it began with) takes any subset of next frames, and
+    // a non-null array keeps it alive; in lockstep, a frame for every lane or for none
+    const bool paced = lv.cur >= 0 && lv.pacing == HPE_PACING_FREE;
+    const int next = !next_depth_mm ? 0 : paced ? 1 : lane_frames(next_depth_mm, B);
     if (next < 0)
         return fail(c, HPE_E_ARG, "next frames for some lanes only: lanes advance in lockstep");
-    hpe_ctx::LiveBatch &lv = c->live;
     if (lv.cur < 0)
         return fail(c, HPE_E_STATE, "no live batch: hpe_batch_pipeline_begin not called, or the "
                     "batch ended");
@@ -3051,12 +3201,14 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     HIPCHK(c, hipSetDevice(c->device));
     const int cur = lv.cur, nxt = cur ^ 1;
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
-    if (next) {  // the pinned buffers' previous frames (two ago) must have been read
+    const uint32_t all = B < 32 ? (1u << B) - 1 : ~0u;
+    const uint32_t given = !next ? 0 : paced ? lane_mask(next_depth_mm, B) : all;
+    if (given) {  // the pinned buffers' previous frames (two ago) must have been read
         if (lv.used_seq[nxt] && !wait_frame_done(lv.h_done, lv.used_seq[nxt]))
             return fail(c, HPE_E_HIP, "live batch frame %llu did not complete",
                         (unsigned long long)lv.used_seq[nxt]);
-        for (int b = 0; b < B; ++b)
-            std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], sizeof(float) * npix);
+        for (int b = 0; b < B; ++b)  // only the lanes given a frame
+            if (given >> b & 1) std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], sizeof(float) * npix);
     }
     const int G = ensure_tracking(c, P, B);  // (the lanes' tables are the begin's)
     if (G < 0) return G;
@@ -3065,6 +3217,8 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     key.wave = batch_wave_wpp(c, P, B);
     key.win = c->win.mode;  // the begin's: it cannot change while the batch lives
     key.hands = lane_hands_set(c);  // ... nor can the hands
+    key.pacing = lv.pacing;  // ... nor the pacing; FREE: next is "the array is non-null", and
+                             // the lanes' masks are never part of the key
     key.cur = cur;
     key.next = next;
     key.to_cm = lv.to_cm;
@@ -3079,11 +3233,16 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     io.follow = c->win.mode == HPE_WINDOW_FOLLOW;
     io.seq = lv.d_seq;
     io.done_host = lv.h_done_dev;
+    if (paced) {
+        write_lane_act(c, B, lv.pending, given);
+        io.act = lv.d_act;
+    }
     if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_LIVE_BATCH], key,
                           [&] { return track_lane_frame(c, P, refine, B, d_states, io); })))
         return rc;
     ++lv.enq;  // this frame's number; lane 0's final workgroup publishes it to h_done
-    if (next) lv.used_seq[nxt] = lv.enq;  // its refine launch reads h_raw[nxt]
+    if (given) lv.used_seq[nxt] = lv.enq;  // its refine launch reads h_raw[nxt]
+    lv.pending = given;
     lv.cur = next ? nxt : -1;
     return HPE_OK;
 }

@@ -1548,21 +1548,13 @@ __device__ __forceinline__ void window_wave(FkSm &f, const DevHand *__restrict__
 // state at its end, so the preparation workgroups riding in it cannot read the pose themselves;
 // the hand-off is the kernel boundary.  hpe_window_from_pose and hpe_lane_window_from_pose run
 // the !HANDS form on one pose, with the hand they name as Hg.
+// (The body is text of its own, hpe_window_body.inc: the idle-aware k_window_bi includes it too.)
 template <bool HANDS>
 __global__ __launch_bounds__(64) void k_window_b(const double *__restrict__ states,
                                                  const DevHand *__restrict__ Hg,
                                                  const WinPar *__restrict__ par,
                                                  DevWindow *__restrict__ wout) {
-    __shared__ DevHand hs;
-    __shared__ FkSm fk;
-    const int l = threadIdx.x;
-    // the lane's hand: entry blockIdx.x of the table (this kernel's lane dimension is x)
-    const double *__restrict__ const hw = (const double *)(HANDS ? Hg + blockIdx.x : Hg);
-    for (int q = l; q < (int)(sizeof(DevHand) / 8); q += 64) ((double *)&hs)[q] = gp(hw)[q];
-    if (l < HPE_DOF) fk.th[l] = states[(size_t)HPE_STATE_N * blockIdx.x + l];
-    const WinPar p = *par;
-    __syncthreads();
-    window_wave(fk, &hs, p, wout + blockIdx.x);
+#include "hpe_window_body.inc"
 }
 
 // ------------------------------------------------------------------ wave-form lanes
@@ -1602,6 +1594,222 @@ __global__ __launch_bounds__(PW_NT, WPP == 2 ? 2 : 4) void k_pso_gen_wb(DevSwarm
     sw = lane_swarm_w(sw, stride);
     const DevObs *__restrict__ const og = obs + blockIdx.y;
 #include "hpe_wave_gen_body.inc"
+}
+
+// ------------------------------------------------------------------ lane pacing
+// hpe_set_batch_pacing(HPE_PACING_FREE): the lanes of a live batch no longer advance in lockstep.
+// Every kernel the live batch launches has an idle-aware form here, the kernel it mirrors behind
+// an entry test of the lane's activity word act[lane] -- bit 0 (HPE_ACT_TRACK): the lane tracks
+// its current frame in this call; bit 1 (HPE_ACT_PREP): it prepares a next frame.  The host
+// writes a call's 16 words on the stream, ahead of the frame's graph (k_lane_act; not when the
+// table already holds them): the graphs hold the table's address alone, never a mask.
+// The test is one scalar load indexed by blockIdx, so the decision is workgroup-uniform, and it
+// stands before everything of the body: an idle workgroup loads nothing through the lane's
+// descriptor, state row, arena or table entries (a lane that never held a frame has descriptors
+// that name nothing), reaches no barrier, counter or hand-off, and stores nothing -- but for lane
+// 0's final workgroup, which publishes the call's frame number whether or not lane 0 tracks.
+// Built in the HANDS shape only: the hand table holds the context's hand in every entry while no
+// lane hands are set, which is pinned bit-identical to the !HANDS forms.
+#define HPE_ACT_TRACK 1
+#define HPE_ACT_PREP 2
+struct LaneAct {
+    int word[16];
+};
+static_assert(HPE_BATCH_MAX == 16, "LaneAct holds one word per lane");
+// One call's activity words, by value (as k_seq_begin_b takes its slots)
+__global__ void k_lane_act(LaneAct a, int *__restrict__ act) {
+    const int t = threadIdx.x;
+    if (t < HPE_BATCH_MAX) act[t] = a.word[t];
+}
+
+template <bool FILT>
+__global__ __launch_bounds__(HPE_NT) void k_pso_init_bi(DevSwarm sw, size_t stride,
+                                                        const double *__restrict__ states,
+                                                        const DevObs *__restrict__ obs,
+                                                        const DevHand *__restrict__ Hg,
+                                                        const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
+    pso_init_body<HPE_NT, FILT>(lane_swarm(sw, stride), states + (size_t)HPE_STATE_N * blockIdx.y,
+                                obs + blockIdx.y, lane_hand<true>(Hg));
+}
+
+template <bool ROW16, bool FILT>
+__global__ __launch_bounds__(HPE_NT) void k_pso_gen_bi(DevSwarm sw, size_t stride,
+                                                       const DevObs *__restrict__ obs,
+                                                       const DevHand *__restrict__ Hg, int g,
+                                                       double W1, double C1, double C2,
+                                                       InboxCounts kin,
+                                                       const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
+    pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, lane_hand<true>(Hg),
+                                             g, W1, C1, C2, kin);
+}
+
+template <int WPP, bool COOP>
+__global__ __launch_bounds__(PW_NT) void k_pso_init_wbi(DevSwarm sw, size_t stride,
+                                                        const double *__restrict__ states,
+                                                        const DevObs *__restrict__ obs,
+                                                        const DevHand *__restrict__ hands,
+                                                        const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
+    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
+    sw = lane_swarm_w(sw, stride);
+    const double *__restrict__ const x0 = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+#include "hpe_wave_init_body.inc"
+}
+
+template <bool ROW16, int WPP, bool COOP>
+__global__ __launch_bounds__(PW_NT, WPP == 2 ? 2 : 4) void k_pso_gen_wbi(DevSwarm sw, size_t stride,
+                                                      const DevObs *__restrict__ obs,
+                                                      const DevHand *__restrict__ hands, int g,
+                                                      double W1, double C1, double C2,
+                                                      const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
+    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
+    constexpr bool XCH = false;  // no exchange inside a batch
+    sw = lane_swarm_w(sw, stride);
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+#include "hpe_wave_gen_body.inc"
+}
+
+// k_pso_final_live_b.  Publication does not depend on lane 0 being active: when lane 0 idles, its
+// workgroup bumps the batch's frame counter and stores it to done_host as the body's first
+// statement would (the same wave, the same stores), then leaves -- once per call, even when no
+// lane tracks, so the host's wait on this parity's frame number always ends.
+template <bool FILT, bool TAIL = true>
+__global__ __launch_bounds__(HPE_NT) void k_pso_final_live_bi(DevSwarm sw, size_t stride,
+                                                              double *__restrict__ states, DevObs *obs,
+                                                              const DevHand *__restrict__ hands,
+                                                              DevObs *__restrict__ obs_out, int same_eval,
+                                                              unsigned long long *__restrict__ seq_b,
+                                                              unsigned long long *done_host,
+                                                              double *__restrict__ hist,
+                                                              const int *__restrict__ fail,
+                                                              const DevObs *__restrict__ seq_table,
+                                                              int *__restrict__ cur,
+                                                              const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) {
+        if (blockIdx.y == 0 && threadIdx.x == HPE_NT - 64) {
+            const unsigned long long n = *seq_b + 1;
+            *seq_b = n;
+            __hip_atomic_store(done_host, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        return;
+    }
+    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
+    sw = lane_swarm(sw, stride);
+    double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
+    DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
+    const DevObs *const og = seq_obs;
+    int *__restrict__ const seq_cur = cur ? cur + 2 * blockIdx.y : nullptr;
+    unsigned long long *__restrict__ const seq_dev = blockIdx.y == 0 ? seq_b : nullptr;
+#include "hpe_final_body.inc"
+}
+
+// k_refine_b, for the batch's ending frame
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_bi(double *__restrict__ states,
+                                                     const DevObs *__restrict__ obs,
+                                                     const DevHand *__restrict__ hands,
+                                                     int *__restrict__ evals_b,
+                                                     const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
+    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    const int do_refine = 1;
+    const PrepArgs pa{};
+    const DevMw mw{};
+    const DevPick pk{};
+    const PrepSplit ps{};
+    constexpr bool WIN = false;
+    const DevWindow pw{};
+#include "hpe_refine_body.inc"
+}
+
+// k_refine_ring_b: workgroup (0, b) runs iff the lane tracks, the preparation workgroups
+// (1.., b) iff it prepares -- all nine or none, so an idle preparation never touches the lane's
+// three hand-off counters, and a preparation that runs finds them as the last one left them.
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_ring_bi(double *__restrict__ states,
+                                                          const DevObs *__restrict__ obs,
+                                                          const DevHand *__restrict__ hands,
+                                                          int *__restrict__ evals_b, int do_refine,
+                                                          const PrepArgs *__restrict__ tab,
+                                                          const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & (blockIdx.x == 0 ? HPE_ACT_TRACK : HPE_ACT_PREP))) return;
+    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    PrepArgs pa{};
+    if (blockIdx.x >= 1) pa = tab[blockIdx.y];
+    const DevMw mw{};
+    const DevPick pk{};
+    const PrepSplit ps{};
+    constexpr bool WIN = false;
+    const DevWindow pw{};
+#include "hpe_refine_body.inc"
+}
+
+template <bool RIGID, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_ring_wbi(double *__restrict__ states,
+                                                           const DevObs *__restrict__ obs,
+                                                           const DevHand *__restrict__ hands,
+                                                           int *__restrict__ evals_b, int do_refine,
+                                                           const PrepArgs *__restrict__ tab,
+                                                           const DevWindow *__restrict__ wtab,
+                                                           const int *__restrict__ act) {
+    if (!(act[blockIdx.y] & (blockIdx.x == 0 ? HPE_ACT_TRACK : HPE_ACT_PREP))) return;
+    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    PrepArgs pa{};
+    DevWindow pw{};
+    if (blockIdx.x >= 1) {
+        pa = tab[blockIdx.y];
+        pw = wtab[blockIdx.y];
+    }
+    const DevMw mw{};
+    const DevPick pk{};
+    const PrepSplit ps{};
+    constexpr bool WIN = true;
+#include "hpe_refine_body.inc"
+}
+
+// k_prepare_ring_b / _wb for the begin: only the lanes given a first frame prepare one
+__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_bi(const PrepArgs *__restrict__ tab,
+                                                             const int *__restrict__ act) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    if (!(act[blockIdx.y] & HPE_ACT_PREP)) return;
+    prep_workgroup(tab[blockIdx.y], blockIdx.x, lds);
+}
+
+__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_wbi(const PrepArgs *__restrict__ tab,
+                                                              const DevWindow *__restrict__ wtab,
+                                                              const int *__restrict__ act) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    if (!(act[blockIdx.y] & HPE_ACT_PREP)) return;
+    const DevWindow pw = wtab[blockIdx.y];
+    prep_workgroup<true>(tab[blockIdx.y], blockIdx.x, lds, nullptr, &pw);
+}
+
+// k_window_b<true> (its lane dimension is x): the window of a lane that accepts no frame in
+// this call stays as it was, and its state row -- a joining lane's may hold anything -- is not read.
+__global__ __launch_bounds__(64) void k_window_bi(const double *__restrict__ states,
+                                                  const DevHand *__restrict__ Hg,
+                                                  const WinPar *__restrict__ par,
+                                                  DevWindow *__restrict__ wout,
+                                                  const int *__restrict__ act) {
+    if (!(act[blockIdx.x] & HPE_ACT_PREP)) return;
+    constexpr bool HANDS = true;
+#include "hpe_window_body.inc"
 }
 
 #include "hpe_optimise.hpp"

@@ -44,6 +44,7 @@ def reference_bounds():
 
 
 BATCH_FORMS = {"auto": _lib.BATCH_FORM_AUTO, "wave": _lib.BATCH_FORM_WAVE}
+BATCH_PACINGS = {"lockstep": _lib.PACING_LOCKSTEP, "free": _lib.PACING_FREE}
 WINDOW_MODES = {"off": _lib.WINDOW_OFF, "fixed": _lib.WINDOW_FIXED, "follow": _lib.WINDOW_FOLLOW}
 
 
@@ -187,18 +188,20 @@ class Context:
             int(to_cm), int(downsample), float(focal), int(frames_per_graph),
             C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
 
-    @staticmethod
-    def _host_frames(what, depths):
+    def _host_frames(self, what, depths):
         """The lanes' host frames as float32 240x320 arrays and the array of their addresses
-        (the arrays must outlive the call that takes the addresses)."""
+        (the arrays must outlive the call that takes the addresses).  Under the "free" pacing
+        (set_batch_pacing) an entry may be None: a null address, no frame for that lane."""
         ds = list(depths)
         if not 1 <= len(ds) <= _lib.BATCH_MAX:
             raise ValueError(f"{what} takes 1..{_lib.BATCH_MAX} lanes, got {len(ds)}")
-        if any(d is None for d in ds):
+        free = getattr(self, "_pacing", _lib.PACING_LOCKSTEP) == _lib.PACING_FREE
+        if not free and any(d is None for d in ds):
             raise ValueError(f"{what}: a frame for every lane or for none (lanes advance in "
                              "lockstep)")
-        fr = [np.ascontiguousarray(d, dtype=np.float32).reshape(IMG_H, IMG_W) for d in ds]
-        return fr, (C.c_void_p * len(fr))(*[f.ctypes.data for f in fr])
+        fr = [None if d is None else
+              np.ascontiguousarray(d, dtype=np.float32).reshape(IMG_H, IMG_W) for d in ds]
+        return fr, (C.c_void_p * len(fr))(*[None if f is None else f.ctypes.data for f in fr])
 
     def batch_pipeline_begin(self, depths, to_cm=True, downsample=True, focal=241.42):
         """Begin a live batch of B = len(depths) lanes: lane b's first raw frame (host, float
@@ -224,6 +227,27 @@ class Context:
             B = len(fr)
         self.check(self.lib.hpe_track_batch_pipelined(self._h, int(num_p), int(refine), B,
                                                       C.c_void_p(d_states_ptr), arr))
+
+    def set_batch_pacing(self, pacing):
+        """Whether the lanes of a live batch advance in lockstep (hpe_set_batch_pacing), read at
+        batch_pipeline_begin: "lockstep" / 0 (default: a frame for every lane or for none) or
+        "free" / 1 -- batch_pipeline_begin and track_batch_pipelined then accept None entries: a
+        lane given no frame idles for that call, bit for bit untouched, and a lane may start empty
+        and join later; a lane tracks in a call iff it holds a prepared frame (batch_pending).
+        A live batch in progress keeps its pacing: a different one raises (HPE_E_STATE)."""
+        if isinstance(pacing, str):
+            if pacing not in BATCH_PACINGS:
+                raise ValueError(f"batch pacing {pacing!r} is not one of {sorted(BATCH_PACINGS)}")
+            pacing = BATCH_PACINGS[pacing]
+        self.check(self.lib.hpe_set_batch_pacing(self._h, int(pacing)))
+        self._pacing = int(pacing)
+
+    def batch_pending(self) -> int:
+        """Bit b set: lane b of the live batch holds a prepared frame that the next
+        track_batch_pipelined tracks (hpe_batch_pending; host bookkeeping, no synchronisation)."""
+        m = C.c_uint32(0)
+        self.check(self.lib.hpe_batch_pending(self._h, C.byref(m)))
+        return m.value
 
     def set_batch_form(self, form):
         """The form of pso_evolve in track_batch, track_raw_batch and the live batch

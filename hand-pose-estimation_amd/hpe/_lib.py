@@ -20,6 +20,7 @@ SUBSWARM_ID_BYTES = 128
 BATCH_MAX = 16  # HPE_BATCH_MAX
 BATCH_FORM_AUTO, BATCH_FORM_WAVE = 0, 1  # HPE_BATCH_FORM_*
 WINDOW_OFF, WINDOW_FIXED, WINDOW_FOLLOW = 0, 1, 2  # HPE_WINDOW_*
+PACING_LOCKSTEP, PACING_FREE = 0, 1  # HPE_PACING_*
 HPE_OK, HPE_E_ARG, HPE_E_HIP, HPE_E_STATE, HPE_E_NOMEM, HPE_E_NODEVICE = 0, -1, -2, -3, -4, -5
 
 dp = C.POINTER(C.c_double)
@@ -83,6 +84,8 @@ SIGNATURES = {
     "hpe_set_batch_hands": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(HandParams)]),
     "hpe_lane_window_from_pose": (C.c_int, [C.c_void_p, C.c_int, dp, C.c_double, C.c_double,
                                             C.c_double, C.POINTER(Window)]),
+    "hpe_set_batch_pacing": (C.c_int, [C.c_void_p, C.c_int]),
+    "hpe_batch_pending": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "hpe_build_spheres":(C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),

@@ -367,7 +367,8 @@ int hpe_track_raw_batch_dev(hpe_ctx *ctx, int num_p, int refine, int B, double *
  * copied into the library's pinned buffers before the call returns (the caller may overwrite
  * its frames at once).  next_depth_mm == NULL (or every entry NULL) tracks the current frames
  * and ends the batch; some but not all entries NULL is HPE_E_ARG: lanes advance in lockstep.
- * To change the lane set, end the batch and begin another; the caller owns d_states (device,
+ * (The default pacing: under hpe_set_batch_pacing(HPE_PACING_FREE), below, lanes skip calls, join
+ * late and pause.)  To change the lane count, end the batch and begin another; the caller owns d_states (device,
  * B x 27 {x0 -> bestp, cost}, read and overwritten every call), so poses carry over.
  * Asynchronous on hpe_stream(ctx).  Before a pinned buffer is refilled the host waits (bounded,
  * HPE_E_HIP on a timeout) for the frame number the final launch publishes to host memory.
@@ -506,6 +507,73 @@ int hpe_batch_windows_readback(hpe_ctx *ctx, int parity, int B, hpe_window *out)
 int hpe_set_batch_hands(hpe_ctx *ctx, int B, const hpe_hand_params *hands);
 int hpe_lane_window_from_pose(hpe_ctx *ctx, int lane, const double theta[26], double focal,
                               double margin_xy, double margin_z, hpe_window *out);
+
+/* Lane pacing: whether the lanes of a live batch (hpe_batch_pipeline_begin /
+ * hpe_track_batch_pipelined) advance in lockstep.  Cameras of a rig are not frame-locked: a 30 Hz
+ * and a 60 Hz camera share it, a USB camera drops a frame, a person leaves one view.
+ *
+ * hpe_set_batch_pacing sets the mode of the context, read at hpe_batch_pipeline_begin; a live
+ * batch keeps the pacing it began with, as it keeps its form, windows and hands.
+ *   HPE_PACING_LOCKSTEP (default)  everything as described above: a frame for every lane or for
+ *       none, in the begin and in every call.
+ *   HPE_PACING_FREE  a lane with no new frame idles for that call, and a lane may start empty and
+ *       join later:
+ *     begin.  depth_mm[b] may be NULL: lane b starts empty, nothing is copied or prepared for it.
+ *       At least one entry must be non-NULL (HPE_E_ARG).  A lane is PENDING iff it was given a
+ *       frame.
+ *     hpe_track_batch_pipelined with a non-NULL next_depth_mm array.  Any subset of its entries
+ *       may be NULL, all of them included.  Lane b tracks its current frame in this call iff it
+ *       is pending; its next frame is copied and prepared iff next_depth_mm[b] != NULL; afterwards
+ *       it is pending iff next_depth_mm[b] != NULL.  The batch stays alive even if no entry is
+ *       set: a call in which no lane is pending (prepare-only) and a call in which every entry is
+ *       NULL (track-only) are both legal.
+ *     next_depth_mm == NULL (the array itself) tracks the pending lanes and ends the batch.
+ *     An idle lane is untouched.  For a lane that does not track in a call, its 27 doubles in
+ *       d_states and its refine evaluation counter are bit for bit what they were.  The caller
+ *       may rewrite such a lane's row between two calls (re-initialising after a pause): a write
+ *       ordered on hpe_stream(ctx) takes effect.  A lane that joins reads its row when its first
+ *       frame is tracked, not before (under HPE_WINDOW_FOLLOW: when that frame is accepted, for
+ *       its window -- below).
+ *     The yardstick.  Let F0 .. Fm-1 be the frames lane b was given, in order, whatever calls
+ *       they arrived in.  Lane b's state after the call that tracks Fi equals, bit for bit, state
+ *       i of the single loop on the same context with the same form and refine form:
+ *       hpe_pipeline_begin(F0), then hpe_track_pipelined(..., Fi+1).  If the caller rewrote the
+ *       lane's row while it idled, the comparison is against the single loop restarted from that
+ *       row.
+ *     Windows.  HPE_WINDOW_FIXED is unchanged.  HPE_WINDOW_FOLLOW: a frame given to the begin is
+ *       masked by init[b]; the window of any later frame is the pose rule on what d_states + 27 b
+ *       holds when the call that accepts that frame starts its launches -- the lane's newest pose
+ *       at that moment, whether or not the lane also tracks in that call.  The window of a lane
+ *       that accepts no frame in a call stays as it was.
+ *     Lane hands, both batch forms and both refine forms are supported, with their yardsticks.
+ *     Frame publication happens once per call whatever the lanes do, and the host's bounded wait
+ *       before it refills a pinned buffer (HPE_E_HIP on a timeout) is the lockstep batch's.
+ * The masks never enter a graph's key: one table of 16 activity words in device memory, written
+ * on the stream before each frame's graph, decides in the kernels which lanes run.  A batch with
+ * arbitrary masks captures at most three graphs (two buffer parities with preparation, the ending
+ * frame); a second batch of that shape with other masks captures none; the lockstep graphs are
+ * their own.
+ * hpe_set_batch_pacing: a mode outside 0..1 -- HPE_E_ARG; another mode while a live batch is in
+ * progress -- HPE_E_STATE, and nothing changes (the mode the batch has is HPE_OK).  The resident
+ * batch calls (hpe_track_batch_dev, hpe_track_raw_batch_dev) and the single-sequence calls ignore
+ * the mode.
+ * hpe_batch_pending: bit b of *mask_out set: lane b holds a prepared frame that the next
+ * hpe_track_batch_pipelined will track (under LOCKSTEP: every lane of the batch).  Host
+ * bookkeeping only, no synchronisation.  HPE_E_STATE without a live batch; a null pointer --
+ * HPE_E_ARG.
+ * When to set it: when the streams are not frame-locked.  Measured on one MI355X at 256 particles
+ * per lane (DESIGN.md §4.7 "Lane pacing"): a free-paced batch whose lanes all have every frame
+ * runs about 1 % slower than the lockstep batch, at one lane as at 4 and 16 and in both batch
+ * forms (+0.7 to +1.4 % where the session's spread allowed a reading) -- the entry test of the
+ * ~34 launches of a frame; the activity words themselves are written only when they change.  With
+ * a staggered drop of one frame in 4 per lane it tracks 1.12x to 1.31x the frames of the only
+ * course open without it, ending the batch and beginning another at every change of the lane set
+ * (1.08x to 1.21x at one frame in 2).  A rig whose lanes are frame-locked is better left on
+ * LOCKSTEP. */
+#define HPE_PACING_LOCKSTEP 0   /* default: everything as without pacing */
+#define HPE_PACING_FREE 1
+int hpe_set_batch_pacing(hpe_ctx *ctx, int mode);
+int hpe_batch_pending(hpe_ctx *ctx, uint32_t *mask_out);
 
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through

@@ -29,8 +29,18 @@ of a B-lane line tracks frames rendered with its own hpe.scaled_hand(0.9 + 0.2 b
 under that hand; the default, shared, is every lane on the context's hand.  Each line is then
 checked first (6 frames, every lane against the single call on its own hand's context; under
 --form wave on the first line only, whose yardstick contexts are created in that form).
+--pacing free (with --live): the live batch under hpe_set_batch_pacing(HPE_PACING_FREE), the
+idle-aware kernel forms; without --drop every lane still gives every frame, so the line prices the
+forms' entry test and the per-call activity write against --pacing lockstep.
+--drop K (with --live): a staggered drop of one frame in K per lane -- lane b gives no frame in
+the next-frame array of every call whose index is = b mod K (the begin takes a frame of every
+lane).  Under --pacing free that lane idles for the following call.  Under --pacing lockstep the
+tool does what a caller has to do without pacing: whenever the set of lanes with a frame changes it
+ends the batch and begins another of just those lanes, their state rows gathered into a dense
+buffer and scattered back.  Both lines count the frames actually tracked ("tracked_frames").
 Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
                                              [--window off|fixed|follow] [--hands shared|distinct]
+                                             [--pacing lockstep|free] [--drop K]
                                              [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
@@ -161,6 +171,62 @@ def run_live(ctx, st, host, n):
                                   [fr[f + 1] for fr in host] if f + 1 < n else None)
 
 
+def gives(b, step, K):
+    """--drop K: whether lane b gives a frame at step `step` (0: the begin, s >= 1: the next-frame
+    array of call s - 1)."""
+    return not K or step == 0 or (step - 1) % K != b % K
+
+
+def run_live_paced(ctx, st, host, n, K):
+    """n steps of a free-paced batch under --drop K: every lane takes its frames in order, and
+    idles in the call after a step it gave no frame at.  Returns the frames tracked."""
+    B = len(host)
+    took = [0] * B
+
+    def frames(step):
+        fr = [None] * B
+        for b in range(B):
+            if gives(b, step, K):
+                fr[b] = host[b][took[b]]
+                took[b] += 1
+        return fr
+
+    ctx.batch_pipeline_begin(frames(0))
+    for s in range(n):
+        ctx.track_batch_pipelined(P, 1, st.data_ptr(), frames(s + 1) if s + 1 < n else None)
+    return sum(took)
+
+
+def run_live_rebegin(ctx, torch, st, subs, host, n, K):
+    """The same schedule without pacing: a lockstep batch of just the lanes that have a frame,
+    ended and begun again whenever that set changes (state rows gathered into subs[len(set)] and
+    scattered back).  Returns the frames tracked."""
+    B = len(host)
+    took = [0] * B
+
+    def frames(A):
+        fr = [host[b][took[b]] for b in A]
+        for b in A:
+            took[b] += 1
+        return fr
+
+    s = 0
+    while s < n:
+        A = [b for b in range(B) if gives(b, s, K)]
+        e = s
+        while e + 1 < n and [b for b in range(B) if gives(b, e + 1, K)] == A:
+            e += 1
+        idx = torch.tensor(A, device="cuda:0")
+        sub = subs[len(A)]
+        sub.copy_(st[idx])
+        ctx.batch_pipeline_begin(frames(A))
+        for q in range(s, e + 1):
+            ctx.track_batch_pipelined(P, 1, sub.data_ptr(), frames(A) if q < e else None)
+        st[idx] = sub
+        s = e + 1
+    return sum(took)
+
+
 def check_live_against_alone(ctx, torch, x0, host, n=6, alone=None):
     B = len(host)
     st = start_states(torch, x0, B)
@@ -212,7 +278,13 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--window", choices=("off", "fixed", "follow"), default="off")
     ap.add_argument("--hands", choices=("shared", "distinct"), default="shared")
+    ap.add_argument("--pacing", choices=("lockstep", "free"), default="lockstep")
+    ap.add_argument("--drop", type=int, default=0)
     a = ap.parse_args()
+    if (a.pacing != "lockstep" or a.drop) and not a.live:
+        ap.error("--pacing and --drop need --live: pacing is the live batch's")
+    if a.drop < 0 or a.drop == 1:
+        ap.error("--drop K: one frame in K per lane, K >= 2 (0: none)")
     if a.raw and a.live:
         ap.error("--raw and --live are two modes")
     if a.window != "off" and not (a.raw or a.live):
@@ -230,6 +302,8 @@ def main():
     pso.set_pso_params(ub, lb, sd, 0.7298, 1.49618, 1.49618, G + 1, 1e-8, 1e-8)
     pso._push(ctx)
     ctx.set_batch_form(a.form)
+    if a.pacing != "lockstep":  # (the default is not set: an older build under A/B lacks the call)
+        ctx.set_batch_pacing(a.pacing)
     nb = min(3, max(counts))  # lanes of the check
     yard = wave_yardstick_context(hpe, pso, ctx.batch_wave_wpp(P, nb)) if a.form == "wave" else None
     alone = yard.ctx if yard else None
@@ -285,8 +359,16 @@ def main():
 
         hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0") if a.raw else None
 
+        tracked = [B * n]
+        subs = {k: torch.zeros((k, 27), dtype=torch.float64, device="cuda:0")
+                for k in range(1, B + 1)} if a.drop and a.pacing == "lockstep" else None
+
         def run():
-            if a.live:
+            if a.live and a.drop and a.pacing == "free":
+                tracked[0] = run_live_paced(ctx, st, host[:B], n, a.drop)
+            elif a.live and a.drop:
+                tracked[0] = run_live_rebegin(ctx, torch, st, subs, host[:B], n, a.drop)
+            elif a.live:
                 run_live(ctx, st, host[:B], n)
             elif a.raw:
                 ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG,
@@ -320,7 +402,7 @@ def main():
             times.append(time.perf_counter() - t0)
         el = float(np.median(times[1:]))
         line = {"lanes": B, "frames_per_lane": n, "reps": a.reps,
-                "aggregate_tracked_fps": B * n / el,
+                "aggregate_tracked_fps": tracked[0] / el,
                 "ms_per_batched_frame": el / n * 1e3,
                 "workload": "256 p x 30 gen, refine on, N = 250, "
                             + ("host frames, one per lane and call, read from pinned buffers in "
@@ -330,6 +412,11 @@ def main():
                             + ", one context, seeds 0..B-1"}
         if a.live:
             line["mode"] = "live"
+            line["pacing"] = a.pacing
+        if a.drop:
+            line["drop"] = a.drop
+            line["tracked_frames"] = tracked[0]
+            line["lane_set_changes"] = "idle lanes" if a.pacing == "free" else "end and begin again"
         if a.form == "wave":
             line["form"] = "wave"
             line["wpp"] = ctx.batch_wave_wpp(P, B)
