@@ -105,6 +105,22 @@ struct OptState {  // pso_optimise buffers, rebuilt when P / G / seed / cloud bo
     unsigned *ctr = nullptr;
 };
 
+// The lane forms' state (hpe_pso_optimise_batch, hpe_batch_pipeline_optimise): per lane one
+// arena {x, v, pb, pc, gbest, trace, ctr}, `stride` bytes apart (off[]: the arrays within an
+// arena, each on a 128-byte line of its own), the shared normals and bounds, and the slot
+// call's descriptor table.  Grown, never shrunk; rebuilt when P or the seed changes or G
+// outgrows the trace.  No graph holds any of it: the calls launch directly.
+struct OptLanes {
+    int P = 0, G = -1, lanes = 0;
+    uint64_t seed = 0;
+    char *arena = nullptr;
+    size_t stride = 0, off[7] = {0};
+    double *normals = nullptr, *bounds = nullptr;
+    double bounds_h[3 * HPE_DOF] = {0};  // what `bounds` holds
+    bool bounds_set = false;
+    DevObs *d_obs = nullptr;  // [HPE_BATCH_MAX]
+};
+
 // What a captured tracking graph depends on besides the context's seed and epoch: one key for
 // the tracking calls, a field a call does not use left zero.  A launch decision that is not
 // in the key replays the wrong kernels (a cached chunk of 250-point frames on 400-point ones).
@@ -418,6 +434,7 @@ struct hpe_ctx {
     uint64_t seed = 1000;
     Swarm sw;
     OptState opt;
+    OptLanes optl;
     // kernel timing: hipExtLaunchKernel start/stop events (dispatch-packet timestamps,
     // the same interval rocprofv3 --kernel-trace reports), one pool per kernel
     bool prof = false;
@@ -567,6 +584,16 @@ static void free_opt(OptState &s) {
     s.P = 0;
     s.G = -1;
     s.n_cap = 0;
+}
+
+static void free_opt_lanes(OptLanes &s) {
+    dfree(s.arena);
+    dfree(s.normals);
+    dfree(s.bounds);
+    s.P = 0;
+    s.G = -1;
+    s.lanes = 0;
+    s.bounds_set = false;
 }
 
 // The lane arenas of a batch call (Swarm::arena): grown, never shrunk, with the epoch bumped
@@ -1164,6 +1191,8 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->ss.d_script_k);
     free_swarm(c->sw);
     free_opt(c->opt);
+    free_opt_lanes(c->optl);
+    dfree(c->optl.d_obs);
     dfree(c->d_hand);
     dfree(c->d_lane_hands);
     dfree(c->d_theta);
@@ -3245,6 +3274,172 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     lv.pending = given;
     lv.cur = next ? nxt : -1;
     return HPE_OK;
+}
+
+// ---------------------------------------------------------------- lane initialisation
+// The lane forms' arenas for swarms of P particles, G generations and `lanes` lanes, and the
+// bounds the context holds now.  Nothing a captured graph uses: no epoch bump.
+static int ensure_opt_lanes(hpe_ctx *c, int P, int G, int lanes) {
+    OptLanes &s = c->optl;
+    if (!s.d_obs) HIPCHK(c, dalloc(&s.d_obs, HPE_BATCH_MAX));
+    if (!(s.P == P && s.G >= G && s.seed == c->seed && s.lanes >= lanes)) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight use the arenas
+        if (lanes < s.lanes) lanes = s.lanes;        // grown, never shrunk
+        if (G < s.G) G = s.G;
+        free_opt_lanes(s);
+        const size_t e = sizeof(double) * (size_t)P * HPE_DOF;
+        const size_t bytes[7] = {e, e, e, sizeof(double) * (size_t)P, sizeof(double) * 28,
+                                 sizeof(double) * (size_t)(G > 0 ? G : 1),
+                                 sizeof(unsigned) * (ARRIVE_SHARDS * 32 + 1)};
+        size_t at = 0;
+        for (int k = 0; k < 7; ++k) {  // every array, the counters included, on lines of its own
+            s.off[k] = at;
+            at += (bytes[k] + 127) & ~(size_t)127;
+        }
+        s.stride = at;
+        HIPCHK(c, dalloc(&s.arena, s.stride * (size_t)lanes));
+        // the counters start at 0 (on the stream: the launches that count follow it there)
+        HIPCHK(c, hipMemsetAsync(s.arena, 0, s.stride * (size_t)lanes, c->stream));
+        HIPCHK(c, dalloc(&s.normals, (size_t)P * HPE_DOF));
+        HIPCHK(c, dalloc(&s.bounds, (size_t)3 * HPE_DOF));
+        std::vector<double> nrm((size_t)P * HPE_DOF);
+        hpe::make_normals(c->seed, P, nrm.data(), ST_OPT_NORMAL);
+        HIPCHK(c, hipMemcpy(s.normals, nrm.data(), e, hipMemcpyHostToDevice));
+        s.P = P;
+        s.G = G;
+        s.lanes = lanes;
+        s.seed = c->seed;
+    }
+    double b[3 * HPE_DOF];
+    std::memcpy(b, c->lb, sizeof(c->lb));
+    std::memcpy(b + HPE_DOF, c->ub, sizeof(c->ub));
+    std::memcpy(b + 2 * HPE_DOF, c->sd, sizeof(c->sd));
+    if (!s.bounds_set || std::memcmp(b, s.bounds_h, sizeof(b))) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight read the old bounds
+        HIPCHK(c, hipMemcpy(s.bounds, b, sizeof(b), hipMemcpyHostToDevice));
+        std::memcpy(s.bounds_h, b, sizeof(b));
+        s.bounds_set = true;
+    }
+    return HPE_OK;
+}
+
+// pso_optimise of the L lanes of `ll` in the same launches, direct and asynchronous: lane b on
+// descriptor obs[b] (at most n_max points each), hand d_lane_hands[b], x0 = d_states + 27 b,
+// which the trailing launch overwrites with {bestp, cost}; its trace to row b of d_trace.  The
+// generation index is a kernel argument and a call runs once per batch, so nothing is captured.
+static int enqueue_opt_lanes(hpe_ctx *c, int P, int G, const DevObs *obs, const OptLaneList &ll,
+                             int L, int n_max, double *d_states, double *d_trace) {
+    const OptLanes &s = c->optl;
+    DevOpt d;
+    d.x = (double *)(s.arena + s.off[0]);
+    d.v = (double *)(s.arena + s.off[1]);
+    d.pb = (double *)(s.arena + s.off[2]);
+    d.pc = (double *)(s.arena + s.off[3]);
+    d.gbest = (double *)(s.arena + s.off[4]);
+    d.trace = (double *)(s.arena + s.off[5]);
+    d.match = nullptr;  // the staged descent keeps matchId in LDS
+    d.ctr = (unsigned *)(s.arena + s.off[6]);
+    d.normals = s.normals;
+    d.bounds = s.bounds;
+    d.seed = c->seed;
+    d.P = P;
+    d.G = G;
+    d.n_cap = 0;
+    d.w = c->omega;
+    d.c1 = c->phip;
+    d.c2 = c->phig;
+    const DevHand *hands = c->d_lane_hands;
+    const unsigned lds = (unsigned)((size_t)n_max * (3 * sizeof(double) + sizeof(int32_t)));
+    const dim3 grid(P, L);
+    hipLaunchKernelGGL(k_opt_init_b, grid, dim3(HPE_NT), 0, c->stream, d, s.stride, ll,
+                       (const double *)d_states, obs, hands);
+    for (int g = 1; g <= G; ++g) {
+        hipLaunchKernelGGL(k_opt_descent_b<true>, grid, dim3(RF_NT), lds, c->stream, d, s.stride, ll, obs,
+                           hands, g);
+        hipLaunchKernelGGL(k_opt_move_b, grid, dim3(HPE_NT), 0, c->stream, d, s.stride, ll, obs,
+                           hands, g);
+    }
+    hipLaunchKernelGGL(k_opt_result_b, dim3(1, L), dim3(64), 0, c->stream, d, s.stride, ll, d_states,
+                       d_trace);
+    HIPCHK(c, hipGetLastError());
+    return HPE_OK;
+}
+
+// What both lane initialisation calls check first (the context is not null).
+static int check_opt_lanes_call(hpe_ctx *c, int P, int B, const double *d_states) {
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!d_states) return fail(c, HPE_E_ARG, "null device states");
+    if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
+    if (int rc = check_P(c, P)) return rc;
+    if (check_hand_lanes(c, B)) return HPE_E_STATE;  // (its message stands)
+    return HPE_OK;
+}
+
+int hpe_pso_optimise_batch(hpe_ctx *c, int P, int B, double *d_states, const int32_t *slots,
+                           double *d_trace) {
+    if (!c) return HPE_E_ARG;
+    if (!slots) return fail(c, HPE_E_ARG, "null slots");
+    int rc = check_opt_lanes_call(c, P, B, d_states);
+    if (rc) return rc;
+    int n_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const int sl = slots[b];
+        if (sl < 0 || sl >= (int)c->slots.size() || !c->slots[sl].valid)
+            return fail(c, HPE_E_ARG, "lane %d: slot %d holds no frame", b, sl);
+        const Slot &s = c->slots[sl];
+        if (s.n_max > RF_STAGE_MAX)
+            return fail(c, HPE_E_ARG, "lane %d: slot %d holds up to %d points, the lane form takes "
+                        "the staged descent (<= %d)", b, sl, s.n_max, RF_STAGE_MAX);
+        if (s.n_max > n_max) n_max = s.n_max;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int G = generations(c);
+    if ((rc = ensure_opt_lanes(c, P, G, B))) return rc;
+    for (int b = 0; b < B; ++b) {  // frames still being prepared on the preprocessing stream
+        Slot &s = c->slots[slots[b]];
+        if (s.dev && s.ready && hipEventQuery(s.ready) != hipSuccess)
+            HIPCHK(c, hipStreamWaitEvent(c->stream, s.ready, 0));
+    }
+    BatchFirst first{};
+    OptLaneList ll{};
+    for (int b = 0; b < B; ++b) {
+        first.slot[b] = slots[b];
+        ll.lane[b] = b;
+    }
+    hipLaunchKernelGGL(k_opt_stage_b, dim3(1, B), dim3(64), 0, c->stream, (const DevObs *)c->d_obs,
+                       first, c->optl.d_obs);
+    if ((rc = enqueue_opt_lanes(c, P, G, c->optl.d_obs, ll, B, n_max, d_states, d_trace))) return rc;
+    return mark_seq_done(c);  // the call is its slots' last reader
+}
+
+int hpe_batch_pipeline_optimise(hpe_ctx *c, int P, int B, double *d_states, uint32_t lanes,
+                                double *d_trace) {
+    if (!c) return HPE_E_ARG;
+    int rc = check_opt_lanes_call(c, P, B, d_states);
+    if (rc) return rc;
+    if (!lanes || (B < 32 && lanes >> B))
+        return fail(c, HPE_E_ARG, "lane mask 0x%x: empty, or a bit at or above B = %d", lanes, B);
+    const hpe_ctx::LiveBatch &lv = c->live;
+    if (lv.cur < 0)
+        return fail(c, HPE_E_STATE, "no live batch: hpe_batch_pipeline_begin not called, or the "
+                    "batch ended");
+    if (B != lv.B)
+        return fail(c, HPE_E_STATE, "%d lanes, the batch began with %d", B, lv.B);
+    if (lanes & ~lv.pending)
+        return fail(c, HPE_E_STATE, "lane mask 0x%x: lanes 0x%x hold no prepared frame "
+                    "(hpe_batch_pending)", lanes, lanes & ~lv.pending);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int G = generations(c);
+    if ((rc = ensure_opt_lanes(c, P, G, B))) return rc;
+    OptLaneList ll{};
+    int L = 0;
+    for (int b = 0; b < B; ++b)
+        if (lanes >> b & 1) ll.lane[L++] = b;
+    // the current frames' descriptors, as the next hpe_track_batch_pipelined reads them; every
+    // live cloud is bounded by 250 points
+    return enqueue_opt_lanes(c, P, G, c->rb.d_obs + lv.cur * HPE_BATCH_MAX, ll, L, 250, d_states,
+                             d_trace);
 }
 
 int hpe_profile_enable(hpe_ctx *c, int on) {

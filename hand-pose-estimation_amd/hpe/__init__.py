@@ -249,6 +249,37 @@ class Context:
         self.check(self.lib.hpe_batch_pending(self._h, C.byref(m)))
         return m.value
 
+    def pso_optimise_batch(self, num_p, d_states_ptr, slots, d_trace_ptr=None):
+        """pso_optimise of B = len(slots) lanes in the same launches (hpe_pso_optimise_batch):
+        lane b is select_frame(slots[b]) + hpe_pso_optimise from x0 = d_states_ptr + 27*8 b, bit
+        for bit, on a context created with lane b's hand (set_batch_hands).  d_states_ptr: B x 27
+        device doubles {x0 -> bestp, cost}; d_trace_ptr (device, optional): B x (maxiter-1) gbest
+        costs.  Asynchronous on the context stream."""
+        sl = [int(s) for s in slots]
+        if not 1 <= len(sl) <= _lib.BATCH_MAX:
+            raise ValueError(f"pso_optimise_batch takes 1..{_lib.BATCH_MAX} lanes, got {len(sl)}")
+        if not d_states_ptr:
+            raise ValueError("pso_optimise_batch needs the device states")
+        arr = (C.c_int32 * len(sl))(*sl)
+        self.check(self.lib.hpe_pso_optimise_batch(
+            self._h, int(num_p), len(sl), C.c_void_p(d_states_ptr), arr,
+            C.c_void_p(d_trace_ptr) if d_trace_ptr else None))
+
+    def batch_pipeline_optimise(self, num_p, d_states_ptr, lanes=None, d_trace_ptr=None):
+        """The same on the live batch's current prepared frames, through the lanes' windows and
+        hands (hpe_batch_pipeline_optimise).  lanes: bit b set = lane b is optimised, the other
+        lanes' rows stay untouched; None: every lane in lockstep, batch_pending() under the "free"
+        pacing.  Changes nothing of the live batch itself.  Asynchronous on the context stream."""
+        if not d_states_ptr:
+            raise ValueError("batch_pipeline_optimise needs the device states")
+        B = getattr(self, "_live_lanes", 0) or 1  # (1 without a begin: the library reports it)
+        if lanes is None:
+            free = getattr(self, "_pacing", _lib.PACING_LOCKSTEP) == _lib.PACING_FREE
+            lanes = self.batch_pending() if free else (1 << B) - 1
+        self.check(self.lib.hpe_batch_pipeline_optimise(
+            self._h, int(num_p), B, C.c_void_p(d_states_ptr), int(lanes),
+            C.c_void_p(d_trace_ptr) if d_trace_ptr else None))
+
     def set_batch_form(self, form):
         """The form of pso_evolve in track_batch, track_raw_batch and the live batch
         (hpe_set_batch_form): "auto" / 0 (default: a workgroup per particle, num_p in the wave

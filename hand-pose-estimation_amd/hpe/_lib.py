@@ -86,6 +86,10 @@ SIGNATURES = {
                                             C.c_double, C.POINTER(Window)]),
     "hpe_set_batch_pacing": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_batch_pending": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "hpe_pso_optimise_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, ip,
+                                         C.c_void_p]),
+    "hpe_batch_pipeline_optimise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_uint32, C.c_void_p]),
     "hpe_build_spheres":(C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),

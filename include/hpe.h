@@ -575,6 +575,50 @@ int hpe_lane_window_from_pose(hpe_ctx *ctx, int lane, const double theta[26], do
 int hpe_set_batch_pacing(hpe_ctx *ctx, int mode);
 int hpe_batch_pending(hpe_ctx *ctx, uint32_t *mask_out);
 
+/* Lane initialisation: the first pose of every lane of a batch, by pso_optimise in the SAME
+ * launches (grid num_p x lanes; 2 (maxiter-1) + 3 launches per call whatever B is).
+ *
+ * hpe_pso_optimise_batch: B lanes on stored slots.  Lane b is
+ *   hpe_select_frame(ctx, slots[b]); hpe_pso_optimise(ctx, x0 = d_states[27 b ..], num_p, ...)
+ * bit for bit on a context created with lane b's hand (hpe_set_batch_hands; the context's own
+ * hand while none are set) under the same seed and PSO parameters: bestp, cost and the gbest
+ * trace.  d_states: device, B x 27 {x0 -> bestp, cost}.  slots: host, B entries (copied before
+ * return; lanes may share a slot).  d_trace (device, optional): B x (maxiter-1), row b = lane b's
+ * gbest cost after each generation.  Asynchronous on hpe_stream(ctx): x0 is read and the result
+ * written on the device, there is no host synchronisation, and the call waits on the stream for
+ * slots still being prepared (hpe_prepare_frame), as hpe_track_batch_dev does.  With maxiter <= 1
+ * (no generation) the result is the initial swarm's best, as in the single call.  The selected
+ * frame stays as it was; hpe_pso_trace and hpe_refine_eval_count are not touched; a later
+ * hpe_prepare_frame waits for the call.
+ *
+ * hpe_batch_pipeline_optimise: the same on a live batch's CURRENT prepared frames -- the
+ * descriptors of the buffer parity the next hpe_track_batch_pipelined tracks -- through the
+ * lanes' windows (the frames are the masked ones) and hands.  lanes: bit b set = lane b is
+ * optimised; the other lanes' rows of d_states (and of d_trace) are left bit for bit untouched,
+ * and no workgroup is launched for them.  It changes nothing of the live batch's own state
+ * (parity, pending mask, frame numbers, pinned buffers): the tracking call that follows reads the
+ * optimised rows as its x0.  The use: frame 0 of a rig, a lane that joins late under
+ * HPE_PACING_FREE, a lane that lost its hand and is re-initialised (the policy is the caller's).
+ *
+ * Refused, never run another way, and a refusal changes nothing: B outside 1..HPE_BATCH_MAX, null
+ * d_states or slots, a slot that holds no frame or more than 2048 cloud points (the lane form is
+ * the staged descent), lanes == 0 or a bit at or above B -- HPE_E_ARG; num_p outside 1..8192 --
+ * HPE_E_ARG; hpe_set_pso_params not called, lane hands set for another B, no live batch or a B
+ * other than the begin's, a selected lane that holds no prepared frame (not in hpe_batch_pending)
+ * -- HPE_E_STATE.
+ * When to use it: whenever more than one lane needs a first pose, or a lane needs its own hand or
+ * its live frame.  Measured on one MI355X at num_p = 32, maxiter = 200, 250-point frames
+ * (DESIGN.md §4.7 "Lane initialisation"): one call for 2 / 4 / 8 / 16 lanes takes 64.7 / 67.9 /
+ * 70.9 / 122.1 ms against 61.2 ms per lane of B consecutive hpe_pso_optimise calls (1.9x, 3.6x,
+ * 7.0x, 8.1x): a lane fills 32 of the 256 CUs, so up to 8 lanes cost about one lane's time and 16
+ * lanes two rounds.  At ONE lane it is 0.2-0.3 % slower than hpe_pso_optimise (two small launches
+ * more): there it offers only what the single call cannot do -- the lane's hand, a live lane's
+ * frame, no host synchronisation. */
+int hpe_pso_optimise_batch(hpe_ctx *ctx, int num_p, int B, double *d_states,
+                           const int32_t *slots, double *d_trace);
+int hpe_batch_pipeline_optimise(hpe_ctx *ctx, int num_p, int B, double *d_states,
+                                uint32_t lanes, double *d_trace);
+
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through
  * hipExtLaunchKernel with a start/stop event pair (dispatch-packet timestamps: the
