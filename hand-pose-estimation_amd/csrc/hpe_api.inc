@@ -134,6 +134,7 @@ struct GraphKey {
     int win;   // the lane windows' mode (hpe_set_batch_window): other kernels, one more launch
     int hands; // lane hands are set (hpe_set_batch_hands): the lane kernels that index the table
     int pacing; // a live batch's pacing (hpe_set_batch_pacing): FREE takes the idle-aware kernels
+    int report; // lane reports are on (hpe_set_batch_report): one more launch, k_report_b; else 0
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
@@ -141,7 +142,7 @@ struct GraphKey {
         return P == o.P && G == o.G && refine == o.refine && k == o.k && staged == o.staged &&
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
                next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
-               hands == o.hands && pacing == o.pacing && to_cm == o.to_cm &&
+               hands == o.hands && pacing == o.pacing && report == o.report && to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -357,7 +358,24 @@ struct hpe_ctx {
         // them once
         int act_words[HPE_BATCH_MAX] = {};
         bool act_known = false;
+        bool report = false;  // the batch began with lane reports on (it keeps that)
     } live;
+    // lane reports (hpe_set_batch_report): the setting the next begin reads (depth 0: off), and
+    // what the rings hold -- the depth and lane count of the last batch begun with reports on
+    // (ring_depth 0: nothing to read), per lane the reports enqueued since that begin.  The ring
+    // (pinned, mapped, coherent, like h_done), the lanes' device words and the parameters are
+    // allocated once, at full size, by the first set that turns reports on: their addresses, all
+    // the graphs hold, never change, and the depth is read from d_par.
+    struct Report {
+        int depth = 0;
+        hpe_report_watch watch = {HUGE_VAL, 0, 0};
+        int ring_depth = 0, ring_B = 0;
+        unsigned long long enq[HPE_BATCH_MAX] = {};
+        char *h_ring = nullptr, *h_ring_dev = nullptr;
+        unsigned long long *d_lane_seq = nullptr;  // [HPE_BATCH_MAX]
+        int *d_streak = nullptr;                   // [HPE_BATCH_MAX]
+        RepPar *d_par = nullptr;
+    } rep;
     // lane windows (hpe_set_batch_window): the mode, and what the next raw batch call or live
     // begin writes to the device -- init into both parities of the window table d_tab (next to
     // rb.d_tab, allocated with it), the margins and the call's focal into d_par -- after the
@@ -1234,6 +1252,10 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->live.d_seq);
     dfree(c->live.d_act);
     if (c->live.h_done) (void)hipHostFree(c->live.h_done);
+    if (c->rep.h_ring) (void)hipHostFree(c->rep.h_ring);
+    dfree(c->rep.d_lane_seq);
+    dfree(c->rep.d_streak);
+    dfree(c->rep.d_par);
     dfree(c->d_raw);
     dfree(c->d_tmp);
     dfree(c->d_ctb);
@@ -3137,6 +3159,160 @@ static void write_lane_act(hpe_ctx *c, int B, uint32_t track, uint32_t prep) {
     lv.act_known = true;
 }
 
+// ---------------------------------------------------------------- lane reports
+static const size_t REP_LANE_BYTES = (size_t)HPE_REP_SLOT * HPE_REP_DEPTH_MAX;
+
+size_t hpe_lane_report_size(void) { return sizeof(hpe_lane_report); }
+
+int hpe_set_batch_report(hpe_ctx *c, int depth, const hpe_report_watch *watch) {
+    if (!c) return HPE_E_ARG;
+    if (depth != 0 && (depth < 2 || depth > HPE_REP_DEPTH_MAX))
+        return fail(c, HPE_E_ARG, "report depth %d is neither 0 nor in [2, %d]", depth,
+                    HPE_REP_DEPTH_MAX);
+    const hpe_report_watch w = watch ? *watch : hpe_report_watch{HUGE_VAL, 0, 0};
+    if (w.streak < 0 || w.n_min < 0)
+        return fail(c, HPE_E_ARG, "report watch: streak %d or n_min %d is negative", w.streak, w.n_min);
+    hpe_ctx::Report &r = c->rep;
+    const bool same = depth == r.depth && std::memcmp(&w.cost_max, &r.watch.cost_max, sizeof(double)) == 0 &&
+                      w.n_min == r.watch.n_min && w.streak == r.watch.streak;
+    // read at the begin: a live batch keeps the reports it began with (hpe_set_batch_form's rule)
+    if (c->live.cur >= 0 && !same)
+        return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the reports it began "
+                    "with (end it first)");
+    if (depth && !r.d_par) {  // once, at full size: never inside a capture, never moved
+        HIPCHK(c, hipSetDevice(c->device));
+        if (!r.h_ring) {
+            HIPCHK(c, hipHostMalloc((void **)&r.h_ring, REP_LANE_BYTES * HPE_BATCH_MAX,
+                                    hipHostMallocMapped | hipHostMallocCoherent));
+            HIPCHK(c, hipHostGetDevicePointer((void **)&r.h_ring_dev, r.h_ring, 0));
+            std::memset(r.h_ring, 0, REP_LANE_BYTES * HPE_BATCH_MAX);
+        }
+        if (!r.d_lane_seq) HIPCHK(c, dalloc(&r.d_lane_seq, HPE_BATCH_MAX));
+        if (!r.d_streak) HIPCHK(c, dalloc(&r.d_streak, HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&r.d_par, 1));  // the last: a set that failed half way is made up for
+    }
+    r.depth = depth;  // no epoch bump: the live graphs are keyed by it (GraphKey::report)
+    r.watch = w;
+    return HPE_OK;
+}
+
+// The begin's part (the stream drained): with reports on, every lane's seq and streak to 0, the
+// rings cleared, the watch rule, depth and focal to the device; off: nothing left to read.
+static int begin_reports(hpe_ctx *c, int B, double focal) {
+    hpe_ctx::Report &r = c->rep;
+    c->live.report = r.depth != 0;
+    r.ring_depth = 0;
+    if (!r.depth) return HPE_OK;
+    const RepPar par{r.watch.cost_max, focal, r.watch.n_min, r.watch.streak, r.depth, 0};
+    HIPCHK(c, hipMemcpy(r.d_par, &par, sizeof(par), hipMemcpyHostToDevice));
+    // (on the stream, as the frame counter is zeroed: the begin synchronises it before it returns)
+    HIPCHK(c, hipMemsetAsync(r.d_lane_seq, 0, sizeof(unsigned long long) * HPE_BATCH_MAX, c->stream));
+    HIPCHK(c, hipMemsetAsync(r.d_streak, 0, sizeof(int) * HPE_BATCH_MAX, c->stream));
+    std::memset(r.h_ring, 0, REP_LANE_BYTES * HPE_BATCH_MAX);
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+    std::memset(r.enq, 0, sizeof(r.enq));
+    r.ring_depth = r.depth;
+    r.ring_B = B;
+    return HPE_OK;
+}
+
+// The report launch of B lanes, after a frame's final launch (TRACK: act as the frame's kernels
+// take it, every lane selected) or after a lane initialisation's last launch (INIT: `sel`), on
+// the preparation records of buffer parity `parity`: the frames just tracked, or held prepared.
+static int enqueue_report(hpe_ctx *c, int B, const double *d_states, int parity, const int *act,
+                          unsigned sel, int kind) {
+    const hpe_ctx::Report &r = c->rep;
+    const RepDev rd{(unsigned long long *)r.h_ring_dev, r.d_par, r.d_lane_seq, r.d_streak};
+    hipLaunchKernelGGL(k_report_b, dim3(B), dim3(64), 0, c->stream, d_states,
+                       (const DevHand *)c->d_lane_hands,
+                       (const PrepInfo *)c->rb.d_info + parity * HPE_BATCH_MAX,
+                       (const unsigned long long *)c->live.d_seq, rd, act, sel, kind);
+    HIPCHK(c, hipGetLastError());
+    return HPE_OK;
+}
+
+// What the three read calls check first; the lane's ring.
+static int report_ring(hpe_ctx *c, int lane, const void *out, const char **ring) {
+    const hpe_ctx::Report &r = c->rep;
+    if (!out) return fail(c, HPE_E_ARG, "null report");
+    if (!r.ring_depth)
+        return fail(c, HPE_E_STATE, "no batch with lane reports has begun (hpe_set_batch_report)");
+    if (lane < 0 || lane >= r.ring_B)
+        return fail(c, HPE_E_ARG, "lane %d outside the batch's %d lanes", lane, r.ring_B);
+    *ring = r.h_ring + REP_LANE_BYTES * lane;
+    return HPE_OK;
+}
+
+int hpe_batch_report(hpe_ctx *c, int lane, uint64_t seq, hpe_lane_report *out) {
+    if (!c) return HPE_E_ARG;
+    const char *ring = nullptr;
+    if (int rc = report_ring(c, lane, out, &ring)) return rc;
+    if (!seq) {
+        hpe_report::read_newest(ring, c->rep.ring_depth, out);
+        return HPE_OK;
+    }
+    if (!hpe_report::read_seq(ring, c->rep.ring_depth, seq, out))
+        return fail(c, HPE_E_STATE, "lane %d: report %llu is not in the ring (not yet, or no longer)",
+                    lane, (unsigned long long)seq);
+    return HPE_OK;
+}
+
+int hpe_batch_report_wait(hpe_ctx *c, int lane, uint64_t seq, int timeout_ms, hpe_lane_report *out) {
+    if (!c) return HPE_E_ARG;
+    const char *ring = nullptr;
+    if (int rc = report_ring(c, lane, out, &ring)) return rc;
+    const hpe_ctx::Report &r = c->rep;
+    const uint64_t enq = r.enq[lane];
+    if (!seq && !enq) {  // nothing was enqueued for the lane
+        out->seq = 0;
+        return HPE_OK;
+    }
+    if (!seq) seq = enq;
+    if (seq > enq || seq + (uint64_t)r.ring_depth <= enq)
+        return fail(c, HPE_E_STATE, "lane %d: report %llu was not enqueued, or its slot has been "
+                    "enqueued again (%llu reports, depth %d)", lane, (unsigned long long)seq,
+                    (unsigned long long)enq, r.ring_depth);
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned it = 0;; ++it) {
+        if (hpe_report::read_seq(ring, r.ring_depth, seq, out)) return HPE_OK;
+        if ((it & 255) == 255) {
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(timeout_ms > 0 ? timeout_ms : 0))
+                return fail(c, HPE_E_HIP, "lane %d: report %llu did not complete in %d ms", lane,
+                            (unsigned long long)seq, timeout_ms);
+            std::this_thread::yield();
+        }
+    }
+}
+
+int hpe_batch_lost(hpe_ctx *c, uint32_t *mask_out) {
+    if (!c) return HPE_E_ARG;
+    const char *ring = nullptr;
+    if (int rc = report_ring(c, 0, mask_out, &ring)) return rc;
+    uint32_t m = 0;
+    hpe_lane_report rep;
+    for (int b = 0; b < c->rep.ring_B; ++b)
+        if (hpe_report::read_newest(ring + REP_LANE_BYTES * b, c->rep.ring_depth, &rep) &&
+            (rep.flags & HPE_REPORT_F_LOST))
+            m |= 1u << b;
+    *mask_out = m;
+    return HPE_OK;
+}
+
+int hpe_lane_joints_dev(hpe_ctx *c, int B, int n, const double *d_hist, double focal,
+                        double *d_joints, double *d_px) {
+    if (!c) return HPE_E_ARG;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (n < 1) return fail(c, HPE_E_ARG, "%d history rows per lane", n);
+    if (!d_hist || !d_joints) return fail(c, HPE_E_ARG, "null history or joints");
+    if (d_px && !(focal > 0)) return fail(c, HPE_E_ARG, "focal %g is not positive", focal);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_lane_joints_b, dim3(n, B), dim3(64), 0, c->stream, d_hist,
+                       (const DevHand *)c->d_lane_hands, focal, d_joints, d_px);
+    HIPCHK(c, hipGetLastError());
+    return HPE_OK;
+}
+
 int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, int to_cm,
                              int downsample, double focal) {
     if (!c) return HPE_E_ARG;
@@ -3176,6 +3352,7 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     __atomic_store_n(lv.h_done, 0ull, __ATOMIC_RELEASE);
     lv.enq = 0;
     lv.used_seq[0] = lv.used_seq[1] = 0;
+    if ((rc = begin_reports(c, B, focal))) return rc;
     // frame 0 of every lane: into its pinned buffer of parity 0, prepared from there
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
     for (int b = 0; b < B; ++b)
@@ -3266,9 +3443,17 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
         write_lane_act(c, B, lv.pending, given);
         io.act = lv.d_act;
     }
-    if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_LIVE_BATCH], key,
-                          [&] { return track_lane_frame(c, P, refine, B, d_states, io); })))
+    key.report = lv.report ? 1 : 0;  // ... nor whether reports are on (never their depth or watch)
+    // with reports on, k_report_b follows the final launch inside the frame's graph: the lanes
+    // that track in this call, on the buffer parity the final launch used
+    if ((rc = run_graphed(c, c->graphs[hpe_ctx::GC_LIVE_BATCH], key, [&] {
+             if (int erc = track_lane_frame(c, P, refine, B, d_states, io)) return erc;
+             return lv.report ? enqueue_report(c, B, d_states, cur, io.act, all, HPE_REPORT_TRACK)
+                              : HPE_OK;
+         })))
         return rc;
+    if (lv.report)
+        for (int b = 0; b < B; ++b) c->rep.enq[b] += (paced ? lv.pending : all) >> b & 1;
     ++lv.enq;  // this frame's number; lane 0's final workgroup publishes it to h_done
     if (given) lv.used_seq[nxt] = lv.enq;  // its refine launch reads h_raw[nxt]
     lv.pending = given;
@@ -3438,8 +3623,13 @@ int hpe_batch_pipeline_optimise(hpe_ctx *c, int P, int B, double *d_states, uint
         if (lanes >> b & 1) ll.lane[L++] = b;
     // the current frames' descriptors, as the next hpe_track_batch_pipelined reads them; every
     // live cloud is bounded by 250 points
-    return enqueue_opt_lanes(c, P, G, c->rb.d_obs + lv.cur * HPE_BATCH_MAX, ll, L, 250, d_states,
-                             d_trace);
+    const DevObs *obs = c->rb.d_obs + lv.cur * HPE_BATCH_MAX;
+    if ((rc = enqueue_opt_lanes(c, P, G, obs, ll, L, 250, d_states, d_trace))) return rc;
+    if (!lv.report) return HPE_OK;
+    // an INIT report of every selected lane: its new row, n of its prepared frame, the streak zeroed
+    if ((rc = enqueue_report(c, B, d_states, lv.cur, nullptr, lanes, HPE_REPORT_INIT))) return rc;
+    for (int b = 0; b < B; ++b) c->rep.enq[b] += lanes >> b & 1;
+    return HPE_OK;
 }
 
 int hpe_profile_enable(hpe_ctx *c, int on) {

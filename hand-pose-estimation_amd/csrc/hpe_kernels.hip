@@ -16,6 +16,7 @@
 
 #include "hpe_device.hpp"
 #include "hpe_prep.hpp"
+#include "hpe_report.hpp"
 #include "../../include/hpe.h"
 
 // ------------------------------------------------------------------ batch kernels
@@ -1810,6 +1811,164 @@ __global__ __launch_bounds__(64) void k_window_bi(const double *__restrict__ sta
     if (!(act[blockIdx.x] & HPE_ACT_PREP)) return;
     constexpr bool HANDS = true;
 #include "hpe_window_body.inc"
+}
+
+// ------------------------------------------------------------------ lane reports
+// hpe_set_batch_report: what the host needs of a tracked lane, computed and delivered by one wave
+// per lane after the frame's final launch (the kernel boundary is the hand-off: no counter, no
+// spin) -- the state row, the hand's 21 joints under the lane's hand, their pixel positions and
+// the lane's health, into the lane's ring in pinned host memory (hpe_report.hpp: the layout and
+// the host reader).
+//
+// joints_wave: hand_joints and their projection at pose f.th, by one wave.  FK is fk_wave, as
+// k_build runs it, and the 63 values are gathered as k_build gathers them, so jt is
+// hpe_build_spheres' joints_out bit for bit.  Lane j < 21 then projects joint j by the pose
+// rule's projection (window_wave) without the floor and the margins: hand_joints is not negated,
+// so x, y, z are camera coordinates; every product is rounded before its add; a non-finite
+// coordinate or z <= 0 gives NaN for both.  Returns {column, row} of joint l in lanes l < 21.
+struct JointPx {
+    double col, row;
+};
+__device__ __forceinline__ JointPx joints_wave(FkSm &f, const DevHand *__restrict__ H, double focal,
+                                               double *__restrict__ jt) {
+    const int l = threadIdx.x & 63;
+    fk_wave(f, H);
+    __syncthreads();  // (one wave: the joints fk_wave's lanes stored, before other lanes read them)
+    if (l < 63) {  // hand_joints rows: wrist, index..little joints 1-4, thumb 1-4 (k_build)
+        double v;
+        if (l < 3) v = f.th[3 + l];
+        else {
+            const int row = l / 3, c = l % 3, k = (row - 1) / 4, jr = 1 + (row - 1) % 4;
+            const int d = (k < 4) ? k + 1 : 0;
+            v = f.J[d][jr][c];
+        }
+        jt[l] = v;
+    }
+    __syncthreads();
+    const int j = l < 21 ? l : 20;
+    const double x = jt[3 * j], y = jt[3 * j + 1], z = jt[3 * j + 2];
+    const bool ok = isfinite(x) && isfinite(y) && isfinite(z) && z > 0;
+    JointPx p;
+    p.col = ok ? (focal * x + 160.0 * z) / z : __builtin_nan("");
+    p.row = ok ? (focal * y + 120.0 * z) / z : __builtin_nan("");
+    return p;
+}
+// Stage lane hand `src` and the 26 angles of `row` for joints_wave (one wave).
+__device__ __forceinline__ void joints_stage(DevHand &hs, FkSm &f, const DevHand *__restrict__ src,
+                                             const double *__restrict__ row) {
+    const int l = threadIdx.x & 63;
+    for (int q = l; q < (int)(sizeof(DevHand) / 8); q += 64) ((double *)&hs)[q] = gp((const double *)src)[q];
+    if (l < HPE_DOF) f.th[l] = gp(row)[l];
+}
+
+// The reports' device words: the watch rule, the ring depth and the batch's focal (written by
+// the begin, the stream drained), and per lane the report counter and the bad streak.
+struct RepPar {
+    double cost_max, focal;
+    int n_min, streak, depth, pad;
+};
+struct RepDev {
+    unsigned long long *ring;      // [HPE_BATCH_MAX][HPE_REP_DEPTH_MAX] slots (the host ring's device address)
+    const RepPar *par;
+    unsigned long long *lane_seq;  // [HPE_BATCH_MAX]
+    int *streak;                   // [HPE_BATCH_MAX]
+};
+// Grid B, one wave per lane: sibling of k_window_b.  act (null in lockstep): a lane whose
+// HPE_ACT_TRACK bit is clear returns at entry, and so does a lane outside `sel` (a by-value word,
+// as k_lane_act takes its words: the lanes hpe_batch_pipeline_optimise selected; the frame graphs
+// hold the constant all-lanes word) -- it loads and stores nothing else.  The hand table holds
+// the context's hand in every entry while no lane hands are set, so entry `lane` is the lane's
+// hand either way.  info: the preparation's records of the frame just tracked (kind TRACK: the
+// buffer parity the final launch used) or currently prepared (INIT) -- n is its n_full, the points
+// the preparation found before downsampling: the descriptor's own n is 250 for every downsampled
+// frame, an empty one included, and a live batch always downsamples.  frame_no: the batch's frame
+// counter, which a TRACK frame's final launch has already bumped.
+// Publication, at system scope: lane 0 stores begin = seq; release; the payload by plain 8-byte
+// vector stores spread over the wave; the wave waits for its own stores, takes a release fence
+// and waits again (the wait AFTER the fence: the fence's own wait may be dropped); lane 0 stores
+// end = seq.  One wave owns the whole slot, so its own vmcnt covers every payload store.
+__global__ __launch_bounds__(64) void k_report_b(const double *__restrict__ states,
+                                                 const DevHand *__restrict__ hands,
+                                                 const PrepInfo *__restrict__ info,
+                                                 const unsigned long long *__restrict__ frame_no,
+                                                 RepDev rd, const int *__restrict__ act,
+                                                 unsigned sel, int kind) {
+    const int b = blockIdx.x, l = threadIdx.x;
+    if (act && !(act[b] & HPE_ACT_TRACK)) return;
+    if (!(sel >> b & 1)) return;
+    __shared__ DevHand hs;
+    __shared__ FkSm fk;
+    __shared__ double jt[64];
+    const double *__restrict__ const row = states + (size_t)HPE_STATE_N * b;
+    joints_stage(hs, fk, hands + b, row);
+    const double sv = gp(row)[l < HPE_STATE_N ? l : HPE_STATE_N - 1];  // lanes < 27: the state row
+    const RepPar par = *rd.par;
+    const int n = gp(info + b)->n_full;
+    const unsigned long long call = *gp(frame_no);
+    const unsigned long long seq = gp(rd.lane_seq)[b] + 1;
+    const int streak_was = gp(rd.streak)[b];
+    __syncthreads();
+    const JointPx px = joints_wave(fk, &hs, par.focal, jt);
+    const double cost = __shfl(sv, HPE_DOF);
+    const bool nan = __ballot(l < HPE_STATE_N && !isfinite(sv)) != 0ull;
+    const bool suspect = kind == HPE_REPORT_TRACK && (!(cost <= par.cost_max) || n < par.n_min);
+    const int bad = suspect ? streak_was + 1 : 0;
+    const int flags = (nan ? HPE_REPORT_F_NAN : 0) | (n == 0 ? HPE_REPORT_F_EMPTY : 0) |
+                      (suspect ? HPE_REPORT_F_SUSPECT : 0) |
+                      (suspect && par.streak > 0 && bad >= par.streak ? HPE_REPORT_F_LOST : 0);
+    if (l == 0) {
+        rd.lane_seq[b] = seq;
+        rd.streak[b] = bad;
+    }
+    typedef HPE_GAS unsigned long long gu64;
+    typedef HPE_GAS double gf64;
+    gu64 *const slot = (gu64 *)rd.ring + ((size_t)b * HPE_REP_DEPTH_MAX + (size_t)((seq - 1) % (unsigned)par.depth)) *
+                                             (HPE_REP_SLOT / 8);
+    if (l == 0) __hip_atomic_store(slot, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    gu64 *const rep = slot + 1;  // hpe_lane_report: 5 header words, state, joints, px
+    if (l < 5) {
+        const unsigned long long hw = l == 0   ? seq
+                                      : l == 1 ? call
+                                      : l == 2 ? ((unsigned long long)(unsigned)kind << 32) | (unsigned)b
+                                      : l == 3 ? ((unsigned long long)(unsigned)flags << 32) | (unsigned)n
+                                               : (unsigned long long)(unsigned)bad;
+        rep[l] = hw;
+    }
+    if (l < HPE_STATE_N) ((gf64 *)rep)[5 + l] = sv;
+    if (l < 63) ((gf64 *)rep)[5 + HPE_STATE_N + l] = jt[l];
+    if (l < 21) {
+        ((gf64 *)rep)[5 + HPE_STATE_N + 63 + 2 * l] = px.col;
+        ((gf64 *)rep)[5 + HPE_STATE_N + 63 + 2 * l + 1] = px.row;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (l == 0)
+        __hip_atomic_store(slot + 1 + HPE_REP_WORDS, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+static_assert(5 + HPE_STATE_N + 63 + 42 == HPE_REP_WORDS, "the report's words");
+
+// hpe_lane_joints_dev: the same device function over a history, grid (n, B), one wave per row:
+// row b n + f of hist under lane b's hand, to joints[b][f][21][3] and (px non-null) px[b][f][21][2].
+__global__ __launch_bounds__(64) void k_lane_joints_b(const double *__restrict__ hist,
+                                                      const DevHand *__restrict__ hands, double focal,
+                                                      double *__restrict__ joints,
+                                                      double *__restrict__ px) {
+    __shared__ DevHand hs;
+    __shared__ FkSm fk;
+    __shared__ double jt[64];
+    const int l = threadIdx.x;
+    const size_t r = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    joints_stage(hs, fk, hands + blockIdx.y, hist + r * HPE_STATE_N);
+    __syncthreads();
+    const JointPx p = joints_wave(fk, &hs, focal, jt);
+    if (l < 63) joints[r * 63 + l] = jt[l];
+    if (px && l < 21) {
+        px[r * 42 + 2 * l] = p.col;
+        px[r * 42 + 2 * l + 1] = p.row;
+    }
 }
 
 #include "hpe_optimise.hpp"

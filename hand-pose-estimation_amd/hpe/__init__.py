@@ -14,7 +14,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _lib, window
+from . import _lib, report, window
 from ._lib import HpeError, ptr
 
 __all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "scaled_hand",
@@ -248,6 +248,53 @@ class Context:
         m = C.c_uint32(0)
         self.check(self.lib.hpe_batch_pending(self._h, C.byref(m)))
         return m.value
+
+    def set_batch_report(self, depth, watch=None):
+        """Lane reports (hpe_set_batch_report), read at batch_pipeline_begin: depth 0 (default)
+        is off; 2..64 gives every lane a ring of `depth` reports in pinned host memory, written
+        by the device inside every tracked frame's graph -- the lane's state row, its 21 joints
+        under the lane's hand, their pixels (hpe.report.project_joints), n and health flags.
+        watch: None, or (cost_max, n_min, streak) / hpe._lib.ReportWatch -- a tracked frame is
+        SUSPECT iff not cost <= cost_max or n < n_min, the lane LOST after `streak` in a row.
+        A live batch in progress keeps its setting: a different one raises (HPE_E_STATE)."""
+        if watch is not None and not isinstance(watch, _lib.ReportWatch):
+            cost_max, n_min, streak = watch
+            watch = _lib.ReportWatch(float(cost_max), int(n_min), int(streak))
+        self.check(self.lib.hpe_set_batch_report(self._h, int(depth),
+                                                 C.byref(watch) if watch is not None else None))
+
+    def batch_report(self, lane, seq=0, raw=False):
+        """Lane `lane`'s report number seq, or its newest complete one (seq = 0; .seq == 0: none
+        yet), as hpe.report.Report (raw: the hpe._lib.LaneReport).  Never blocks, never touches
+        the stream (hpe_batch_report); a seq not in the ring raises (HPE_E_STATE)."""
+        r = _lib.LaneReport()
+        self.check(self.lib.hpe_batch_report(self._h, int(lane), int(seq), C.byref(r)))
+        return r if raw else report.as_report(r)
+
+    def batch_report_wait(self, lane, seq=0, timeout_ms=2000, raw=False):
+        """Wait, at most timeout_ms, for lane `lane`'s report seq to complete (seq = 0: the last
+        one enqueued for the lane) and return it (hpe_batch_report_wait); no synchronisation of
+        the stream.  Raises on expiry (HPE_E_HIP)."""
+        r = _lib.LaneReport()
+        self.check(self.lib.hpe_batch_report_wait(self._h, int(lane), int(seq), int(timeout_ms),
+                                                  C.byref(r)))
+        return r if raw else report.as_report(r)
+
+    def batch_lost(self) -> int:
+        """Bit b set: lane b's newest report has HPE_REPORT_F_LOST (hpe_batch_lost); the
+        application re-initialises such a lane with batch_pipeline_optimise."""
+        m = C.c_uint32(0)
+        self.check(self.lib.hpe_batch_lost(self._h, C.byref(m)))
+        return m.value
+
+    def lane_joints(self, B, n, d_hist_ptr, d_joints_ptr, d_px_ptr=None, focal=241.42):
+        """The reports' joints and pixels for a resident batch's history (hpe_lane_joints_dev):
+        row b n + f of d_hist (27 doubles) under lane b's hand into d_joints [B][n][21][3] and,
+        if given, d_px [B][n][21][2] -- device pointers.  Asynchronous on the context stream."""
+        self.check(self.lib.hpe_lane_joints_dev(
+            self._h, int(B), int(n), C.c_void_p(d_hist_ptr) if d_hist_ptr else None, float(focal),
+            C.c_void_p(d_joints_ptr) if d_joints_ptr else None,
+            C.c_void_p(d_px_ptr) if d_px_ptr else None))
 
     def pso_optimise_batch(self, num_p, d_states_ptr, slots, d_trace_ptr=None):
         """pso_optimise of B = len(slots) lanes in the same launches (hpe_pso_optimise_batch):

@@ -45,6 +45,23 @@ class Window(C.Structure):
                 ("col_hi", C.c_int32), ("z_lo", C.c_double), ("z_hi", C.c_double)]
 
 
+REPORT_TRACK, REPORT_INIT = 1, 2  # HPE_REPORT_* kinds
+REPORT_F_NAN, REPORT_F_EMPTY, REPORT_F_SUSPECT, REPORT_F_LOST = 1, 2, 4, 8  # HPE_REPORT_F_*
+
+
+class LaneReport(C.Structure):
+    """hpe_lane_report: 1096 bytes, every field naturally aligned."""
+    _fields_ = [("seq", C.c_uint64), ("call", C.c_uint64), ("lane", C.c_int32),
+                ("kind", C.c_int32), ("n", C.c_int32), ("flags", C.c_int32),
+                ("bad_streak", C.c_int32), ("pad", C.c_int32), ("state", C.c_double * 27),
+                ("joints", (C.c_double * 3) * 21), ("px", (C.c_double * 2) * 21)]
+
+
+class ReportWatch(C.Structure):
+    """hpe_report_watch: SUSPECT iff !(cost <= cost_max) || n < n_min; LOST after `streak`."""
+    _fields_ = [("cost_max", C.c_double), ("n_min", C.c_int32), ("streak", C.c_int32)]
+
+
 # name -> (restype, argtypes); the list IS the exported C ABI (tests check it against
 # include/hpe.h)
 SIGNATURES = {
@@ -90,6 +107,14 @@ SIGNATURES = {
                                          C.c_void_p]),
     "hpe_batch_pipeline_optimise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                               C.c_uint32, C.c_void_p]),
+    "hpe_lane_report_size": (C.c_size_t, []),
+    "hpe_set_batch_report": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ReportWatch)]),
+    "hpe_batch_report": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(LaneReport)]),
+    "hpe_batch_report_wait": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int,
+                                        C.POINTER(LaneReport)]),
+    "hpe_batch_lost": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "hpe_lane_joints_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                      C.c_void_p, C.c_void_p]),
     "hpe_build_spheres":(C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),

@@ -24,6 +24,7 @@
 #ifndef HPE_H
 #define HPE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -618,6 +619,75 @@ int hpe_pso_optimise_batch(hpe_ctx *ctx, int num_p, int B, double *d_states,
                            const int32_t *slots, double *d_trace);
 int hpe_batch_pipeline_optimise(hpe_ctx *ctx, int num_p, int B, double *d_states,
                                 uint32_t lanes, double *d_trace);
+
+/* Lane reports: every tracked frame of a live batch's lane, delivered to the host by the device
+ * inside the frame's graph -- no stream synchronisation, no device-to-host copy.
+ *
+ * hpe_set_batch_report(depth, watch): depth 0 (default) is off, and everything runs as without
+ * reports.  depth in 2..64 gives every lane a ring of `depth` slots in pinned, mapped, coherent
+ * host memory; a slot is {begin word, hpe_lane_report, end word} padded to 1152 bytes, and slot
+ * (seq - 1) % depth holds the lane's report number seq.  After the final launch of every
+ * hpe_track_batch_pipelined one more launch (k_report_b, one wave per lane, part of the frame's
+ * graph) writes a TRACK report for every lane that tracked in the call (an idle lane of a
+ * free-paced batch writes nothing); hpe_batch_pipeline_optimise writes an INIT report for each
+ * lane it selected.  A report holds the lane's row of d_states bit for bit, the hand's 21 joints
+ * at that pose under the LANE's hand (rows as hpe_build_spheres' joints_out: wrist, index ..
+ * little joints 1-4, thumb 1-4; camera coordinates, cm), each joint's pixel position
+ *   column = (focal x + 160 z) / z,  row = (focal y + 120 z) / z
+ * (fp64, every product rounded before its add; both NaN when a coordinate is not finite or
+ * z <= 0; hpe.report.project_joints is the host mirror), the frame's point count n -- the points
+ * the preparation found in the frame (through the lane's window) BEFORE downsampling, what
+ * hpe_preprocess_depth returns in n_out with downsample = 0: the tracked cloud itself always
+ * holds 250 points, even of an empty frame -- the batch's frame number and the lane's health flags.
+ *
+ * The watch rule (the thresholds are the caller's; NULL means {+inf, 0, 0}, which never holds):
+ * a TRACK report is SUSPECT iff !(cost <= cost_max) || n < n_min -- a NaN cost is suspect.
+ * bad_streak counts the lane's consecutive SUSPECT TRACK reports (a device word per lane, zeroed
+ * by a healthy report, by an INIT report and by the begin); LOST is set iff streak > 0 &&
+ * bad_streak >= streak.  The library only reports: the application re-initialises a lost lane
+ * with hpe_batch_pipeline_optimise.
+ *
+ * The setting is read at hpe_batch_pipeline_begin, which resets every lane's seq to 0 and clears
+ * the rings; the rings survive the end of a batch and stay readable until the next begin.
+ * Changing the setting while a live batch is in progress is HPE_E_STATE and changes nothing.
+ * Any other depth, or a watch with streak < 0 or n_min < 0: HPE_E_ARG.
+ *
+ * hpe_batch_report never blocks and never touches the stream: seq == 0 asks for the lane's newest
+ * complete report (out->seq == 0: none yet); a specific seq that is not in the ring, not yet or
+ * no longer, is HPE_E_STATE.  hpe_batch_report_wait waits, at most timeout_ms, for that report to
+ * complete; seq == 0 there is the last report enqueued for the lane (out->seq == 0 if none was);
+ * HPE_E_HIP on expiry.  hpe_batch_lost ORs bit b for every lane b whose newest report has
+ * HPE_REPORT_F_LOST.  A lane outside the batch or a null out: HPE_E_ARG; no batch with reports
+ * begun: HPE_E_STATE.
+ *
+ * hpe_lane_joints_dev: the same joints and pixels for the resident batches, from their history:
+ * row b n + f of d_hist (27 doubles) under lane b's hand, into d_joints[b][f][21][3] and, if
+ * d_px is non-null, d_px[b][f][21][2] (device memory).  Asynchronous on hpe_stream(ctx).
+ * HPE_E_ARG: B outside 1..HPE_BATCH_MAX, n < 1, null d_hist or d_joints, focal <= 0 with a
+ * non-null d_px. */
+#define HPE_REPORT_TRACK 1          /* kind: a tracked frame */
+#define HPE_REPORT_INIT  2          /* kind: hpe_batch_pipeline_optimise wrote the lane's row */
+#define HPE_REPORT_F_NAN     1      /* a state entry is not finite */
+#define HPE_REPORT_F_EMPTY   2      /* n == 0 */
+#define HPE_REPORT_F_SUSPECT 4      /* the watch rule held for this frame */
+#define HPE_REPORT_F_LOST    8      /* ... for `streak` consecutive TRACK reports of the lane */
+typedef struct hpe_lane_report {    /* 1096 bytes, every field naturally aligned */
+    uint64_t seq;                   /* this lane's report number since the begin, from 1 */
+    uint64_t call;                  /* the batch's frame number, the one the final launch publishes */
+    int32_t lane, kind, n, flags, bad_streak, pad;
+    double state[27];               /* the lane's row of d_states {bestp, cost}, bit for bit */
+    double joints[21][3];           /* hand_joints rows, as hpe_build_spheres' joints_out */
+    double px[21][2];               /* {column, row} of each joint in the 320x240 image */
+} hpe_lane_report;
+typedef struct { double cost_max; int32_t n_min; int32_t streak; } hpe_report_watch;
+
+size_t hpe_lane_report_size(void);
+int hpe_set_batch_report(hpe_ctx *ctx, int depth, const hpe_report_watch *watch);
+int hpe_batch_report(hpe_ctx *ctx, int lane, uint64_t seq, hpe_lane_report *out);
+int hpe_batch_report_wait(hpe_ctx *ctx, int lane, uint64_t seq, int timeout_ms, hpe_lane_report *out);
+int hpe_batch_lost(hpe_ctx *ctx, uint32_t *mask_out);
+int hpe_lane_joints_dev(hpe_ctx *ctx, int B, int n, const double *d_hist, double focal,
+                        double *d_joints, double *d_px);
 
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through

@@ -38,13 +38,21 @@ lane).  Under --pacing free that lane idles for the following call.  Under --pac
 tool does what a caller has to do without pacing: whenever the set of lanes with a frame changes it
 ends the batch and begins another of just those lanes, their state rows gathered into a dense
 buffer and scattered back.  Both lines count the frames actually tracked ("tracked_frames").
+--report DEPTH (with --live): lane reports on (hpe_set_batch_report), a ring of DEPTH per lane, so
+the line prices the report launch per frame against a run without it.
+--consume sync|report (with --live): the application reads every frame's result -- sync: what it
+does without reports, hpe_sync and a device-to-host copy of the B x 27 states after every call;
+report (needs --report): each lane's newest report after every call, one call behind, never
+synchronising.  "results_consumed" counts the rows / complete reports read.
 Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
                                              [--window off|fixed|follow] [--hands shared|distinct]
                                              [--pacing lockstep|free] [--drop K]
+                                             [--report DEPTH] [--consume sync|report]
                                              [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import sys
@@ -163,12 +171,25 @@ def make_host_lanes(ctx, B, n):
              for th in synth.trajectory(n, b, revert=0.02)] for b in range(B)]
 
 
-def run_live(ctx, st, host, n):
-    """n frames of every lane of host through the live batch, a frame per lane and call."""
+def run_live(ctx, st, host, n, consume=None):
+    """n frames of every lane of host through the live batch, a frame per lane and call.
+    consume "sync": after every call hpe_sync and a device-to-host copy of the B x 27 states (what
+    an application does without reports); "report": after every call each lane's newest report is
+    read, one call behind and without any synchronisation (--report), and the last ones at the
+    end.  Returns the results consumed: the number of state rows or complete reports read."""
+    B, got = len(host), 0
     ctx.batch_pipeline_begin([fr[0] for fr in host])
     for f in range(n):
         ctx.track_batch_pipelined(P, 1, st.data_ptr(),
                                   [fr[f + 1] for fr in host] if f + 1 < n else None)
+        if consume == "sync":
+            ctx.check(ctx.lib.hpe_sync(ctx.h))
+            got += len(st.cpu().numpy())
+        elif consume == "report":
+            got += sum(ctx.batch_report(b, raw=True).seq > 0 for b in range(B))
+    if consume == "report":
+        got += sum(ctx.batch_report_wait(b, 0, 5000, raw=True).seq == n for b in range(B))
+    return got
 
 
 def gives(b, step, K):
@@ -280,7 +301,13 @@ def main():
     ap.add_argument("--hands", choices=("shared", "distinct"), default="shared")
     ap.add_argument("--pacing", choices=("lockstep", "free"), default="lockstep")
     ap.add_argument("--drop", type=int, default=0)
+    ap.add_argument("--report", type=int, default=0, metavar="DEPTH")
+    ap.add_argument("--consume", choices=("sync", "report"), default=None)
     a = ap.parse_args()
+    if (a.report or a.consume) and (not a.live or a.drop):
+        ap.error("--report and --consume need --live without --drop: reports are the live batch's")
+    if a.consume == "report" and not a.report:
+        ap.error("--consume report needs --report DEPTH")
     if (a.pacing != "lockstep" or a.drop) and not a.live:
         ap.error("--pacing and --drop need --live: pacing is the live batch's")
     if a.drop < 0 or a.drop == 1:
@@ -304,6 +331,8 @@ def main():
     ctx.set_batch_form(a.form)
     if a.pacing != "lockstep":  # (the default is not set: an older build under A/B lacks the call)
         ctx.set_batch_pacing(a.pacing)
+    if a.report:  # (likewise)
+        ctx.set_batch_report(a.report)
     nb = min(3, max(counts))  # lanes of the check
     yard = wave_yardstick_context(hpe, pso, ctx.batch_wave_wpp(P, nb)) if a.form == "wave" else None
     alone = yard.ctx if yard else None
@@ -360,6 +389,7 @@ def main():
         hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0") if a.raw else None
 
         tracked = [B * n]
+        consumed = [0]
         subs = {k: torch.zeros((k, 27), dtype=torch.float64, device="cuda:0")
                 for k in range(1, B + 1)} if a.drop and a.pacing == "lockstep" else None
 
@@ -369,7 +399,7 @@ def main():
             elif a.live and a.drop:
                 tracked[0] = run_live_rebegin(ctx, torch, st, subs, host[:B], n, a.drop)
             elif a.live:
-                run_live(ctx, st, host[:B], n)
+                consumed[0] = run_live(ctx, st, host[:B], n, a.consume)
             elif a.raw:
                 ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG,
                                     d_hist_ptr=hist.data_ptr())
@@ -413,6 +443,11 @@ def main():
         if a.live:
             line["mode"] = "live"
             line["pacing"] = a.pacing
+        if a.report:
+            line["report_depth"] = a.report
+        if a.consume:
+            line["consume"] = a.consume
+            line["results_consumed"] = consumed[0]
         if a.drop:
             line["drop"] = a.drop
             line["tracked_frames"] = tracked[0]
@@ -430,6 +465,8 @@ def main():
             line["checked_against_own_hand_contexts"] = checked
         if off is not None:
             line["equals_off"] = bool(np.array_equal(results(), off))
+        # the timed run's results (raw: the histories; else the final states), for an A/B of builds
+        line["results_sha1"] = hashlib.sha1(results().tobytes()).hexdigest()[:16]
         if a.profile:
             st.copy_(x0)
             torch.cuda.synchronize()
