@@ -135,6 +135,8 @@ struct GraphKey {
     int hands; // lane hands are set (hpe_set_batch_hands): the lane kernels that index the table
     int pacing; // a live batch's pacing (hpe_set_batch_pacing): FREE takes the idle-aware kernels
     int report; // lane reports are on (hpe_set_batch_report): one more launch, k_report_b; else 0
+    int u16;    // a live batch of 16-bit frames (hpe_batch_pipeline_begin_u16): the u16 ring
+                // kernels; never its depth unit, which device memory holds
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
@@ -142,7 +144,8 @@ struct GraphKey {
         return P == o.P && G == o.G && refine == o.refine && k == o.k && staged == o.staged &&
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
                next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
-               hands == o.hands && pacing == o.pacing && report == o.report && to_cm == o.to_cm &&
+               hands == o.hands && pacing == o.pacing && report == o.report && u16 == o.u16 &&
+               to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -216,6 +219,9 @@ struct LaneFrameIo {
     // lane pacing (hpe_set_batch_pacing, HPE_PACING_FREE): the lanes' activity words, which the
     // idle-aware kernel forms test at entry (null: lockstep, the plain forms)
     const int *act = nullptr;
+    // lane input: the pinned ring holds 16-bit pixels, in this depth unit (device memory; null:
+    // float frames)
+    const float *unit = nullptr;
 };
 
 }  // namespace
@@ -359,6 +365,14 @@ struct hpe_ctx {
         int act_words[HPE_BATCH_MAX] = {};
         bool act_known = false;
         bool report = false;  // the batch began with lane reports on (it keeps that)
+        // lane input: the batch's frames are 16-bit pixels (it keeps the format it began with)
+        // in a depth unit (mm per count) that the begin writes to d_unit; a u16 frame fills the
+        // first half of the lane's pinned buffer
+        bool u16 = false;
+        float *d_unit = nullptr;
+        size_t frame_bytes() const {
+            return (u16 ? sizeof(uint16_t) : sizeof(float)) * (size_t)HPE_IMG_H * HPE_IMG_W;
+        }
     } live;
     // lane reports (hpe_set_batch_report): the setting the next begin reads (depth 0: off), and
     // what the rings hold -- the depth and lane count of the last batch begun with reports on
@@ -1251,6 +1265,7 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->live.d_tab);
     dfree(c->live.d_seq);
     dfree(c->live.d_act);
+    dfree(c->live.d_unit);
     if (c->live.h_done) (void)hipHostFree(c->live.h_done);
     if (c->rep.h_ring) (void)hipHostFree(c->rep.h_ring);
     dfree(c->rep.d_lane_seq);
@@ -2377,7 +2392,20 @@ static int track_lane_frame_t(hpe_ctx *c, int P, int refine, int B, double *d_st
     const DevObs *obs = io.obs;
     const DevHand *hand = c->d_lane_hands;  // the table: lane b's kernels read entry b
     const dim3 prep_grid(1 + PREP_WG, B);
-    if (io.prep && io.win) {
+    if (io.prep && io.unit) {
+        // 16-bit frames in the ring (lane input): the u16 forms of the two ring kernels below
+        if (io.follow)
+            hipLaunchKernelGGL(k_window_b<HANDS>, dim3(B), dim3(64), 0, c->stream,
+                               (const double *)d_states, hand, (const WinPar *)c->win.d_par, io.win);
+        const bool rigid = !c->refine_exact;
+        launch(c, HPE_PROF_REFINE,
+               io.win ? (rigid ? k_refine_ring_u16<true, HANDS, true, false>
+                               : k_refine_ring_u16<false, HANDS, true, false>)
+                      : (rigid ? k_refine_ring_u16<true, HANDS, false, false>
+                               : k_refine_ring_u16<false, HANDS, false, false>),
+               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
+               io.prep, (const DevWindow *)io.win, (const int *)nullptr, io.unit);
+    } else if (io.prep && io.win) {
         // the windowed forms; FOLLOW: first every lane's window from the pose its state holds
         // now -- this launch's refine workgroup overwrites it -- into the parity being prepared
         if (io.follow)
@@ -2422,7 +2450,18 @@ static int track_lane_frame_paced(hpe_ctx *c, int P, int refine, int B, double *
     const int *act = io.act;
     const dim3 prep_grid(1 + PREP_WG, B);
     const bool rigid = !c->refine_exact;
-    if (io.prep && io.win) {
+    if (io.prep && io.unit) {  // 16-bit frames in the ring (lane input)
+        if (io.follow)
+            hipLaunchKernelGGL(k_window_bi, dim3(B), dim3(64), 0, c->stream, (const double *)d_states,
+                               hand, (const WinPar *)c->win.d_par, io.win, act);
+        launch(c, HPE_PROF_REFINE,
+               io.win ? (rigid ? k_refine_ring_u16<true, true, true, true>
+                               : k_refine_ring_u16<false, true, true, true>)
+                      : (rigid ? k_refine_ring_u16<true, true, false, true>
+                               : k_refine_ring_u16<false, true, false, true>),
+               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
+               io.prep, (const DevWindow *)io.win, act, io.unit);
+    } else if (io.prep && io.win) {
         if (io.follow)
             hipLaunchKernelGGL(k_window_bi, dim3(B), dim3(64), 0, c->stream, (const double *)d_states,
                                hand, (const WinPar *)c->win.d_par, io.win, act);
@@ -3106,6 +3145,7 @@ static int ensure_live_batch(hpe_ctx *c, int B) {
         HIPCHK(c, dalloc(&lv.d_seq, 1));
         HIPCHK(c, dalloc(&lv.d_act, HPE_BATCH_MAX));  // the lanes' activity words (lane pacing)
         HIPCHK(c, hipMemset(lv.d_act, 0, sizeof(int) * HPE_BATCH_MAX));
+        HIPCHK(c, dalloc(&lv.d_unit, 1));  // a u16 batch's depth unit (lane input)
         HIPCHK(c, hipHostMalloc((void **)&lv.h_done, sizeof(unsigned long long),
                                 hipHostMallocMapped | hipHostMallocCoherent));
         HIPCHK(c, hipHostGetDevicePointer((void **)&lv.h_done_dev, lv.h_done, 0));
@@ -3129,14 +3169,15 @@ static int ensure_live_batch(hpe_ctx *c, int B) {
     return HPE_OK;
 }
 
+// (The frame-array helpers take the lanes' frames as untyped pointers: float or 16-bit frames.)
 // Every entry of a lane frame array non-null: 1; every entry null: 0; mixed: -1.
-static int lane_frames(const float *const *frames, int B) {
+static int lane_frames(const void *const *frames, int B) {
     int set = 0;
     for (int b = 0; b < B; ++b) set += frames[b] != nullptr;
     return set == B ? 1 : set == 0 ? 0 : -1;
 }
 // Bit b: entry b is non-null.
-static uint32_t lane_mask(const float *const *frames, int B) {
+static uint32_t lane_mask(const void *const *frames, int B) {
     uint32_t m = 0;
     for (int b = 0; b < B; ++b) m |= (uint32_t)(frames[b] != nullptr) << b;
     return m;
@@ -3313,9 +3354,10 @@ int hpe_lane_joints_dev(hpe_ctx *c, int B, int n, const double *d_hist, double f
     return HPE_OK;
 }
 
-int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, int to_cm,
-                             int downsample, double focal) {
-    if (!c) return HPE_E_ARG;
+// The begin of a live batch in either frame format: u16 false, float mm frames; true, 16-bit
+// frames of unit_mm each.
+static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool u16, float unit_mm,
+                            int to_cm, int downsample, double focal) {
     if (B < 1 || B > HPE_BATCH_MAX)
         return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
     const bool paced = c->batch_pacing == HPE_PACING_FREE;
@@ -3339,6 +3381,8 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
                         "(a live batch reads its pinned buffers in place)");
     if (int wrc = check_window_lanes(c, B)) return wrc;
     if (int hrc = check_hand_lanes(c, B)) return hrc;
+    if (u16 && !(std::isfinite(unit_mm) && unit_mm > 0))
+        return fail(c, HPE_E_ARG, "depth unit %g mm is not finite and positive", (double)unit_mm);
     HIPCHK(c, hipSetDevice(c->device));
     // the frames of a batch in progress are done with: its pinned buffers are free to refill
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3348,16 +3392,28 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     int rc = ensure_batch_lanes(c);
     if (rc || (rc = ensure_raw_batch(c, B, to_cm, focal)) || (rc = ensure_live_batch(c, B))) return rc;
     if ((rc = write_windows(c, focal, to_cm))) return rc;
+    lv.u16 = u16;
+    // the depth unit, as the windows' parameters: device memory, not the graphs, holds it (the
+    // stream has drained)
+    if (u16) HIPCHK(c, hipMemcpy(lv.d_unit, &unit_mm, sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemsetAsync(lv.d_seq, 0, sizeof(unsigned long long), c->stream));
     __atomic_store_n(lv.h_done, 0ull, __ATOMIC_RELEASE);
     lv.enq = 0;
     lv.used_seq[0] = lv.used_seq[1] = 0;
     if ((rc = begin_reports(c, B, focal))) return rc;
     // frame 0 of every lane: into its pinned buffer of parity 0, prepared from there
-    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
     for (int b = 0; b < B; ++b)
-        if (given >> b & 1) std::memcpy(lv.h_raw[0][b], depth_mm[b], sizeof(float) * npix);
-    if (paced) {  // only the lanes given a frame prepare one; the others start empty
+        if ((given >> b & 1) && depth_mm[b] != lv.h_raw[0][b])
+            std::memcpy(lv.h_raw[0][b], depth_mm[b], lv.frame_bytes());
+    const bool win = c->win.mode != HPE_WINDOW_OFF;
+    if (u16) {
+        if (paced) write_lane_act(c, B, 0, given);
+        hipLaunchKernelGGL(win ? (paced ? k_prepare_ring_u16<true, true> : k_prepare_ring_u16<true, false>)
+                               : (paced ? k_prepare_ring_u16<false, true> : k_prepare_ring_u16<false, false>),
+                           dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream, (const PrepArgs *)lv.d_tab,
+                           (const DevWindow *)(win ? c->win.d_tab : nullptr),
+                           (const int *)(paced ? lv.d_act : nullptr), (const float *)lv.d_unit);
+    } else if (paced) {  // only the lanes given a frame prepare one; the others start empty
         write_lane_act(c, B, 0, given);
         if (c->win.mode != HPE_WINDOW_OFF)
             hipLaunchKernelGGL(k_prepare_ring_wbi, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
@@ -3383,9 +3439,41 @@ int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, in
     return HPE_OK;
 }
 
-int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_states,
-                              const float *const *next_depth_mm) {
+int hpe_batch_pipeline_begin(hpe_ctx *c, int B, const float *const *depth_mm, int to_cm,
+                             int downsample, double focal) {
     if (!c) return HPE_E_ARG;
+    return live_batch_begin(c, B, (const void *const *)depth_mm, false, 1.f, to_cm, downsample, focal);
+}
+
+int hpe_batch_pipeline_begin_u16(hpe_ctx *c, int B, const uint16_t *const *depth, float unit_mm,
+                                 int to_cm, int downsample, double focal) {
+    if (!c) return HPE_E_ARG;
+    return live_batch_begin(c, B, (const void *const *)depth, true, unit_mm, to_cm, downsample, focal);
+}
+
+// Lane `lane`'s pinned buffer of the parity the next track call reads, once the device has read
+// the frame it last held (the track call's own wait, before its copy).
+int hpe_batch_frame_buffer(hpe_ctx *c, int lane, void **buf_out, size_t *bytes_out) {
+    if (!c) return HPE_E_ARG;
+    if (!buf_out) return fail(c, HPE_E_ARG, "null buffer pointer");
+    hpe_ctx::LiveBatch &lv = c->live;
+    if (lv.cur < 0)
+        return fail(c, HPE_E_STATE, "no live batch: hpe_batch_pipeline_begin not called, or the "
+                    "batch ended");
+    if (lane < 0 || lane >= lv.B)
+        return fail(c, HPE_E_ARG, "lane %d outside the batch's %d lanes", lane, lv.B);
+    const int nxt = lv.cur ^ 1;
+    if (lv.used_seq[nxt] && !wait_frame_done(lv.h_done, lv.used_seq[nxt]))
+        return fail(c, HPE_E_HIP, "live batch frame %llu did not complete",
+                    (unsigned long long)lv.used_seq[nxt]);
+    *buf_out = lv.h_raw[nxt][lane];
+    if (bytes_out) *bytes_out = lv.frame_bytes();
+    return HPE_OK;
+}
+
+// The track call of a live batch in either frame format (u16: the entry point's).
+static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                            const void *const *next_depth_mm, bool u16) {
     if (int erc = mw_check_async(c)) return erc;
     if (!c->params) return fail(c, HPE_E_STATE, "hpe_set_pso_params not called");
     int rc = check_P(c, P);
@@ -3404,17 +3492,27 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     if (B != lv.B)
         return fail(c, HPE_E_STATE, "%d lanes, the batch began with %d (end it and begin another)",
                     B, lv.B);
+    if (u16 != lv.u16)
+        return fail(c, HPE_E_STATE, "the batch began with %s frames and keeps that format: this is "
+                    "the track call for %s frames", lv.u16 ? "u16" : "f32", u16 ? "u16" : "f32");
     HIPCHK(c, hipSetDevice(c->device));
     const int cur = lv.cur, nxt = cur ^ 1;
-    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
     const uint32_t all = B < 32 ? (1u << B) - 1 : ~0u;
     const uint32_t given = !next ? 0 : paced ? lane_mask(next_depth_mm, B) : all;
+    // a lane's own pinned buffer as its next frame (hpe_batch_frame_buffer) was filled in place;
+    // a buffer of the other parity holds a current frame: its pointer is from before an earlier call
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; (given >> b & 1) && k < B; ++k)
+            if (next_depth_mm[b] == lv.h_raw[cur][k])
+                return fail(c, HPE_E_ARG, "lane %d: stale frame buffer (lane %d's, which holds its "
+                            "current frame: ask hpe_batch_frame_buffer after every track call)", b, k);
     if (given) {  // the pinned buffers' previous frames (two ago) must have been read
         if (lv.used_seq[nxt] && !wait_frame_done(lv.h_done, lv.used_seq[nxt]))
             return fail(c, HPE_E_HIP, "live batch frame %llu did not complete",
                         (unsigned long long)lv.used_seq[nxt]);
-        for (int b = 0; b < B; ++b)  // only the lanes given a frame
-            if (given >> b & 1) std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], sizeof(float) * npix);
+        for (int b = 0; b < B; ++b)  // only the lanes given a frame, and not one filled in place
+            if ((given >> b & 1) && next_depth_mm[b] != lv.h_raw[nxt][b])
+                std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], lv.frame_bytes());
     }
     const int G = ensure_tracking(c, P, B);  // (the lanes' tables are the begin's)
     if (G < 0) return G;
@@ -3430,6 +3528,7 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     key.to_cm = lv.to_cm;
     key.downsample = 1;
     key.focal = lv.focal;
+    key.u16 = lv.u16 ? 1 : 0;  // ... nor the frame format (never the unit)
     // a frame of a raw batch's on the descriptors of parity cur, with the ring's preparation (the
     // next frames read from the pinned buffers of parity nxt), no history or cursor, and the final
     // launch that publishes the batch's frame number
@@ -3439,6 +3538,7 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     io.follow = c->win.mode == HPE_WINDOW_FOLLOW;
     io.seq = lv.d_seq;
     io.done_host = lv.h_done_dev;
+    if (lv.u16) io.unit = lv.d_unit;
     if (paced) {
         write_lane_act(c, B, lv.pending, given);
         io.act = lv.d_act;
@@ -3459,6 +3559,18 @@ int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_st
     lv.pending = given;
     lv.cur = next ? nxt : -1;
     return HPE_OK;
+}
+
+int hpe_track_batch_pipelined(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                              const float *const *next_depth_mm) {
+    if (!c) return HPE_E_ARG;
+    return live_batch_track(c, P, refine, B, d_states, (const void *const *)next_depth_mm, false);
+}
+
+int hpe_track_batch_pipelined_u16(hpe_ctx *c, int P, int refine, int B, double *d_states,
+                                  const uint16_t *const *next_depth) {
+    if (!c) return HPE_E_ARG;
+    return live_batch_track(c, P, refine, B, d_states, (const void *const *)next_depth, true);
 }
 
 // ---------------------------------------------------------------- lane initialisation

@@ -2,7 +2,8 @@
 // included as text by the whole transform (prep_dt) and by the split one (dt_forward_half,
 // prep_dt_split), so all compile the same statements.  DT_PART selects the piece; names expected
 // in scope: W, H, msk, t, l and
-//   0  mask + first hand row: DT_RAW (the raw frame), optionally DT_HINT (word the band
+//   0  mask + first hand row: DT_RAW(i) (the load of the raw frame's pixel i, of type DT_RAW_T)
+//      and DT_VAL(v) (the raw float a loaded v stands for), optionally DT_HINT (word the band
 //      workgroups wait for) and DT_WIN(pix, v) (the raw value v of pixel pix as the lane's
 //      window leaves it); defines r0.  Every wave of the workgroup; two barriers.
 //   1  forward scan by one wave: r0, DT_FWD (the forward values, written)
@@ -14,19 +15,19 @@
     // one round trip each; the raw frame may sit in pinned host memory, behind PCIe)
     constexpr int NPT = W * H / PREP_NT, B = NPT / 3;  // 150 pixels per thread, 3 batches
     static_assert(W * H % PREP_NT == 0 && NPT % 3 == 0, "whole batches");
-    float va[B], vb[B];
-    auto issue = [&](float (&v)[B], int k0) {
+    DT_RAW_T va[B], vb[B];
+    auto issue = [&](DT_RAW_T (&v)[B], int k0) {
 #pragma unroll
-        for (int q = 0; q < B; ++q) v[q] = DT_RAW[(k0 + q) * PREP_NT + t];
+        for (int q = 0; q < B; ++q) v[q] = DT_RAW((k0 + q) * PREP_NT + t);
     };
-    auto fold = [&](const float (&v)[B], int k0) {
+    auto fold = [&](const DT_RAW_T (&v)[B], int k0) {
 #pragma unroll
         for (int q = 0; q < B; ++q) {
             const int pix = (k0 + q) * PREP_NT + t;
 #ifdef DT_WIN
-            const unsigned long long bm = __ballot(DT_WIN(pix, v[q]) != 0.f);
+            const unsigned long long bm = __ballot(DT_WIN(pix, DT_VAL(v[q])) != 0.f);
 #else
-            const unsigned long long bm = __ballot(v[q] != 0.f);
+            const unsigned long long bm = __ballot(DT_VAL(v[q]) != 0.f);
 #endif
             if ((l & 31) == 0) msk[pix >> 5] = (unsigned)(bm >> (l & 32));
         }

@@ -1813,6 +1813,63 @@ __global__ __launch_bounds__(64) void k_window_bi(const double *__restrict__ sta
 #include "hpe_window_body.inc"
 }
 
+// ------------------------------------------------------------------ lane input
+// hpe_batch_pipeline_begin_u16: the eight ring kernels above on lanes whose pinned buffers hold
+// 16-bit pixels.  The preparation workgroups read them in place, as unsigned 16-bit values, and
+// multiply by the batch's depth unit *unit -- device memory written at the begin, never a
+// captured argument -- so half the bytes cross the host link and no launch is added
+// (PrepArgsU16, hpe_prep.hpp).  One template for each of the two kernels: WIN and PACED select
+// the form mirrored (k_*_ring_b, _wb, _bi, _wbi), whose statements these are; wtab is read under
+// WIN and act under PACED alone (null otherwise).  PACED is built in the HANDS shape only, as
+// the idle-aware forms are.
+__device__ __forceinline__ PrepArgsU16 lane_prep_u16(const PrepArgs *__restrict__ tab,
+                                                     const float *__restrict__ unit) {
+    PrepArgsU16 a;
+    static_cast<PrepArgs &>(a) = tab[blockIdx.y];
+    a.unit = *unit;
+    return a;
+}
+
+template <bool WIN, bool PACED>
+__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_u16(const PrepArgs *__restrict__ tab,
+                                                              const DevWindow *__restrict__ wtab,
+                                                              const int *__restrict__ act,
+                                                              const float *__restrict__ unit) {
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    if (PACED && !(act[blockIdx.y] & HPE_ACT_PREP)) return;
+    DevWindow pw{};
+    if (WIN) pw = wtab[blockIdx.y];
+    prep_workgroup<WIN>(lane_prep_u16(tab, unit), blockIdx.x, lds, nullptr, &pw);
+}
+
+template <bool RIGID, bool HANDS, bool WIN, bool PACED, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_ring_u16(double *__restrict__ states,
+                                                           const DevObs *__restrict__ obs,
+                                                           const DevHand *__restrict__ hands,
+                                                           int *__restrict__ evals_b, int do_refine,
+                                                           const PrepArgs *__restrict__ tab,
+                                                           const DevWindow *__restrict__ wtab,
+                                                           const int *__restrict__ act,
+                                                           const float *__restrict__ unit) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    if (PACED && !(act[blockIdx.y] & (blockIdx.x == 0 ? HPE_ACT_TRACK : HPE_ACT_PREP))) return;
+    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
+    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
+    const DevObs *__restrict__ const og = obs + blockIdx.y;
+    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
+    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
+    PrepArgsU16 pa{};
+    DevWindow pw{};
+    if (blockIdx.x >= 1) {
+        pa = lane_prep_u16(tab, unit);
+        if (WIN) pw = wtab[blockIdx.y];
+    }
+    const DevMw mw{};
+    const DevPick pk{};
+    const PrepSplit ps{};
+#include "hpe_refine_body.inc"
+}
+
 // ------------------------------------------------------------------ lane reports
 // hpe_set_batch_report: what the host needs of a tracked lane, computed and delivered by one wave
 // per lane after the frame's final launch (the kernel boundary is the hand-off: no counter, no

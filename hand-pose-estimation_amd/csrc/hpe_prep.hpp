@@ -57,6 +57,24 @@ struct PrepArgs {
     unsigned long long raw_stride;  // floats per raw frame
 };
 
+// The same for a frame of 16-bit pixels (the live batch's u16 lanes, include/hpe.h): raw names
+// 240x320 unsigned 16-bit values, and pixel value u stands for the raw float (float)u * unit --
+// one fp32 multiply, 0 stays 0 -- on which everything downstream is the float forms' code.  The
+// argument type selects the typed load (raw_load / raw_value below): prep_workgroup, prep_band
+// and prep_dt are templates on it, and the float forms compile as before.
+struct PrepArgsU16 : PrepArgs {
+    float unit;  // the batch's depth unit in mm, read from device memory by the kernel
+};
+__device__ __forceinline__ float raw_load(const PrepArgs &a, int i) { return a.raw[i]; }
+__device__ __forceinline__ float raw_value(const PrepArgs &, float r) { return r; }
+// an unsigned load: values above 32767 are depths like the others
+__device__ __forceinline__ unsigned short raw_load(const PrepArgsU16 &a, int i) {
+    return ((const unsigned short *)a.raw)[i];
+}
+__device__ __forceinline__ float raw_value(const PrepArgsU16 &a, unsigned short u) {
+    return (float)u * a.unit;
+}
+
 // The distance transform split over two launches (resident raw sequences; prep_dt_split).
 // The frame a launch prepares has its forward scan in PrepArgs::dtf already; the scratch is
 // double-buffered by frame parity.
@@ -204,9 +222,10 @@ __device__ __forceinline__ bool arrive_last_sharded(unsigned *ctr, unsigned part
 }
 
 // ---- band workgroup b: rows [30b, 30b + 30).  WIN: the raw values pass the lane's window *wn
-// first (the batch calls' windowed kernels); the other forms compile as before.
-template <bool WIN = false>
-__device__ __forceinline__ void prep_band(const PrepArgs &a, int b, unsigned char *lds,
+// first (the batch calls' windowed kernels); the other forms compile as before.  A: PrepArgs, or
+// PrepArgsU16 for 16-bit pixels -- the same pixel per thread per pass, so the same cloud order.
+template <bool WIN = false, class A = PrepArgs>
+__device__ __forceinline__ void prep_band(const A &a, int b, unsigned char *lds,
                                           const DevWindow *wn = nullptr) {
     constexpr int W = HPE_IMG_W, NWV = PREP_NT / 64;
     int *wcnt = (int *)(lds + PREP_CH * 8 + 64), *hcnt = wcnt + NWV;
@@ -226,15 +245,16 @@ __device__ __forceinline__ void prep_band(const PrepArgs &a, int b, unsigned cha
     // the band's raw pixels, all loads in flight at once (unconditional, clamped): one
     // round trip, also when the raw frame is read from pinned host memory over PCIe
     constexpr int NPASS = (PREP_BAND_PIX + PREP_NT - 1) / PREP_NT;
-    float rvs[NPASS];
+    decltype(raw_load(a, 0)) rvs[NPASS];
 #pragma unroll
-    for (int k = 0; k < NPASS; ++k) rvs[k] = a.raw[pbase + min(k * PREP_NT + t, PREP_BAND_PIX - 1)];
+    for (int k = 0; k < NPASS; ++k) rvs[k] = raw_load(a, pbase + min(k * PREP_NT + t, PREP_BAND_PIX - 1));
 #pragma unroll
     for (int k = 0; k < NPASS; ++k) {
         const int p0 = k * PREP_NT;
         const int q = p0 + t, pix = pbase + q;
         const bool in = q < PREP_BAND_PIX;
-        const float rv = WIN ? win_raw(*wn, pix, rvs[k]) : rvs[k];
+        const float rk = raw_value(a, rvs[k]);
+        const float rv = WIN ? win_raw(*wn, pix, rk) : rk;
         const double Z = a.to_cm ? (double)rv / 10. : (double)rv;
         if (in) a.depth_cm[pix] = Z;
         const bool nz = in && Z != 0;
@@ -360,15 +380,18 @@ __device__ __forceinline__ void prep_merge(const PrepArgs &a, unsigned char *lds
 }
 
 // ---- DT workgroup: mask bits by all waves, the raster scans by wave 0.  WIN: the mask is of
-// the raw values behind the lane's window *wn, the ones the bands read.
-template <bool WIN = false>
-__device__ __forceinline__ void prep_dt(const PrepArgs &a, unsigned char *lds,
+// the raw values behind the lane's window *wn, the ones the bands read (A: as prep_band's).
+template <bool WIN = false, class A = PrepArgs>
+__device__ __forceinline__ void prep_dt(const A &a, unsigned char *lds,
                                         const DevWindow *wn = nullptr) {
     constexpr int W = HPE_IMG_W, H = HPE_IMG_H;
     unsigned *msk = (unsigned *)(lds + PREP_CH * 8 + 64 + 2 * (PREP_NT / 64) * 4);
     float *wmaxp = (float *)(msk + W * H / 32);
     const int t = threadIdx.x, l = t & 63;
-#define DT_RAW a.raw
+    using raw_t = decltype(raw_load(a, 0));
+#define DT_RAW_T raw_t
+#define DT_RAW(i) raw_load(a, i)
+#define DT_VAL(v) raw_value(a, v)
 #define DT_HINT &a.ctr[2]
 #define DT_FWD a.dtf
 #define DT_OUT a.dt
@@ -387,7 +410,9 @@ __device__ __forceinline__ void prep_dt(const PrepArgs &a, unsigned char *lds,
     __syncthreads();
     if (t == 0) a.info->dtmax = *wmaxp;
 }
+#undef DT_RAW_T
 #undef DT_RAW
+#undef DT_VAL
 #undef DT_HINT
 #undef DT_FWD
 #undef DT_OUT
@@ -408,7 +433,9 @@ __device__ __forceinline__ void dt_forward_half(const float *raw, int *dtf, int 
     constexpr int W = HPE_IMG_W, H = HPE_IMG_H;
     unsigned *msk = (unsigned *)(lds + PREP_CH * 8 + 64 + 2 * (PREP_NT / 64) * 4);
     const int t = threadIdx.x, l = t & 63;
-#define DT_RAW raw
+#define DT_RAW_T float
+#define DT_RAW(i) raw[i]
+#define DT_VAL(v) (v)
 #define DT_FWD dtf
 #define DT_PART 0
 #include "hpe_dt_parts.inc"
@@ -417,7 +444,9 @@ __device__ __forceinline__ void dt_forward_half(const float *raw, int *dtf, int 
 #include "hpe_dt_parts.inc"
         if (l == 0) *r0_out = r0;
     }
+#undef DT_RAW_T
 #undef DT_RAW
+#undef DT_VAL
 #undef DT_FWD
 }
 
@@ -486,18 +515,21 @@ __device__ __forceinline__ void prep_write_descriptor(const PrepArgs &a) {
 // descriptor.  With a split (ps and ps->dtf_next) the DT workgroup runs prep_dt_split.
 // WIN: the bands and the transform's mask both read the frame through the window *wn (the
 // split transform has no windowed form: the batch calls, which alone have windows, never split).
-template <bool WIN = false>
-__device__ __forceinline__ void prep_workgroup(const PrepArgs &a0, int g, unsigned char *lds,
+// A = PrepArgsU16: a frame of 16-bit pixels in a live batch's pinned ring, which has neither a
+// raw row cursor nor a split.
+template <bool WIN = false, class A = PrepArgs>
+__device__ __forceinline__ void prep_workgroup(const A &a0, int g, unsigned char *lds,
                                                const PrepSplit *ps = nullptr,
                                                const DevWindow *wn = nullptr) {
+    constexpr bool U16 = std::is_same_v<A, PrepArgsU16>;
     int *flag = (int *)(lds + PREP_CH * 8 + 8);
-    PrepArgs a = a0;
-    if (a0.raw_row) a.raw = a0.raw + (size_t)(*a0.raw_row + 1) * a0.raw_stride;
+    A a = a0;
+    if (!U16 && a0.raw_row) a.raw = a0.raw + (size_t)(*a0.raw_row + 1) * a0.raw_stride;
     if (g < PREP_BANDS) {
         prep_band<WIN>(a, g, lds, wn);
         if (!prep_arrive_last(a.ctr, PREP_BANDS, flag)) return;
         prep_merge(a, lds);
-    } else if (!WIN && ps && ps->dtf_next) {
+    } else if (!WIN && !U16 && ps && ps->dtf_next) {
         prep_dt_split(a, *ps, lds);
     } else {
         prep_dt<WIN>(a, lds, wn);

@@ -20,7 +20,7 @@ from ._lib import HpeError, ptr
 __all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "scaled_hand",
            "HpeError",
            "gnd_truth_err",
-           "Context", "preprocess_depth", "reference_bounds", "X0"]
+           "Context", "preprocess_depth", "reference_bounds", "X0", "depth_u16_to_mm"]
 
 IMG_H, IMG_W = 240, 320
 # testmodel.cpp:34-40
@@ -41,6 +41,19 @@ def reference_bounds():
         lb[6 + 4 * k:10 + 4 * k] = (-15, 0, 0, 0)
     sd[0:3], sd[3:6], sd[6:26] = 9.0, 7.0, 9.0
     return ub, lb, sd
+
+
+BATCH_INPUTS = {"f32": np.float32, "u16": np.uint16}  # a live batch's frame formats
+
+
+def depth_u16_to_mm(frame_u16, unit_mm=1.0):
+    """The float mm frame a 16-bit depth frame stands for in a u16 live batch
+    (hpe_batch_pipeline_begin_u16): float32(u) * float32(unit_mm), one fp32 multiply per pixel,
+    0 stays 0.  frame_u16 must be a uint16 array (nothing is converted silently)."""
+    f = np.asarray(frame_u16)
+    if f.dtype != np.uint16:
+        raise TypeError(f"depth_u16_to_mm takes uint16 frames, got {f.dtype}")
+    return f.astype(np.float32) * np.float32(unit_mm)
 
 
 BATCH_FORMS = {"auto": _lib.BATCH_FORM_AUTO, "wave": _lib.BATCH_FORM_WAVE}
@@ -188,10 +201,13 @@ class Context:
             int(to_cm), int(downsample), float(focal), int(frames_per_graph),
             C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
 
-    def _host_frames(self, what, depths):
-        """The lanes' host frames as float32 240x320 arrays and the array of their addresses
+    def _host_frames(self, what, depths, dtype=np.float32):
+        """The lanes' host frames as 240x320 arrays of `dtype` and the array of their addresses
         (the arrays must outlive the call that takes the addresses).  Under the "free" pacing
-        (set_batch_pacing) an entry may be None: a null address, no frame for that lane."""
+        (set_batch_pacing) an entry may be None: a null address, no frame for that lane.
+        float32 frames are converted from whatever is given; uint16 frames must be uint16
+        already.  An array that is contiguous and of the dtype is never copied, so a
+        batch_frame_buffer view reaches the library with the buffer's own address."""
         ds = list(depths)
         if not 1 <= len(ds) <= _lib.BATCH_MAX:
             raise ValueError(f"{what} takes 1..{_lib.BATCH_MAX} lanes, got {len(ds)}")
@@ -199,34 +215,70 @@ class Context:
         if not free and any(d is None for d in ds):
             raise ValueError(f"{what}: a frame for every lane or for none (lanes advance in "
                              "lockstep)")
+        if dtype == np.uint16:
+            for d in ds:
+                if d is not None and np.asarray(d).dtype != np.uint16:
+                    raise TypeError(f"{what}: a u16 batch takes uint16 frames, got "
+                                    f"{np.asarray(d).dtype} (nothing is converted silently)")
+        elif any(d is not None and np.asarray(d).dtype == np.uint16 for d in ds):
+            raise TypeError(f"{what}: a float batch was given uint16 frames (begin the batch "
+                            "with input=\"u16\", or convert with depth_u16_to_mm)")
         fr = [None if d is None else
-              np.ascontiguousarray(d, dtype=np.float32).reshape(IMG_H, IMG_W) for d in ds]
+              np.ascontiguousarray(d, dtype=dtype).reshape(IMG_H, IMG_W) for d in ds]
         return fr, (C.c_void_p * len(fr))(*[None if f is None else f.ctypes.data for f in fr])
 
-    def batch_pipeline_begin(self, depths, to_cm=True, downsample=True, focal=241.42):
+    def batch_pipeline_begin(self, depths, to_cm=True, downsample=True, focal=241.42,
+                             input="f32", unit_mm=1.0):
         """Begin a live batch of B = len(depths) lanes: lane b's first raw frame (host, float
-        mm 240x320) is copied and prepared.  Ends a live batch in progress."""
-        fr, arr = self._host_frames("batch_pipeline_begin", depths)
-        self.check(self.lib.hpe_batch_pipeline_begin(self._h, len(fr), arr, int(to_cm),
-                                                     int(downsample), float(focal)))
+        mm 240x320) is copied and prepared.  Ends a live batch in progress.
+        input="u16": the batch's frames are uint16 arrays of unit_mm millimetres per count
+        (hpe_batch_pipeline_begin_u16), read as such by the device; lane b then equals the
+        float batch on depth_u16_to_mm(frame, unit_mm) bit for bit.  The batch keeps its format:
+        track_batch_pipelined follows it."""
+        if input not in BATCH_INPUTS:
+            raise ValueError(f"batch input {input!r} is not one of {sorted(BATCH_INPUTS)}")
+        fr, arr = self._host_frames("batch_pipeline_begin", depths, BATCH_INPUTS[input])
+        if input == "u16":
+            self.check(self.lib.hpe_batch_pipeline_begin_u16(
+                self._h, len(fr), arr, float(unit_mm), int(to_cm), int(downsample), float(focal)))
+        else:
+            self.check(self.lib.hpe_batch_pipeline_begin(self._h, len(fr), arr, int(to_cm),
+                                                         int(downsample), float(focal)))
         self._live_lanes = len(fr)
+        self._live_input = input
+
+    def batch_frame_buffer(self, lane):
+        """Lane `lane`'s pinned buffer that the next track_batch_pipelined reads, as a 240x320
+        numpy view (float32 or uint16, the batch's format) over the library's memory
+        (hpe_batch_frame_buffer: it first waits until the device has read the frame the buffer
+        last held).  Write the lane's next frame into it and pass the view back as that lane's
+        entry of next_depths: nothing is copied for the lane.  Ask again after every call: the
+        view of an earlier call is refused (HPE_E_ARG, "stale frame buffer")."""
+        buf, n = C.c_void_p(), C.c_size_t(0)
+        self.check(self.lib.hpe_batch_frame_buffer(self._h, int(lane), C.byref(buf), C.byref(n)))
+        dt = BATCH_INPUTS[getattr(self, "_live_input", "f32")]
+        raw = (C.c_char * n.value).from_address(buf.value)
+        return np.frombuffer(raw, dtype=dt).reshape(IMG_H, IMG_W)
 
     def track_batch_pipelined(self, num_p, refine, d_states_ptr, next_depths=None):
         """Track the current frame of every lane of the live batch in the same launches -- lane b
         is track_pipelined(num_p, refine, d_states_ptr + 27*8 b, next_depths[b]) bit for bit --
         and prepare next_depths (one host frame per lane, copied before return) as the following
         frames; None ends the batch.  d_states_ptr: B x 27 device doubles.  Asynchronous on the
-        context stream."""
+        context stream.  The frames are of the begin's format (uint16 arrays for a u16 batch); an
+        entry that is the lane's batch_frame_buffer view was filled in place and is not copied."""
         if not d_states_ptr:
             raise ValueError("track_batch_pipelined needs the device states")
+        inp = getattr(self, "_live_input", "f32")  # the begin's format
         if next_depths is None:
             # the lane count of the begin (1 without one: the library then reports the state)
             B, arr = getattr(self, "_live_lanes", 0) or 1, None
         else:
-            fr, arr = self._host_frames("track_batch_pipelined", next_depths)
+            fr, arr = self._host_frames("track_batch_pipelined", next_depths, BATCH_INPUTS[inp])
             B = len(fr)
-        self.check(self.lib.hpe_track_batch_pipelined(self._h, int(num_p), int(refine), B,
-                                                      C.c_void_p(d_states_ptr), arr))
+        track = (self.lib.hpe_track_batch_pipelined_u16 if inp == "u16"
+                 else self.lib.hpe_track_batch_pipelined)
+        self.check(track(self._h, int(num_p), int(refine), B, C.c_void_p(d_states_ptr), arr))
 
     def set_batch_pacing(self, pacing):
         """Whether the lanes of a live batch advance in lockstep (hpe_set_batch_pacing), read at

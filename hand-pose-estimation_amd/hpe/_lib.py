@@ -91,6 +91,12 @@ SIGNATURES = {
                                            C.c_int, C.c_double]),
     "hpe_track_batch_pipelined": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.POINTER(C.c_void_p)]),
+    "hpe_batch_pipeline_begin_u16": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
+                                               C.c_float, C.c_int, C.c_int, C.c_double]),
+    "hpe_track_batch_pipelined_u16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.POINTER(C.c_void_p)]),
+    "hpe_batch_frame_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_size_t)]),
     "hpe_set_batch_form": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_batch_wave_wpp": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hpe_set_batch_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Window),

@@ -387,6 +387,45 @@ int hpe_batch_pipeline_begin(hpe_ctx *ctx, int B, const float *const *depth_mm,
 int hpe_track_batch_pipelined(hpe_ctx *ctx, int num_p, int refine, int B, double *d_states,
                               const float *const *next_depth_mm);
 
+/* Lane input: what a live batch's frames are, and who fills the lanes' pinned buffers.
+ *
+ * 16-bit frames.  Depth cameras deliver unsigned 16-bit pixels in a depth unit (1 mm, or a
+ * fraction of one).  hpe_batch_pipeline_begin_u16 / hpe_track_batch_pipelined_u16 are the two
+ * calls above on such frames: depth, next_depth are host arrays of B host pointers, each one
+ * 240x320 uint16_t frame, and pixel value u stands for the raw float
+ *   rv = (float)u * unit_mm                       (one fp32 multiply; 0 stays 0, "no depth")
+ * on which everything is the float calls' computation: lane b equals, bit for bit,
+ * hpe_pipeline_begin + hpe_track_pipelined on that stream converted on the host by that rule --
+ * with windows, lane hands, either pacing, either batch form, reports and
+ * hpe_batch_pipeline_optimise.  The library copies 2 bytes per pixel into the lanes' pinned
+ * buffers (the float batch's, a u16 frame fills the first half: one context runs float and u16
+ * batches in turn without reallocating), and the preparation workgroups read the 16-bit pixels in
+ * place, unsigned, and multiply: half the bytes cross the host link, and no launch is added.
+ * unit_mm lives in device memory, written at the begin: two u16 batches of one shape with
+ * different units replay the same graphs.  A batch keeps the format it began with:
+ * hpe_track_batch_pipelined on a u16 batch and hpe_track_batch_pipelined_u16 on a float batch are
+ * HPE_E_STATE.  unit_mm not finite or <= 0 -- HPE_E_ARG; every other refusal is the float calls'.
+ *
+ * Filling a buffer in place.  Between a begin and the end of the batch, in either format,
+ * hpe_batch_frame_buffer returns lane `lane`'s pinned buffer of the parity the NEXT track call
+ * reads, and in *bytes_out (optional) the bytes one frame of the batch's format takes.  Before
+ * it returns it waits, bounded (HPE_E_HIP on expiry), until the device has read the frame that
+ * buffer last held -- the wait the track call makes before its copy.  The caller writes the
+ * lane's next frame there (a camera SDK's receive buffer can be that memory) and passes the same
+ * pointer as that lane's entry of the next frame array: the track call recognises it and copies
+ * nothing for that lane.  Other lanes of the call may pass ordinary arrays (copied as ever), or
+ * NULL under free pacing.  Asking again before the track call returns the same pointer.  After a
+ * track call the pointer names a buffer whose frame is current: passing it again is refused with
+ * HPE_E_ARG ("stale frame buffer") and changes nothing; ask again after every track call.  Frame
+ * 0 is always copied by the begin.  Nothing captured changes: an in-place call replays the
+ * graphs of a copying call.  No live batch -- HPE_E_STATE; a lane outside the batch or a null
+ * buf_out -- HPE_E_ARG. */
+int hpe_batch_pipeline_begin_u16(hpe_ctx *ctx, int B, const uint16_t *const *depth,
+                                 float unit_mm, int to_cm, int downsample, double focal);
+int hpe_track_batch_pipelined_u16(hpe_ctx *ctx, int num_p, int refine, int B, double *d_states,
+                                  const uint16_t *const *next_depth);
+int hpe_batch_frame_buffer(hpe_ctx *ctx, int lane, void **buf_out, size_t *bytes_out);
+
 /* The form of pso_evolve in the three batch calls above (hpe_track_batch_dev,
  * hpe_track_raw_batch_dev, hpe_batch_pipeline_begin / hpe_track_batch_pipelined).
  * HPE_BATCH_FORM_AUTO (default): as described there -- a workgroup per particle, and num_p in the

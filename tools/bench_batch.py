@@ -44,10 +44,20 @@ the line prices the report launch per frame against a run without it.
 does without reports, hpe_sync and a device-to-host copy of the B x 27 states after every call;
 report (needs --report): each lane's newest report after every call, one call behind, never
 synchronising.  "results_consumed" counts the rows / complete reports read.
+--input f32|u16, --unit MM (with --live): the lanes' frame format.  --input u16 or any --unit
+quantises the rendered frames once, np.rint(render / unit) as uint16 (unit default 1 mm); a u16
+run feeds those (hpe_batch_pipeline_begin_u16), the matching f32 run (--input f32 --unit MM)
+hpe.depth_u16_to_mm of the same frames, so both track identical trajectories, do identical device
+work and print the same results_sha1.  Without either option the rendered floats are fed as ever.
+--in-place (with --live): every next frame is written into the lane's pinned buffer
+(hpe_batch_frame_buffer) and that buffer passed back, so the library copies nothing; the write is
+the tool's, standing in for the camera's.  Every --live line names its "input" and "in_place",
+and "host_bytes_copied_per_call", the bytes the library copies into the ring per call.
 Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
                                              [--window off|fixed|follow] [--hands shared|distinct]
                                              [--pacing lockstep|free] [--drop K]
                                              [--report DEPTH] [--consume sync|report]
+                                             [--input f32|u16] [--unit MM] [--in-place]
                                              [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
@@ -171,17 +181,34 @@ def make_host_lanes(ctx, B, n):
              for th in synth.trajectory(n, b, revert=0.02)] for b in range(B)]
 
 
-def run_live(ctx, st, host, n, consume=None):
-    """n frames of every lane of host through the live batch, a frame per lane and call.
+def next_in_place(ctx, host, f):
+    """Frame f of every lane written into the lane's pinned buffer of the next call: the buffers,
+    to be passed back as the call's next frames."""
+    out = []
+    for b, fr in enumerate(host):
+        buf = ctx.batch_frame_buffer(b)
+        buf[:] = fr[f]
+        out.append(buf)
+    return out
+
+
+def run_live(ctx, st, host, n, consume=None, begin_kw=None, in_place=False):
+    """n frames of every lane of host through the live batch, a frame per lane and call
+    (begin_kw: the begin's input format; in_place: next_in_place instead of arrays to copy).
     consume "sync": after every call hpe_sync and a device-to-host copy of the B x 27 states (what
     an application does without reports); "report": after every call each lane's newest report is
     read, one call behind and without any synchronisation (--report), and the last ones at the
     end.  Returns the results consumed: the number of state rows or complete reports read."""
     B, got = len(host), 0
-    ctx.batch_pipeline_begin([fr[0] for fr in host])
+    ctx.batch_pipeline_begin([fr[0] for fr in host], **(begin_kw or {}))
     for f in range(n):
-        ctx.track_batch_pipelined(P, 1, st.data_ptr(),
-                                  [fr[f + 1] for fr in host] if f + 1 < n else None)
+        if f + 1 >= n:
+            nxt = None
+        elif in_place:
+            nxt = next_in_place(ctx, host, f + 1)
+        else:
+            nxt = [fr[f + 1] for fr in host]
+        ctx.track_batch_pipelined(P, 1, st.data_ptr(), nxt)
         if consume == "sync":
             ctx.check(ctx.lib.hpe_sync(ctx.h))
             got += len(st.cpu().numpy())
@@ -248,14 +275,23 @@ def run_live_rebegin(ctx, torch, st, subs, host, n, K):
     return sum(took)
 
 
-def check_live_against_alone(ctx, torch, x0, host, n=6, alone=None):
+def check_live_against_alone(ctx, torch, x0, host, n=6, alone=None, feed=None, begin_kw=None,
+                             in_place=False):
+    """host: the lanes' float frames, which the lanes alone track; feed: what the batch is given
+    (default: host; the u16 frames that host converts, for a u16 batch)."""
     B = len(host)
+    feed = host if feed is None else feed
     st = start_states(torch, x0, B)
     hist = []
-    ctx.batch_pipeline_begin([fr[0] for fr in host])
+    ctx.batch_pipeline_begin([fr[0] for fr in feed], **(begin_kw or {}))
     for f in range(n):
-        ctx.track_batch_pipelined(P, 1, st.data_ptr(),
-                                  [fr[f + 1] for fr in host] if f + 1 < n else None)
+        if f + 1 >= n:
+            nxt = None
+        elif in_place:
+            nxt = next_in_place(ctx, feed, f + 1)
+        else:
+            nxt = [fr[f + 1] for fr in feed]
+        ctx.track_batch_pipelined(P, 1, st.data_ptr(), nxt)
         ctx.check(ctx.lib.hpe_sync(ctx.h))
         hist.append(st.cpu().numpy().copy())
     s1 = torch.empty(27, dtype=torch.float64, device="cuda:0")
@@ -303,7 +339,18 @@ def main():
     ap.add_argument("--drop", type=int, default=0)
     ap.add_argument("--report", type=int, default=0, metavar="DEPTH")
     ap.add_argument("--consume", choices=("sync", "report"), default=None)
+    ap.add_argument("--input", choices=("f32", "u16"), default="f32")
+    ap.add_argument("--unit", type=float, default=None, metavar="MM")
+    ap.add_argument("--in-place", action="store_true")
     a = ap.parse_args()
+    quantised = a.input == "u16" or a.unit is not None
+    if (quantised or a.in_place) and (not a.live or a.drop or a.hands != "shared"):
+        ap.error("--input, --unit and --in-place need --live without --drop and --hands distinct")
+    if a.unit is not None and not (np.isfinite(a.unit) and a.unit > 0):
+        ap.error("--unit MM: finite and > 0")
+    unit = np.float32(1.0 if a.unit is None else a.unit)
+    # (no keyword to the begin unless asked for: an older build under A/B lacks them)
+    begin_kw = {"input": "u16", "unit_mm": float(unit)} if a.input == "u16" else None
     if (a.report or a.consume) and (not a.live or a.drop):
         ap.error("--report and --consume need --live without --drop: reports are the live batch's")
     if a.consume == "report" and not a.report:
@@ -338,7 +385,14 @@ def main():
     alone = yard.ctx if yard else None
     if a.live:
         host = make_host_lanes(ctx, max(counts), n)
-        check_live_against_alone(ctx, torch, hpe.X0, host[:nb], alone=alone)
+        feed = host
+        if quantised:  # once: the u16 frames, and the floats they stand for
+            q16 = [[np.ascontiguousarray(np.rint(f / unit).clip(0, 65535).astype(np.uint16))
+                    for f in fr] for fr in host]
+            host = [[hpe.depth_u16_to_mm(q, unit) for q in fr] for fr in q16]
+            feed = q16 if a.input == "u16" else host
+        check_live_against_alone(ctx, torch, hpe.X0, host[:nb], alone=alone, feed=feed[:nb],
+                                 begin_kw=begin_kw, in_place=a.in_place)
     elif a.raw:
         raws = make_raw_lanes(ctx, torch, max(counts), n)
         check_raw_against_alone(ctx, torch, hpe.X0, raws[:nb], alone=alone)
@@ -399,7 +453,7 @@ def main():
             elif a.live and a.drop:
                 tracked[0] = run_live_rebegin(ctx, torch, st, subs, host[:B], n, a.drop)
             elif a.live:
-                consumed[0] = run_live(ctx, st, host[:B], n, a.consume)
+                consumed[0] = run_live(ctx, st, feed[:B], n, a.consume, begin_kw, a.in_place)
             elif a.raw:
                 ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG,
                                     d_hist_ptr=hist.data_ptr())
@@ -443,6 +497,12 @@ def main():
         if a.live:
             line["mode"] = "live"
             line["pacing"] = a.pacing
+            line["input"] = a.input
+            if quantised:
+                line["unit_mm"] = float(unit)
+            line["in_place"] = a.in_place
+            line["host_bytes_copied_per_call"] = 0 if a.in_place else \
+                B * 240 * 320 * (2 if a.input == "u16" else 4)
         if a.report:
             line["report_depth"] = a.report
         if a.consume:
