@@ -782,19 +782,7 @@ static WaveGenFn wave_gen_kernel(int wpp, bool coop, bool x, bool r16) {
     if (wpp == 2) return coop ? wave_gen_kernel_t<2, true>(x, r16) : wave_gen_kernel_t<2, false>(x, r16);
     return coop ? wave_gen_kernel_t<1, true>(x, r16) : wave_gen_kernel_t<1, false>(x, r16);
 }
-// ... and its lane form's (no exchange)
-typedef void (*WaveLaneGenFn)(DevSwarm, size_t, const DevObs *, const DevHand *, int, double, double,
-                              double);
-template <int WPP, bool COOP, bool HANDS>
-static WaveLaneGenFn wave_lane_gen_kernel_t(bool r16) {
-    return r16 ? k_pso_gen_wb<true, WPP, COOP, HANDS> : k_pso_gen_wb<false, WPP, COOP, HANDS>;
-}
-template <bool HANDS>
-static WaveLaneGenFn wave_lane_gen_kernel(int wpp, bool coop, bool r16) {
-    if (wpp == 2)
-        return coop ? wave_lane_gen_kernel_t<2, true, HANDS>(r16) : wave_lane_gen_kernel_t<2, false, HANDS>(r16);
-    return coop ? wave_lane_gen_kernel_t<1, true, HANDS>(r16) : wave_lane_gen_kernel_t<1, false, HANDS>(r16);
-}
+// (its lane form's: lane_wave_gen_kernel, with the lane frame)
 
 // Waves per particle of the wave form: two while the swarm leaves SIMDs idle at one (the
 // search's latency halves), one beyond (the duplicated FK would cost throughput).
@@ -2328,198 +2316,205 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
     return mark_seq_done(c);
 }
 
-// pso_evolve and cal_cost(bestp) of one frame for B lanes: launch_pso's workgroup form with a
-// lane dimension -- init and the generations on (P, B), the final kernel on (1, B) -- lane b on
-// descriptor io.obs[b], arena b of the swarm (batch_swarm) and cursor io.cur[2 b].  With a frame
-// counter (the live batch), k_pso_final_live_b stands in k_pso_final_b's place.
-// HPE_BATCH_FORM_WAVE: launch_pso's wave form with the lane dimension instead -- init and the
-// generations on (ceil(P / particles per workgroup), B) at pso_wpp(B * P) waves per particle, no
-// inbox counts -- and the same final kernels with same_eval = 0: they evaluate cal_cost(bestp).
-extern "C++" {  // (templates: the two lane launch functions, by whether lane hands are set)
-template <bool HANDS>
-static int launch_pso_lanes(hpe_ctx *c, int P, int B, double *d_states, const LaneFrameIo &io) {
-    const DevSwarm d = batch_swarm(c);
-    const size_t stride = c->sw.stride;
-    const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
-    static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
-    const bool r16 = d.K <= 15, filt = io.filt;
-    const DevHand *hand = c->d_lane_hands;  // the table: lane b's kernels read entry b
-    const int wpp = batch_wave_wpp(c, P, B);
-    if (wpp) {  // one or two waves per particle
-        const int per_wg = PW_WPB / wpp;
-        const dim3 grid((P + per_wg - 1) / per_wg, B);
-        const bool coop = c->fk_coop;
-        auto ki = wpp == 2 ? (coop ? k_pso_init_wb<2, true, HANDS> : k_pso_init_wb<2, false, HANDS>)
-                           : (coop ? k_pso_init_wb<1, true, HANDS> : k_pso_init_wb<1, false, HANDS>);
-        launch(c, HPE_PROF_PSO_INIT, ki, grid, dim3(PW_NT), 0, d, stride, (const double *)d_states,
-               (const DevObs *)io.obs, hand);
-        auto kw = wave_lane_gen_kernel<HANDS>(wpp, coop, r16);
-        for (int g = 1; g <= d.G; ++g)
-            launch(c, HPE_PROF_PSO_GEN, kw, grid, dim3(PW_NT), 0, d, stride, (const DevObs *)io.obs,
-                   hand, g, W1, C1, C2);
-    } else {
-        launch(c, HPE_PROF_PSO_INIT, filt ? k_pso_init_b<true, HANDS> : k_pso_init_b<false, HANDS>,
-               dim3(P, B), dim3(HPE_NT), 0, d, stride, (const double *)d_states, (const DevObs *)io.obs,
-               hand);
-        for (int g = 1; g <= d.G; ++g) {
-            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
-            launch(c, HPE_PROF_PSO_GEN,
-                   filt ? (r16 ? k_pso_gen_b<true, true, HANDS> : k_pso_gen_b<false, true, HANDS>)
-                        : (r16 ? k_pso_gen_b<true, false, HANDS> : k_pso_gen_b<false, false, HANDS>),
-                   dim3(P, B), dim3(HPE_NT), 0, d, stride, (const DevObs *)io.obs, hand, g, W1, C1, C2,
-                   kg);
-        }
-    }
-    // every live cloud is bounded by 250 points: the non-FILT kernel
-    auto final_k = io.seq ? k_pso_final_live_b<false, HANDS>
-                          : (filt ? k_pso_final_b<true, HANDS> : k_pso_final_b<false, HANDS>);
-    launch(c, HPE_PROF_PSO_FINAL, final_k, dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states, io.obs,
-           hand, (DevObs *)nullptr, wpp ? 0 : 1, io.seq, io.done_host, io.hist, (const int *)nullptr,
-           io.slots, io.cur);
-    HIPCHK(c, hipGetLastError());
-    return HPE_OK;
+// The kernel forms of one frame of B lanes: the axes of hpe_kernels.hip's lane templates, derived
+// once from the frame's targets and the context.
+struct LaneForm {
+    bool hands;   // the HANDS forms: lane hands are set (the batch graphs' key field), or paced
+    LaneSrc src;  // the refine launch prepares every lane's next frame from there (NONE: no next)
+    bool win;     // ... through the lanes' windows
+    bool paced;   // HPE_PACING_FREE: the idle-aware forms, in the HANDS shape alone (the table
+                  // holds the context's hand in every entry while no lane hands are set)
+    bool live;    // the live batch: the final launch publishes the batch's frame number
+    bool rigid;
+    int wpp;      // HPE_BATCH_FORM_WAVE: waves per particle (0: the workgroup form)
+    bool coop, r16, filt;
+};
+static int lane_hands_set(const hpe_ctx *c) { return c->lane_hands_B ? 1 : 0; }
+static LaneForm lane_form(hpe_ctx *c, int P, int B, const DevSwarm &d, const LaneFrameIo &io) {
+    LaneForm f{};
+    f.paced = io.act != nullptr;
+    f.hands = f.paced || lane_hands_set(c);
+    f.src = !io.prep ? LANE_SRC_NONE : io.unit ? LANE_SRC_U16 : io.raw ? LANE_SRC_RAW : LANE_SRC_RING;
+    f.win = io.prep && io.win;
+    f.live = io.seq != nullptr;
+    f.rigid = !c->refine_exact;
+    f.wpp = batch_wave_wpp(c, P, B);
+    f.coop = c->fk_coop;
+    f.r16 = d.K <= 15;
+    f.filt = io.filt;  // (every live cloud is bounded by 250 points: the non-FILT kernels)
+    return f;
 }
 
-// One tracked frame of B lanes, the frame every batch call enqueues: track_frame's launches with a
-// lane dimension, each lane on its own descriptor, cursor and arena.  The refine launch (the
-// CU-filling LDS size puts the lanes on B CUs) is on grid (1, B), or with io.prep on
-// (1 + PREP_WG, B): it then carries every lane's next preparation, read through the raw cursor or
-// from the pinned ring, as a raw sequence's and the pipelined loop's do.  Then launch_pso_lanes.
-// (The _b kernels are emitted in the order the host code first names them: k_pso_init_b first.)
-template <bool HANDS>
-static int track_lane_frame_t(hpe_ctx *c, int P, int refine, int B, double *d_states,
-                              const LaneFrameIo &io) {
-    const DevObs *obs = io.obs;
-    const DevHand *hand = c->d_lane_hands;  // the table: lane b's kernels read entry b
-    const dim3 prep_grid(1 + PREP_WG, B);
-    if (io.prep && io.unit) {
-        // 16-bit frames in the ring (lane input): the u16 forms of the two ring kernels below
-        if (io.follow)
-            hipLaunchKernelGGL(k_window_b<HANDS>, dim3(B), dim3(64), 0, c->stream,
-                               (const double *)d_states, hand, (const WinPar *)c->win.d_par, io.win);
-        const bool rigid = !c->refine_exact;
-        launch(c, HPE_PROF_REFINE,
-               io.win ? (rigid ? k_refine_ring_u16<true, HANDS, true, false>
-                               : k_refine_ring_u16<false, HANDS, true, false>)
-                      : (rigid ? k_refine_ring_u16<true, HANDS, false, false>
-                               : k_refine_ring_u16<false, HANDS, false, false>),
-               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
-               io.prep, (const DevWindow *)io.win, (const int *)nullptr, io.unit);
-    } else if (io.prep && io.win) {
-        // the windowed forms; FOLLOW: first every lane's window from the pose its state holds
-        // now -- this launch's refine workgroup overwrites it -- into the parity being prepared
-        if (io.follow)
-            hipLaunchKernelGGL(k_window_b<HANDS>, dim3(B), dim3(64), 0, c->stream,
-                               (const double *)d_states, hand, (const WinPar *)c->win.d_par, io.win);
-        if (io.raw)
-            launch(c, HPE_PROF_REFINE,
-                   c->refine_exact ? k_refine_prep_wb<false, HANDS> : k_refine_prep_wb<true, HANDS>, prep_grid,
-                   dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep,
-                   io.raw, (const int *)io.cur, (const DevWindow *)io.win);
-        else
-            launch(c, HPE_PROF_REFINE,
-                   c->refine_exact ? k_refine_ring_wb<false, HANDS> : k_refine_ring_wb<true, HANDS>, prep_grid,
-                   dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep,
-                   (const DevWindow *)io.win);
-    } else if (io.prep && io.raw)  // testmodel.cpp:126 + next_frame of the following iteration
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_prep_b<false, HANDS> : k_refine_prep_b<true, HANDS>,
-               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals,
-               refine ? 1 : 0, io.prep, io.raw, (const int *)io.cur);
-    else if (io.prep)
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_ring_b<false, HANDS> : k_refine_ring_b<true, HANDS>,
-               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals,
-               refine ? 1 : 0, io.prep);
-    else if (refine)  // testmodel.cpp:126
-        launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine_b<false, HANDS> : k_refine_b<true, HANDS>,
-               dim3(1, B), dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals);
-    return launch_pso_lanes<HANDS>(c, P, B, d_states, io);
+// One selector per role: the instantiations the host can reach and no others (WIN needs a source;
+// PACED is the live batch's -- the ring, 16-bit or not -- in the HANDS shape and never FILT).
+extern "C++" {
+typedef void (*LaneRefineFn)(double *, const DevObs *, const DevHand *, int *, int, const PrepArgs *,
+                             const DevWindow *, const int *, const float *, const float *const *,
+                             const int *);
+template <bool RIGID, bool HANDS, bool PACED>
+static LaneRefineFn lane_refine_kernel_t(LaneSrc src, bool win) {
+    switch (src) {
+    case LANE_SRC_NONE:
+        return k_refine_lane<RIGID, HANDS, LANE_SRC_NONE, false, PACED>;
+    case LANE_SRC_RING:
+        return win ? k_refine_lane<RIGID, HANDS, LANE_SRC_RING, true, PACED>
+                   : k_refine_lane<RIGID, HANDS, LANE_SRC_RING, false, PACED>;
+    case LANE_SRC_U16:
+        return win ? k_refine_lane<RIGID, HANDS, LANE_SRC_U16, true, PACED>
+                   : k_refine_lane<RIGID, HANDS, LANE_SRC_U16, false, PACED>;
+    case LANE_SRC_RAW:
+        if constexpr (!PACED)
+            return win ? k_refine_lane<RIGID, HANDS, LANE_SRC_RAW, true, false>
+                       : k_refine_lane<RIGID, HANDS, LANE_SRC_RAW, false, false>;
+    }
+    return nullptr;  // a raw batch is never paced
+}
+static LaneRefineFn lane_refine_kernel(const LaneForm &f) {
+    if (f.paced)
+        return f.rigid ? lane_refine_kernel_t<true, true, true>(f.src, f.win)
+                       : lane_refine_kernel_t<false, true, true>(f.src, f.win);
+    if (f.hands)
+        return f.rigid ? lane_refine_kernel_t<true, true, false>(f.src, f.win)
+                       : lane_refine_kernel_t<false, true, false>(f.src, f.win);
+    return f.rigid ? lane_refine_kernel_t<true, false, false>(f.src, f.win)
+                   : lane_refine_kernel_t<false, false, false>(f.src, f.win);
+}
+
+// (the first frame's preparation: the batch calls' begins)
+typedef void (*LanePrepareFn)(const PrepArgs *, const DevWindow *, const int *, const float *,
+                              const float *const *, const int *);
+template <LaneSrc SRC>
+static LanePrepareFn lane_prepare_kernel_t(bool win, bool paced) {
+    if constexpr (SRC != LANE_SRC_RAW)
+        if (paced) return win ? k_prepare_lane<SRC, true, true> : k_prepare_lane<SRC, false, true>;
+    return win ? k_prepare_lane<SRC, true, false> : k_prepare_lane<SRC, false, false>;
+}
+static LanePrepareFn lane_prepare_kernel(LaneSrc src, bool win, bool paced) {
+    if (src == LANE_SRC_RAW) return lane_prepare_kernel_t<LANE_SRC_RAW>(win, false);
+    return src == LANE_SRC_U16 ? lane_prepare_kernel_t<LANE_SRC_U16>(win, paced)
+                               : lane_prepare_kernel_t<LANE_SRC_RING>(win, paced);
+}
+
+typedef void (*LaneWindowFn)(const double *, const DevHand *, const WinPar *, DevWindow *, const int *);
+static LaneWindowFn lane_window_kernel(const LaneForm &f) {
+    return f.paced ? k_window_b<true, true> : f.hands ? k_window_b<true, false> : k_window_b<false, false>;
+}
+
+// init: both forms have one argument list
+typedef void (*LaneInitFn)(DevSwarm, size_t, const double *, const DevObs *, const DevHand *,
+                           const int *);
+template <bool HANDS, bool PACED>
+static LaneInitFn lane_init_kernel_t(const LaneForm &f) {
+    if (f.wpp == 2)
+        return f.coop ? k_pso_init_wb<2, true, HANDS, PACED> : k_pso_init_wb<2, false, HANDS, PACED>;
+    if (f.wpp)
+        return f.coop ? k_pso_init_wb<1, true, HANDS, PACED> : k_pso_init_wb<1, false, HANDS, PACED>;
+    if constexpr (!PACED)
+        if (f.filt) return k_pso_init_b<true, HANDS, false>;
+    return k_pso_init_b<false, HANDS, PACED>;
+}
+static LaneInitFn lane_init_kernel(const LaneForm &f) {
+    return f.paced ? lane_init_kernel_t<true, true>(f)
+                   : f.hands ? lane_init_kernel_t<true, false>(f) : lane_init_kernel_t<false, false>(f);
+}
+
+typedef void (*LaneGenFn)(DevSwarm, size_t, const DevObs *, const DevHand *, int, double, double,
+                          double, InboxCounts, const int *);
+template <bool HANDS, bool PACED>
+static LaneGenFn lane_gen_kernel_t(const LaneForm &f) {
+    if constexpr (!PACED)
+        if (f.filt)
+            return f.r16 ? k_pso_gen_b<true, true, HANDS, false> : k_pso_gen_b<false, true, HANDS, false>;
+    return f.r16 ? k_pso_gen_b<true, false, HANDS, PACED> : k_pso_gen_b<false, false, HANDS, PACED>;
+}
+static LaneGenFn lane_gen_kernel(const LaneForm &f) {
+    return f.paced ? lane_gen_kernel_t<true, true>(f)
+                   : f.hands ? lane_gen_kernel_t<true, false>(f) : lane_gen_kernel_t<false, false>(f);
+}
+
+// the wave form's generation (no exchange, no inbox counts)
+typedef void (*LaneWaveGenFn)(DevSwarm, size_t, const DevObs *, const DevHand *, int, double, double,
+                              double, const int *);
+template <int WPP, bool HANDS, bool PACED>
+static LaneWaveGenFn lane_wave_gen_kernel_t(bool coop, bool r16) {
+    return coop ? (r16 ? k_pso_gen_wb<true, WPP, true, HANDS, PACED> : k_pso_gen_wb<false, WPP, true, HANDS, PACED>)
+                : (r16 ? k_pso_gen_wb<true, WPP, false, HANDS, PACED> : k_pso_gen_wb<false, WPP, false, HANDS, PACED>);
+}
+template <bool HANDS, bool PACED>
+static LaneWaveGenFn lane_wave_gen_kernel_t(const LaneForm &f) {
+    return f.wpp == 2 ? lane_wave_gen_kernel_t<2, HANDS, PACED>(f.coop, f.r16)
+                      : lane_wave_gen_kernel_t<1, HANDS, PACED>(f.coop, f.r16);
+}
+static LaneWaveGenFn lane_wave_gen_kernel(const LaneForm &f) {
+    return f.paced ? lane_wave_gen_kernel_t<true, true>(f)
+                   : f.hands ? lane_wave_gen_kernel_t<true, false>(f)
+                             : lane_wave_gen_kernel_t<false, false>(f);
+}
+
+typedef void (*LaneFinalFn)(DevSwarm, size_t, double *, DevObs *, const DevHand *, DevObs *, int,
+                            unsigned long long *, unsigned long long *, double *, const int *,
+                            const DevObs *, int *, const int *);
+static LaneFinalFn lane_final_kernel(const LaneForm &f) {
+    if (f.paced) return k_pso_final_b<false, true, true, true>;
+    if (f.live) return f.hands ? k_pso_final_b<false, true, true, false> : k_pso_final_b<false, false, true, false>;
+    if (f.hands) return f.filt ? k_pso_final_b<true, true, false, false> : k_pso_final_b<false, true, false, false>;
+    return f.filt ? k_pso_final_b<true, false, false, false> : k_pso_final_b<false, false, false, false>;
 }
 }  // extern "C++"
 
-// The same frame of a free-paced live batch (io.act, HPE_PACING_FREE): launch for launch what
-// track_lane_frame_t and launch_pso_lanes enqueue for a live frame, whatever the lanes' masks are,
-// in the idle-aware kernel forms -- each tests its lane's activity word at entry, so which lanes
-// track and which prepare is decided on the device, by the words the call wrote on the stream
-// before this graph.  The forms exist in the HANDS shape alone (the table holds the context's
-// hand in every entry while no lane hands are set).  No raw cursor, history or slot table: the
-// live batch has none.
-static int track_lane_frame_paced(hpe_ctx *c, int P, int refine, int B, double *d_states,
-                                  const LaneFrameIo &io) {
-    const DevObs *obs = io.obs;
-    const DevHand *hand = c->d_lane_hands;
-    const int *act = io.act;
-    const dim3 prep_grid(1 + PREP_WG, B);
-    const bool rigid = !c->refine_exact;
-    if (io.prep && io.unit) {  // 16-bit frames in the ring (lane input)
-        if (io.follow)
-            hipLaunchKernelGGL(k_window_bi, dim3(B), dim3(64), 0, c->stream, (const double *)d_states,
-                               hand, (const WinPar *)c->win.d_par, io.win, act);
-        launch(c, HPE_PROF_REFINE,
-               io.win ? (rigid ? k_refine_ring_u16<true, true, true, true>
-                               : k_refine_ring_u16<false, true, true, true>)
-                      : (rigid ? k_refine_ring_u16<true, true, false, true>
-                               : k_refine_ring_u16<false, true, false, true>),
-               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
-               io.prep, (const DevWindow *)io.win, act, io.unit);
-    } else if (io.prep && io.win) {
-        if (io.follow)
-            hipLaunchKernelGGL(k_window_bi, dim3(B), dim3(64), 0, c->stream, (const double *)d_states,
-                               hand, (const WinPar *)c->win.d_par, io.win, act);
-        launch(c, HPE_PROF_REFINE, rigid ? k_refine_ring_wbi<true> : k_refine_ring_wbi<false>,
-               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
-               io.prep, (const DevWindow *)io.win, act);
-    } else if (io.prep)
-        launch(c, HPE_PROF_REFINE, rigid ? k_refine_ring_bi<true> : k_refine_ring_bi<false>,
-               prep_grid, dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, refine ? 1 : 0,
-               io.prep, act);
-    else if (refine)
-        launch(c, HPE_PROF_REFINE, rigid ? k_refine_bi<true> : k_refine_bi<false>, dim3(1, B),
-               dim3(RF_NT), RF_DYN_LDS, d_states, obs, hand, c->d_bevals, act);
-    const DevSwarm d = batch_swarm(c);
-    const size_t stride = c->sw.stride;
-    const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
-    static const InboxCounts all_k{};
-    const bool r16 = d.K <= 15;
-    const int wpp = batch_wave_wpp(c, P, B);
-    if (wpp) {
-        const int per_wg = PW_WPB / wpp;
-        const dim3 grid((P + per_wg - 1) / per_wg, B);
-        const bool coop = c->fk_coop;
-        auto ki = wpp == 2 ? (coop ? k_pso_init_wbi<2, true> : k_pso_init_wbi<2, false>)
-                           : (coop ? k_pso_init_wbi<1, true> : k_pso_init_wbi<1, false>);
-        launch(c, HPE_PROF_PSO_INIT, ki, grid, dim3(PW_NT), 0, d, stride, (const double *)d_states,
-               obs, hand, act);
-        auto kw = wpp == 2 ? (coop ? (r16 ? k_pso_gen_wbi<true, 2, true> : k_pso_gen_wbi<false, 2, true>)
-                                   : (r16 ? k_pso_gen_wbi<true, 2, false> : k_pso_gen_wbi<false, 2, false>))
-                           : (coop ? (r16 ? k_pso_gen_wbi<true, 1, true> : k_pso_gen_wbi<false, 1, true>)
-                                   : (r16 ? k_pso_gen_wbi<true, 1, false> : k_pso_gen_wbi<false, 1, false>));
-        for (int g = 1; g <= d.G; ++g)
-            launch(c, HPE_PROF_PSO_GEN, kw, grid, dim3(PW_NT), 0, d, stride, obs, hand, g, W1, C1, C2,
-                   act);
-    } else {
-        // every live cloud is bounded by 250 points: the non-FILT kernels
-        launch(c, HPE_PROF_PSO_INIT, k_pso_init_bi<false>, dim3(P, B), dim3(HPE_NT), 0, d, stride,
-               (const double *)d_states, obs, hand, act);
-        for (int g = 1; g <= d.G; ++g) {
-            const InboxCounts &kg = c->sw.kin.empty() ? all_k : c->sw.kin[g];
-            launch(c, HPE_PROF_PSO_GEN, r16 ? k_pso_gen_bi<true, false> : k_pso_gen_bi<false, false>,
-                   dim3(P, B), dim3(HPE_NT), 0, d, stride, obs, hand, g, W1, C1, C2, kg, act);
-        }
-    }
-    launch(c, HPE_PROF_PSO_FINAL, k_pso_final_live_bi<false>, dim3(1, B), dim3(HPE_NT), 0, d, stride,
-           d_states, io.obs, hand, (DevObs *)nullptr, wpp ? 0 : 1, io.seq, io.done_host,
-           (double *)nullptr, (const int *)nullptr, (const DevObs *)nullptr, (int *)nullptr, act);
-    HIPCHK(c, hipGetLastError());
-    return HPE_OK;
-}
-// ... in the kernels' HANDS forms while lane hands are set, else in the forms that read the
-// context's hand as they did before there were lane hands (the batch graphs' key field).
-static int lane_hands_set(const hpe_ctx *c) { return c->lane_hands_B ? 1 : 0; }
+// One tracked frame of B lanes, the frame every batch call enqueues: track_frame's launches with a
+// lane dimension, each lane on its own descriptor io.obs[b], cursor io.cur[2 b] and arena b of the
+// swarm (batch_swarm).  FOLLOW: first every lane's window from the pose its state holds now --
+// the refine workgroup overwrites it -- into the parity being prepared.  The refine launch (the
+// CU-filling LDS size puts the lanes on B CUs) is on grid (1, B), or with a next frame on
+// (1 + PREP_WG, B): it then carries every lane's preparation, read through the raw cursor or from
+// the pinned ring, as a raw sequence's and the pipelined loop's do (testmodel.cpp:126 + next_frame
+// of the following iteration).  Then pso_evolve and cal_cost(bestp): launch_pso's workgroup form
+// with the lane dimension -- init and the generations on (P, B) -- or, HPE_BATCH_FORM_WAVE, its
+// wave form on (ceil(P / particles per workgroup), B) at pso_wpp(B * P) waves per particle, no
+// inbox counts; the final kernel on (1, B), in the wave form with same_eval = 0: it evaluates
+// cal_cost(bestp).  A free-paced batch (io.act) enqueues the same launches whatever the lanes'
+// masks are: which lanes track and which prepare is decided on the device, by the words the call
+// wrote on the stream before this graph.
 static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_states,
                             const LaneFrameIo &io) {
-    if (io.act) return track_lane_frame_paced(c, P, refine, B, d_states, io);
-    return lane_hands_set(c) ? track_lane_frame_t<true>(c, P, refine, B, d_states, io)
-                             : track_lane_frame_t<false>(c, P, refine, B, d_states, io);
+    const DevSwarm d = batch_swarm(c);
+    const LaneForm f = lane_form(c, P, B, d, io);
+    const DevObs *obs = io.obs;
+    const DevHand *hand = c->d_lane_hands;  // the table: lane b's kernels read entry b
+    const int *act = io.act;
+    const bool prep = f.src != LANE_SRC_NONE;
+    const LaneRefineFn kr = lane_refine_kernel(f);
+    if (!kr) return fail(c, HPE_E_STATE, "a paced frame has no raw cursor");
+    if (f.win && io.follow)
+        hipLaunchKernelGGL(lane_window_kernel(f), dim3(B), dim3(64), 0, c->stream,
+                           (const double *)d_states, hand, (const WinPar *)c->win.d_par, io.win, act);
+    if (prep || refine)
+        launch(c, HPE_PROF_REFINE, kr, dim3(prep ? 1 + PREP_WG : 1, B), dim3(RF_NT), RF_DYN_LDS,
+               d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep, (const DevWindow *)io.win,
+               act, io.unit, io.raw, (const int *)io.cur);
+    const size_t stride = c->sw.stride;
+    const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
+    const int per_wg = f.wpp ? PW_WPB / f.wpp : 1;  // one or two waves per particle, or a workgroup
+    const dim3 grid((P + per_wg - 1) / per_wg, B), block(f.wpp ? PW_NT : HPE_NT);
+    launch(c, HPE_PROF_PSO_INIT, lane_init_kernel(f), grid, block, 0, d, stride,
+           (const double *)d_states, obs, hand, act);
+    if (f.wpp) {
+        const LaneWaveGenFn kw = lane_wave_gen_kernel(f);
+        for (int g = 1; g <= d.G; ++g)
+            launch(c, HPE_PROF_PSO_GEN, kw, grid, block, 0, d, stride, obs, hand, g, W1, C1, C2, act);
+    } else {
+        static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
+        const LaneGenFn kg = lane_gen_kernel(f);
+        for (int g = 1; g <= d.G; ++g)
+            launch(c, HPE_PROF_PSO_GEN, kg, grid, block, 0, d, stride, obs, hand, g, W1, C1, C2,
+                   c->sw.kin.empty() ? all_k : c->sw.kin[g], act);
+    }
+    launch(c, HPE_PROF_PSO_FINAL, lane_final_kernel(f), dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states,
+           io.obs, hand, (DevObs *)nullptr, f.wpp ? 0 : 1, io.seq, io.done_host, io.hist,
+           (const int *)nullptr, io.slots, io.cur, act);
+    HIPCHK(c, hipGetLastError());
+    return HPE_OK;
 }
 
 int hpe_set_batch_form(hpe_ctx *c, int form) {
@@ -2631,8 +2626,9 @@ static int window_from_pose(hpe_ctx *c, const DevHand *hand, const double *theta
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(w.d_one_state, theta, sizeof(double) * HPE_DOF, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(w.d_one_par, &par, sizeof(par), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_window_b<false>, dim3(1), dim3(64), 0, c->stream,
-                       (const double *)w.d_one_state, hand, (const WinPar *)w.d_one_par, w.d_one);
+    hipLaunchKernelGGL((k_window_b<false, false>), dim3(1), dim3(64), 0, c->stream,
+                       (const double *)w.d_one_state, hand, (const WinPar *)w.d_one_par, w.d_one,
+                       (const int *)nullptr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     DevWindow r;
@@ -3100,14 +3096,11 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
     BatchRaw first{};
     for (int b = 0; b < B; ++b) first.raw[b] = d_raw_mm[b];
     hipLaunchKernelGGL(k_raw_begin_b, dim3(1, B), dim3(64), 0, c->stream, first, n, rb.d_raw, rb.d_cur);
-    if (c->win.mode != HPE_WINDOW_OFF)
-        hipLaunchKernelGGL(k_prepare_wb, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                           (const PrepArgs *)rb.d_tab, (const float *const *)rb.d_raw,
-                           (const int *)rb.d_cur, (const DevWindow *)c->win.d_tab);
-    else
-        hipLaunchKernelGGL(k_prepare_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                           (const PrepArgs *)rb.d_tab, (const float *const *)rb.d_raw,
-                           (const int *)rb.d_cur);
+    const bool win = c->win.mode != HPE_WINDOW_OFF;
+    hipLaunchKernelGGL(lane_prepare_kernel(LANE_SRC_RAW, win, false), dim3(PREP_WG, B), dim3(PREP_NT),
+                       0, c->stream, (const PrepArgs *)rb.d_tab,
+                       (const DevWindow *)(win ? c->win.d_tab : nullptr), (const int *)nullptr,
+                       (const float *)nullptr, (const float *const *)rb.d_raw, (const int *)rb.d_cur);
     HIPCHK(c, hipGetLastError());
     const int K = frames_per_graph ? frames_per_graph : HPE_SEQ_CHUNK;
     for (int f0 = 0; f0 < n; f0 += K) {
@@ -3406,28 +3399,14 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
         if ((given >> b & 1) && depth_mm[b] != lv.h_raw[0][b])
             std::memcpy(lv.h_raw[0][b], depth_mm[b], lv.frame_bytes());
     const bool win = c->win.mode != HPE_WINDOW_OFF;
-    if (u16) {
-        if (paced) write_lane_act(c, B, 0, given);
-        hipLaunchKernelGGL(win ? (paced ? k_prepare_ring_u16<true, true> : k_prepare_ring_u16<true, false>)
-                               : (paced ? k_prepare_ring_u16<false, true> : k_prepare_ring_u16<false, false>),
-                           dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream, (const PrepArgs *)lv.d_tab,
-                           (const DevWindow *)(win ? c->win.d_tab : nullptr),
-                           (const int *)(paced ? lv.d_act : nullptr), (const float *)lv.d_unit);
-    } else if (paced) {  // only the lanes given a frame prepare one; the others start empty
-        write_lane_act(c, B, 0, given);
-        if (c->win.mode != HPE_WINDOW_OFF)
-            hipLaunchKernelGGL(k_prepare_ring_wbi, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                               (const PrepArgs *)lv.d_tab, (const DevWindow *)c->win.d_tab,
-                               (const int *)lv.d_act);
-        else
-            hipLaunchKernelGGL(k_prepare_ring_bi, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                               (const PrepArgs *)lv.d_tab, (const int *)lv.d_act);
-    } else if (c->win.mode != HPE_WINDOW_OFF)
-        hipLaunchKernelGGL(k_prepare_ring_wb, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                           (const PrepArgs *)lv.d_tab, (const DevWindow *)c->win.d_tab);
-    else
-        hipLaunchKernelGGL(k_prepare_ring_b, dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                           (const PrepArgs *)lv.d_tab);
+    // paced: only the lanes given a frame prepare one; the others start empty
+    if (paced) write_lane_act(c, B, 0, given);
+    hipLaunchKernelGGL(lane_prepare_kernel(u16 ? LANE_SRC_U16 : LANE_SRC_RING, win, paced),
+                       dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream, (const PrepArgs *)lv.d_tab,
+                       (const DevWindow *)(win ? c->win.d_tab : nullptr),
+                       (const int *)(paced ? lv.d_act : nullptr),
+                       (const float *)(u16 ? lv.d_unit : nullptr), (const float *const *)nullptr,
+                       (const int *)nullptr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     lv.B = B;

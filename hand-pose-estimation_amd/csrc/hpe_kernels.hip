@@ -1177,8 +1177,47 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
 // the mutable arrays of all lanes are B identical arenas `stride` bytes apart, the argument
 // holds lane 0's pointers, and a lane rebases them with scalar adds on the entry batch's
 // words (no table of per-lane structs to load first).  normals, outl, bounds and the inbox
-// counts are shared: every lane draws under the context's seed.  The hand is the context's, or
-// the lane's own (lane_hand below).  Lanes never communicate.
+// counts are shared: every lane draws under the context's seed.  Lanes never communicate.
+//
+// One template per role -- k_pso_init_b, k_pso_gen_b, k_pso_init_wb, k_pso_gen_wb (pso_evolve in
+// the workgroup and the wave form), k_pso_final_b, k_refine_lane, k_prepare_lane, k_window_b --
+// and four independent axes, each a template parameter.  Every form of a role has one argument
+// list; what a form does not read is passed null and never loaded.
+//   SRC (LaneSrc): where the preparation workgroups find the lane's next raw frame.  They ride in
+//     the refine launch, grid (1 + PREP_WG, B): workgroup (0, b) refines, (1.., b) run
+//     prep_workgroup into the lane's other buffer, as k_refine's do.  All sources name the lane's
+//     buffers, descriptors, scratch and hand-off counters (a 128-byte line of its own) by the
+//     device table tab[parity][b] (PrepArgs; the kernels take tab + parity * HPE_BATCH_MAX).
+//       NONE  no next frame: grid (1, B), do_refine the constant 1 (a prepared batch, and the
+//             last frame of the others)
+//       RAW   hpe_track_raw_batch_dev: frame cur[2 b] + 1 of the resident sequence raw_base[b]
+//             (the cursor's slot word counts frames; k_pso_final_b advances it)
+//       RING  hpe_track_batch_pipelined: tab[b].raw itself, the lane's pinned (mapped, coherent)
+//             host buffer of the parity being prepared, read over PCIe inside the launch
+//       U16   hpe_batch_pipeline_begin_u16: the ring holding unsigned 16-bit pixels, read in place
+//             and multiplied by the batch's depth unit *unit -- device memory written at the
+//             begin, never a captured argument (PrepArgsU16, hpe_prep.hpp)
+//   WIN: hpe_set_batch_window.  The frame is read through the lane's window wtab[b] (the
+//     DevWindow table next to the PrepArgs table, same parity offset), in the band workgroups and
+//     the distance transform's mask alike (prep_workgroup<true>): the preparation of the frame
+//     masked on the host.  One more independent load of the preparation workgroups alone.
+//   PACED: hpe_set_batch_pacing(HPE_PACING_FREE).  The first statement tests the lane's activity
+//     word act[lane] -- HPE_ACT_TRACK: the lane tracks its current frame in this call;
+//     HPE_ACT_PREP: it prepares a next frame.  The host writes a call's 16 words on the stream
+//     ahead of the frame's graph (k_lane_act): the graphs hold the table's address, never a mask.
+//     One scalar load indexed by blockIdx, so the decision is workgroup-uniform; an idle
+//     workgroup loads nothing through the lane's descriptor, state row, arena or table entries
+//     (a lane that never held a frame has descriptors that name nothing), reaches no barrier,
+//     counter or hand-off, and stores nothing -- but for lane 0's final workgroup, which
+//     publishes the call's frame number whether or not lane 0 tracks.
+//   HANDS: hpe_set_batch_hands.  The hand is entry blockIdx.y of the flat table (lane_hand).
+// The host names these combinations and no others (hpe_api.inc, the lane_*_kernel selectors):
+// WIN needs a source; PACED is the live batch's, so RING or U16 (or NONE, its ending frame), and
+// is built in the HANDS shape alone -- the table holds the context's hand in every entry while
+// no lane hands are set, which is pinned bit-identical to the !HANDS forms.
+enum LaneSrc { LANE_SRC_NONE, LANE_SRC_RAW, LANE_SRC_RING, LANE_SRC_U16 };
+#define HPE_ACT_TRACK 1
+#define HPE_ACT_PREP 2
 __device__ __forceinline__ DevSwarm lane_swarm(DevSwarm sw, size_t stride) {
     const size_t off = stride * blockIdx.y;
     sw.xh = (double *)((char *)sw.xh + off);
@@ -1205,21 +1244,27 @@ __device__ __forceinline__ const DevHand *lane_hand(const DevHand *__restrict__ 
 #define HPE_EVALS_N 4              // a lane's refine evaluation counter {last, -, total (u64)}
 
 // states: B x 27; obs: B descriptors, lane b's current frame (k_seq_begin_b / k_pso_final_b)
-template <bool FILT, bool HANDS>
+template <bool FILT, bool HANDS, bool PACED>
 __global__ __launch_bounds__(HPE_NT) void k_pso_init_b(DevSwarm sw, size_t stride,
                                                        const double *__restrict__ states,
                                                        const DevObs *__restrict__ obs,
-                                                       const DevHand *__restrict__ Hg) {
+                                                       const DevHand *__restrict__ Hg,
+                                                       const int *__restrict__ act) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
     pso_init_body<HPE_NT, FILT>(lane_swarm(sw, stride), states + (size_t)HPE_STATE_N * blockIdx.y,
                                 obs + blockIdx.y, lane_hand<HANDS>(Hg));
 }
 
-template <bool ROW16, bool FILT, bool HANDS>
+template <bool ROW16, bool FILT, bool HANDS, bool PACED>
 __global__ __launch_bounds__(HPE_NT) void k_pso_gen_b(DevSwarm sw, size_t stride,
                                                       const DevObs *__restrict__ obs,
                                                       const DevHand *__restrict__ Hg, int g,
                                                       double W1, double C1, double C2,
-                                                      InboxCounts kin) {
+                                                      InboxCounts kin,
+                                                      const int *__restrict__ act) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
     pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, lane_hand<HANDS>(Hg),
                                              g, W1, C1, C2, kin);
 }
@@ -1229,46 +1274,46 @@ __global__ __launch_bounds__(HPE_NT) void k_pso_gen_b(DevSwarm sw, size_t stride
 // obs[b].  The arguments are k_pso_final's own (the host passes same_eval = 1 and no
 // selected-frame hand-back, pipeline counter or refine failure flag), so the body compiles as
 // it does there.
-template <bool FILT, bool HANDS, bool TAIL = true>
+// LIVE (the live batch): the cursor may be null (no cursor, history or slot table), and the
+// batch's frame counter seq_b (published to done_host for the host's wait before it refills a
+// pinned buffer) is bumped by lane 0's workgroup alone -- once per frame, not B times on one
+// word.  One counter serves the batch: the refine launch of every lane, which read the pinned
+// buffers, has retired before any workgroup of this launch starts.  blockIdx.y is uniform, and
+// the body's counter branch reaches no barrier.
+// PACED: publication does not depend on lane 0 being active.  When lane 0 idles, its workgroup
+// bumps the counter and stores it to done_host as the body's first statement would (the same
+// wave, the same stores), then leaves -- once per call, even when no lane tracks, so the host's
+// wait on this parity's frame number always ends.
+template <bool FILT, bool HANDS, bool LIVE, bool PACED, bool TAIL = true>
 __global__ __launch_bounds__(HPE_NT) void k_pso_final_b(DevSwarm sw, size_t stride,
                                                         double *__restrict__ states, DevObs *obs,
                                                         const DevHand *__restrict__ hands,
                                                         DevObs *__restrict__ obs_out, int same_eval,
-                                                        unsigned long long *__restrict__ seq_dev,
+                                                        unsigned long long *__restrict__ seq_b,
                                                         unsigned long long *done_host,
                                                         double *__restrict__ hist,
                                                         const int *__restrict__ fail,
                                                         const DevObs *__restrict__ seq_table,
-                                                        int *__restrict__ cur) {
+                                                        int *__restrict__ cur,
+                                                        const int *__restrict__ act) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    static_assert(LIVE || !PACED, "only a live batch is paced");
+    if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) {
+        if (blockIdx.y == 0 && threadIdx.x == HPE_NT - 64) {
+            const unsigned long long n = *seq_b + 1;
+            *seq_b = n;
+            __hip_atomic_store(done_host, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        return;
+    }
     const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     sw = lane_swarm(sw, stride);
     double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
     DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
     const DevObs *const og = seq_obs;
-    int *__restrict__ const seq_cur = cur + 2 * blockIdx.y;
+    int *__restrict__ const seq_cur = LIVE && !cur ? nullptr : cur + 2 * blockIdx.y;
+    unsigned long long *__restrict__ const seq_dev = LIVE && blockIdx.y != 0 ? nullptr : seq_b;
 #include "hpe_final_body.inc"
-}
-
-// The single-workgroup staged refine, one workgroup per lane (grid (1, B)): no preparation
-// workgroups, no exchange pick, no helpers.
-template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_b(double *__restrict__ states,
-                                                    const DevObs *__restrict__ obs,
-                                                    const DevHand *__restrict__ hands,
-                                                    int *__restrict__ evals_b) {
-    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    const int do_refine = 1;
-    const PrepArgs pa{};
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-    constexpr bool WIN = false;
-    const DevWindow pw{};
-#include "hpe_refine_body.inc"
 }
 
 // Start of a batch call: lane b's first descriptor staged, its cursor at {first slot, row b n}.
@@ -1286,28 +1331,8 @@ __global__ void k_seq_begin_b(const DevObs *__restrict__ table, BatchFirst first
     }
 }
 
-// ------------------------------------------------------------------ batched raw lanes
-// hpe_track_raw_batch_dev: B resident raw sequences in the same launches.  Lane b owns two frame
-// buffers, their descriptors obs[parity][b], preparation scratch and hand-off counters (a
-// 128-byte line of its own), all named by the device table tab[parity][b] (PrepArgs with no raw
-// frame, written when the buffers are allocated); raw_base[b] is the lane's first raw frame and
-// cur[2 b] = {frame, history row} its cursor, which k_pso_final_b advances (no slot table: the
-// slot word counts frames).  The kernels take tab + parity * HPE_BATCH_MAX.
-
-// The preparation of lane blockIdx.y: its table entry, on raw frame cur + next.  Three
-// independent loads; only the preparation workgroups call it.
-__device__ __forceinline__ PrepArgs lane_prep(const PrepArgs *__restrict__ tab,
-                                              const float *const *__restrict__ raw_base,
-                                              const int *__restrict__ cur, int next) {
-    const int b = blockIdx.y;
-    PrepArgs a = tab[b];
-    a.raw = raw_base[b] + (size_t)(cur[2 * b] + next) * a.raw_stride;
-    a.raw_row = nullptr;  // a.raw is the frame itself
-    return a;
-}
-
 // Start of a raw batch call: lane b's raw base, its cursor at {frame 0, row b n}.  Frame 0 goes
-// to buffer parity 0 (k_prepare_b below).
+// to buffer parity 0 (k_prepare_lane below).
 struct BatchRaw {
     const float *raw[16];
 };
@@ -1321,180 +1346,89 @@ __global__ void k_raw_begin_b(BatchRaw first, int n, const float **__restrict__ 
     }
 }
 
-// k_prepare for every lane's frame at its cursor (frame 0 of a call), grid (PREP_WG, B)
-__global__ __launch_bounds__(PREP_NT) void k_prepare_b(const PrepArgs *__restrict__ tab,
-                                                       const float *const *__restrict__ raw_base,
-                                                       const int *__restrict__ cur) {
-    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
-    prep_workgroup(lane_prep(tab, raw_base, cur, 0), blockIdx.x, lds);
+// The preparation of lane blockIdx.y from source SRC: its table entry, and with it RAW: on raw
+// frame cur + next (three independent loads); RING: nothing else; U16: the depth unit.  Only the
+// preparation workgroups call it.
+template <LaneSrc SRC>
+__device__ __forceinline__ auto lane_prep(const PrepArgs *__restrict__ tab,
+                                          const float *__restrict__ unit,
+                                          const float *const *__restrict__ raw_base,
+                                          const int *__restrict__ cur, int next) {
+    // (each branch is the statements its forms were measured with -- the lane signed here,
+    // unsigned below; the entry copied whole here, assigned below: DESIGN.md 4.7)
+    if constexpr (SRC == LANE_SRC_RAW) {
+        const int b = blockIdx.y;
+        PrepArgs a = tab[b];
+        a.raw = raw_base[b] + (size_t)(cur[2 * b] + next) * a.raw_stride;
+        a.raw_row = nullptr;  // a.raw is the frame itself
+        return a;
+    } else if constexpr (SRC == LANE_SRC_U16) {
+        PrepArgsU16 a;
+        static_cast<PrepArgs &>(a) = tab[blockIdx.y];
+        a.unit = *unit;
+        return a;
+    } else {
+        return tab[blockIdx.y];
+    }
 }
 
-// k_refine_b with the lane's next frame prepared in the same launch, grid (1 + PREP_WG, B):
-// workgroup (0, b) is k_refine_b's (it reads what that one reads: tab, raw_base and cur are
-// touched by the preparation workgroups (1.., b) alone), the others run prep_workgroup into the
-// lane's other buffer, as k_refine's do.  do_refine = 0: the preparation only.
-template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_prep_b(double *__restrict__ states,
-                                                         const DevObs *__restrict__ obs,
-                                                         const DevHand *__restrict__ hands,
-                                                         int *__restrict__ evals_b, int do_refine,
-                                                         const PrepArgs *__restrict__ tab,
-                                                         const float *const *__restrict__ raw_base,
-                                                         const int *__restrict__ cur) {
+// k_prepare for every lane's first frame of a call (RAW: the frame at its cursor), grid
+// (PREP_WG, B); PACED: only the lanes given a first frame prepare one
+template <LaneSrc SRC, bool WIN, bool PACED>
+__global__ __launch_bounds__(PREP_NT) void k_prepare_lane(const PrepArgs *__restrict__ tab,
+                                                          const DevWindow *__restrict__ wtab,
+                                                          const int *__restrict__ act,
+                                                          const float *__restrict__ unit,
+                                                          const float *const *__restrict__ raw_base,
+                                                          const int *__restrict__ cur) {
+    static_assert(SRC != LANE_SRC_NONE, "a preparation has a source");
+    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
+    if (PACED && !(act[blockIdx.y] & HPE_ACT_PREP)) return;
+    DevWindow pw{};
+    if (WIN) pw = wtab[blockIdx.y];
+    prep_workgroup<WIN>(lane_prep<SRC>(tab, unit, raw_base, cur, 0), blockIdx.x, lds, nullptr, &pw);
+}
+
+// The single-workgroup staged refine, one workgroup per lane: no exchange pick, no helpers.
+// With a source, workgroups (1.., b) prepare the lane's next frame (do_refine = 0: the
+// preparation only); workgroup (0, b) reads what it reads without one.  PACED: workgroup (0, b)
+// runs iff the lane tracks, the preparation workgroups iff it prepares -- all nine or none, so an
+// idle preparation never touches the lane's three hand-off counters, and a preparation that
+// runs finds them as the last one left them.
+template <bool RIGID, bool HANDS, LaneSrc SRC, bool WIN, bool PACED, bool STAGED = true, bool MW = false>
+__global__ __launch_bounds__(RF_NT) void k_refine_lane(double *__restrict__ states,
+                                                       const DevObs *__restrict__ obs,
+                                                       const DevHand *__restrict__ hands,
+                                                       int *__restrict__ evals_b, int do_refine_arg,
+                                                       const PrepArgs *__restrict__ tab,
+                                                       const DevWindow *__restrict__ wtab,
+                                                       const int *__restrict__ act,
+                                                       const float *__restrict__ unit,
+                                                       const float *const *__restrict__ raw_base,
+                                                       const int *__restrict__ cur) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    static_assert(SRC != LANE_SRC_NONE || !WIN, "a window is the preparation's");
+    if (PACED && !(act[blockIdx.y] & (SRC == LANE_SRC_NONE || blockIdx.x == 0 ? HPE_ACT_TRACK
+                                                                              : HPE_ACT_PREP)))
+        return;
     const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
     int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
     int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    PrepArgs pa{};
-    if (blockIdx.x >= 1) pa = lane_prep(tab, raw_base, cur, 1);
+    const int do_refine = SRC == LANE_SRC_NONE ? 1 : do_refine_arg;
+    decltype(lane_prep<SRC>(tab, unit, raw_base, cur, 1)) pa{};
+    DevWindow pw{};
+    if (SRC != LANE_SRC_NONE && blockIdx.x >= 1) {
+        pa = lane_prep<SRC>(tab, unit, raw_base, cur, 1);
+        if (WIN) pw = wtab[blockIdx.y];
+    }
     const DevMw mw{};
     const DevPick pk{};
     const PrepSplit ps{};
-    constexpr bool WIN = false;
-    const DevWindow pw{};
 #include "hpe_refine_body.inc"
 }
 static_assert(PREP_NT == RF_NT, "the preparation workgroups ride in the refine launch");
-
-// ------------------------------------------------------------------ live batched lanes
-// hpe_track_batch_pipelined: the raw lanes above, fed a frame per call from host memory.  The
-// lane's raw frame is not raw_base + cursor frames but a two-deep ring: its pinned (mapped,
-// coherent) host buffer of the parity being prepared, which the table entry names itself --
-// tab[parity][b].raw, written once with the buffers, raw_row null.  So the preparation of lane
-// blockIdx.y is its table entry and nothing else; the preparation workgroups read the frame
-// over PCIe inside the launch they ride in, as k_refine's do for hpe_track_pipelined.
-
-// k_prepare for frame 0 of every lane (hpe_batch_pipeline_begin), grid (PREP_WG, B)
-__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_b(const PrepArgs *__restrict__ tab) {
-    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
-    prep_workgroup(tab[blockIdx.y], blockIdx.x, lds);
-}
-
-// k_refine_prep_b on the ring, grid (1 + PREP_WG, B): workgroup (0, b) is k_refine_b's, the
-// others prepare the lane's next frame from tab[b].raw.  do_refine = 0: the preparation only.
-template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_ring_b(double *__restrict__ states,
-                                                         const DevObs *__restrict__ obs,
-                                                         const DevHand *__restrict__ hands,
-                                                         int *__restrict__ evals_b, int do_refine,
-                                                         const PrepArgs *__restrict__ tab) {
-    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    PrepArgs pa{};
-    if (blockIdx.x >= 1) pa = tab[blockIdx.y];
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-    constexpr bool WIN = false;
-    const DevWindow pw{};
-#include "hpe_refine_body.inc"
-}
-
-// k_pso_final_b for the live batch, its arguments k_pso_final_b's: no cursor, history or slot
-// table, and the batch's frame counter (seq_b, published to done_host for the host's wait before
-// it refills a pinned buffer) bumped by lane 0's workgroup alone -- once per frame, not B times
-// on one word.  One counter serves the batch: the refine launch of every lane, which read the
-// pinned buffers, has retired before any workgroup of this launch starts.  blockIdx.y is
-// uniform, and the body's counter branch reaches no barrier.
-template <bool FILT, bool HANDS, bool TAIL = true>
-__global__ __launch_bounds__(HPE_NT) void k_pso_final_live_b(DevSwarm sw, size_t stride,
-                                                             double *__restrict__ states, DevObs *obs,
-                                                             const DevHand *__restrict__ hands,
-                                                             DevObs *__restrict__ obs_out, int same_eval,
-                                                             unsigned long long *__restrict__ seq_b,
-                                                             unsigned long long *done_host,
-                                                             double *__restrict__ hist,
-                                                             const int *__restrict__ fail,
-                                                             const DevObs *__restrict__ seq_table,
-                                                             int *__restrict__ cur) {
-    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
-    sw = lane_swarm(sw, stride);
-    double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
-    DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
-    const DevObs *const og = seq_obs;
-    int *__restrict__ const seq_cur = cur ? cur + 2 * blockIdx.y : nullptr;
-    unsigned long long *__restrict__ const seq_dev = blockIdx.y == 0 ? seq_b : nullptr;
-#include "hpe_final_body.inc"
-}
-
-// ------------------------------------------------------------------ lane windows
-// hpe_set_batch_window: the four lane preparation kernels above with every lane's frame read
-// through its window -- wtab + parity * HPE_BATCH_MAX, the DevWindow table next to the PrepArgs
-// table, entry blockIdx.y -- in the band workgroups and in the distance transform's mask alike
-// (prep_workgroup<true>): the preparation of the frame masked on the host.  The window is one
-// more independent load of the preparation workgroups; the refine workgroup (0, b) reads what
-// it reads in the kernel it mirrors.
-__global__ __launch_bounds__(PREP_NT) void k_prepare_wb(const PrepArgs *__restrict__ tab,
-                                                        const float *const *__restrict__ raw_base,
-                                                        const int *__restrict__ cur,
-                                                        const DevWindow *__restrict__ wtab) {
-    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
-    const DevWindow pw = wtab[blockIdx.y];
-    prep_workgroup<true>(lane_prep(tab, raw_base, cur, 0), blockIdx.x, lds, nullptr, &pw);
-}
-
-__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_wb(const PrepArgs *__restrict__ tab,
-                                                             const DevWindow *__restrict__ wtab) {
-    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
-    const DevWindow pw = wtab[blockIdx.y];
-    prep_workgroup<true>(tab[blockIdx.y], blockIdx.x, lds, nullptr, &pw);
-}
-
-template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_prep_wb(double *__restrict__ states,
-                                                          const DevObs *__restrict__ obs,
-                                                          const DevHand *__restrict__ hands,
-                                                          int *__restrict__ evals_b, int do_refine,
-                                                          const PrepArgs *__restrict__ tab,
-                                                          const float *const *__restrict__ raw_base,
-                                                          const int *__restrict__ cur,
-                                                          const DevWindow *__restrict__ wtab) {
-    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    PrepArgs pa{};
-    DevWindow pw{};
-    if (blockIdx.x >= 1) {
-        pa = lane_prep(tab, raw_base, cur, 1);
-        pw = wtab[blockIdx.y];
-    }
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-    constexpr bool WIN = true;
-#include "hpe_refine_body.inc"
-}
-
-template <bool RIGID, bool HANDS, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_ring_wb(double *__restrict__ states,
-                                                          const DevObs *__restrict__ obs,
-                                                          const DevHand *__restrict__ hands,
-                                                          int *__restrict__ evals_b, int do_refine,
-                                                          const PrepArgs *__restrict__ tab,
-                                                          const DevWindow *__restrict__ wtab) {
-    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    PrepArgs pa{};
-    DevWindow pw{};
-    if (blockIdx.x >= 1) {
-        pa = tab[blockIdx.y];
-        pw = wtab[blockIdx.y];
-    }
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-    constexpr bool WIN = true;
-#include "hpe_refine_body.inc"
-}
 
 // The pose rule (include/hpe.h): the window of the context hand at pose th[0..25], by one wave.
 // FK is fk_wave, as k_build runs it, so the centres are hpe_build_spheres' bit for bit; lane
@@ -1549,12 +1483,16 @@ __device__ __forceinline__ void window_wave(FkSm &f, const DevHand *__restrict__
 // state at its end, so the preparation workgroups riding in it cannot read the pose themselves;
 // the hand-off is the kernel boundary.  hpe_window_from_pose and hpe_lane_window_from_pose run
 // the !HANDS form on one pose, with the hand they name as Hg.
-// (The body is text of its own, hpe_window_body.inc: the idle-aware k_window_bi includes it too.)
-template <bool HANDS>
+// PACED (this kernel's lane dimension is x): the window of a lane that accepts no frame in this
+// call stays as it was, and its state row -- a joining lane's may hold anything -- is not read.
+template <bool HANDS, bool PACED>
 __global__ __launch_bounds__(64) void k_window_b(const double *__restrict__ states,
                                                  const DevHand *__restrict__ Hg,
                                                  const WinPar *__restrict__ par,
-                                                 DevWindow *__restrict__ wout) {
+                                                 DevWindow *__restrict__ wout,
+                                                 const int *__restrict__ act) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    if (PACED && !(act[blockIdx.x] & HPE_ACT_PREP)) return;
 #include "hpe_window_body.inc"
 }
 
@@ -1573,11 +1511,14 @@ __device__ __forceinline__ DevSwarm lane_swarm_w(DevSwarm sw, size_t stride) {
     return sw;
 }
 
-template <int WPP, bool COOP, bool HANDS>
+template <int WPP, bool COOP, bool HANDS, bool PACED>
 __global__ __launch_bounds__(PW_NT) void k_pso_init_wb(DevSwarm sw, size_t stride,
                                                        const double *__restrict__ states,
                                                        const DevObs *__restrict__ obs,
-                                                       const DevHand *__restrict__ hands) {
+                                                       const DevHand *__restrict__ hands,
+                                                       const int *__restrict__ act) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
     const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     sw = lane_swarm_w(sw, stride);
     const double *__restrict__ const x0 = states + (size_t)HPE_STATE_N * blockIdx.y;
@@ -1585,11 +1526,14 @@ __global__ __launch_bounds__(PW_NT) void k_pso_init_wb(DevSwarm sw, size_t strid
 #include "hpe_wave_init_body.inc"
 }
 
-template <bool ROW16, int WPP, bool COOP, bool HANDS>
+template <bool ROW16, int WPP, bool COOP, bool HANDS, bool PACED>
 __global__ __launch_bounds__(PW_NT, WPP == 2 ? 2 : 4) void k_pso_gen_wb(DevSwarm sw, size_t stride,
                                                       const DevObs *__restrict__ obs,
                                                       const DevHand *__restrict__ hands, int g,
-                                                      double W1, double C1, double C2) {
+                                                      double W1, double C1, double C2,
+                                                      const int *__restrict__ act) {
+    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
     const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     constexpr bool XCH = false;  // no exchange inside a batch
     sw = lane_swarm_w(sw, stride);
@@ -1598,21 +1542,7 @@ __global__ __launch_bounds__(PW_NT, WPP == 2 ? 2 : 4) void k_pso_gen_wb(DevSwarm
 }
 
 // ------------------------------------------------------------------ lane pacing
-// hpe_set_batch_pacing(HPE_PACING_FREE): the lanes of a live batch no longer advance in lockstep.
-// Every kernel the live batch launches has an idle-aware form here, the kernel it mirrors behind
-// an entry test of the lane's activity word act[lane] -- bit 0 (HPE_ACT_TRACK): the lane tracks
-// its current frame in this call; bit 1 (HPE_ACT_PREP): it prepares a next frame.  The host
-// writes a call's 16 words on the stream, ahead of the frame's graph (k_lane_act; not when the
-// table already holds them): the graphs hold the table's address alone, never a mask.
-// The test is one scalar load indexed by blockIdx, so the decision is workgroup-uniform, and it
-// stands before everything of the body: an idle workgroup loads nothing through the lane's
-// descriptor, state row, arena or table entries (a lane that never held a frame has descriptors
-// that name nothing), reaches no barrier, counter or hand-off, and stores nothing -- but for lane
-// 0's final workgroup, which publishes the call's frame number whether or not lane 0 tracks.
-// Built in the HANDS shape only: the hand table holds the context's hand in every entry while no
-// lane hands are set, which is pinned bit-identical to the !HANDS forms.
-#define HPE_ACT_TRACK 1
-#define HPE_ACT_PREP 2
+// The activity words the PACED forms test (HPE_ACT_TRACK, HPE_ACT_PREP above)
 struct LaneAct {
     int word[16];
 };
@@ -1621,253 +1551,6 @@ static_assert(HPE_BATCH_MAX == 16, "LaneAct holds one word per lane");
 __global__ void k_lane_act(LaneAct a, int *__restrict__ act) {
     const int t = threadIdx.x;
     if (t < HPE_BATCH_MAX) act[t] = a.word[t];
-}
-
-template <bool FILT>
-__global__ __launch_bounds__(HPE_NT) void k_pso_init_bi(DevSwarm sw, size_t stride,
-                                                        const double *__restrict__ states,
-                                                        const DevObs *__restrict__ obs,
-                                                        const DevHand *__restrict__ Hg,
-                                                        const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
-    pso_init_body<HPE_NT, FILT>(lane_swarm(sw, stride), states + (size_t)HPE_STATE_N * blockIdx.y,
-                                obs + blockIdx.y, lane_hand<true>(Hg));
-}
-
-template <bool ROW16, bool FILT>
-__global__ __launch_bounds__(HPE_NT) void k_pso_gen_bi(DevSwarm sw, size_t stride,
-                                                       const DevObs *__restrict__ obs,
-                                                       const DevHand *__restrict__ Hg, int g,
-                                                       double W1, double C1, double C2,
-                                                       InboxCounts kin,
-                                                       const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
-    pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, lane_hand<true>(Hg),
-                                             g, W1, C1, C2, kin);
-}
-
-template <int WPP, bool COOP>
-__global__ __launch_bounds__(PW_NT) void k_pso_init_wbi(DevSwarm sw, size_t stride,
-                                                        const double *__restrict__ states,
-                                                        const DevObs *__restrict__ obs,
-                                                        const DevHand *__restrict__ hands,
-                                                        const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
-    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
-    sw = lane_swarm_w(sw, stride);
-    const double *__restrict__ const x0 = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-#include "hpe_wave_init_body.inc"
-}
-
-template <bool ROW16, int WPP, bool COOP>
-__global__ __launch_bounds__(PW_NT, WPP == 2 ? 2 : 4) void k_pso_gen_wbi(DevSwarm sw, size_t stride,
-                                                      const DevObs *__restrict__ obs,
-                                                      const DevHand *__restrict__ hands, int g,
-                                                      double W1, double C1, double C2,
-                                                      const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
-    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
-    constexpr bool XCH = false;  // no exchange inside a batch
-    sw = lane_swarm_w(sw, stride);
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-#include "hpe_wave_gen_body.inc"
-}
-
-// k_pso_final_live_b.  Publication does not depend on lane 0 being active: when lane 0 idles, its
-// workgroup bumps the batch's frame counter and stores it to done_host as the body's first
-// statement would (the same wave, the same stores), then leaves -- once per call, even when no
-// lane tracks, so the host's wait on this parity's frame number always ends.
-template <bool FILT, bool TAIL = true>
-__global__ __launch_bounds__(HPE_NT) void k_pso_final_live_bi(DevSwarm sw, size_t stride,
-                                                              double *__restrict__ states, DevObs *obs,
-                                                              const DevHand *__restrict__ hands,
-                                                              DevObs *__restrict__ obs_out, int same_eval,
-                                                              unsigned long long *__restrict__ seq_b,
-                                                              unsigned long long *done_host,
-                                                              double *__restrict__ hist,
-                                                              const int *__restrict__ fail,
-                                                              const DevObs *__restrict__ seq_table,
-                                                              int *__restrict__ cur,
-                                                              const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) {
-        if (blockIdx.y == 0 && threadIdx.x == HPE_NT - 64) {
-            const unsigned long long n = *seq_b + 1;
-            *seq_b = n;
-            __hip_atomic_store(done_host, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        return;
-    }
-    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
-    sw = lane_swarm(sw, stride);
-    double *__restrict__ const out = states + (size_t)HPE_STATE_N * blockIdx.y;
-    DevObs *const seq_obs = obs + blockIdx.y;  // aliases og
-    const DevObs *const og = seq_obs;
-    int *__restrict__ const seq_cur = cur ? cur + 2 * blockIdx.y : nullptr;
-    unsigned long long *__restrict__ const seq_dev = blockIdx.y == 0 ? seq_b : nullptr;
-#include "hpe_final_body.inc"
-}
-
-// k_refine_b, for the batch's ending frame
-template <bool RIGID, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_bi(double *__restrict__ states,
-                                                     const DevObs *__restrict__ obs,
-                                                     const DevHand *__restrict__ hands,
-                                                     int *__restrict__ evals_b,
-                                                     const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & HPE_ACT_TRACK)) return;
-    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    const int do_refine = 1;
-    const PrepArgs pa{};
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-    constexpr bool WIN = false;
-    const DevWindow pw{};
-#include "hpe_refine_body.inc"
-}
-
-// k_refine_ring_b: workgroup (0, b) runs iff the lane tracks, the preparation workgroups
-// (1.., b) iff it prepares -- all nine or none, so an idle preparation never touches the lane's
-// three hand-off counters, and a preparation that runs finds them as the last one left them.
-template <bool RIGID, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_ring_bi(double *__restrict__ states,
-                                                          const DevObs *__restrict__ obs,
-                                                          const DevHand *__restrict__ hands,
-                                                          int *__restrict__ evals_b, int do_refine,
-                                                          const PrepArgs *__restrict__ tab,
-                                                          const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & (blockIdx.x == 0 ? HPE_ACT_TRACK : HPE_ACT_PREP))) return;
-    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    PrepArgs pa{};
-    if (blockIdx.x >= 1) pa = tab[blockIdx.y];
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-    constexpr bool WIN = false;
-    const DevWindow pw{};
-#include "hpe_refine_body.inc"
-}
-
-template <bool RIGID, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_ring_wbi(double *__restrict__ states,
-                                                           const DevObs *__restrict__ obs,
-                                                           const DevHand *__restrict__ hands,
-                                                           int *__restrict__ evals_b, int do_refine,
-                                                           const PrepArgs *__restrict__ tab,
-                                                           const DevWindow *__restrict__ wtab,
-                                                           const int *__restrict__ act) {
-    if (!(act[blockIdx.y] & (blockIdx.x == 0 ? HPE_ACT_TRACK : HPE_ACT_PREP))) return;
-    const DevHand *__restrict__ const Hg = lane_hand<true>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    PrepArgs pa{};
-    DevWindow pw{};
-    if (blockIdx.x >= 1) {
-        pa = tab[blockIdx.y];
-        pw = wtab[blockIdx.y];
-    }
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-    constexpr bool WIN = true;
-#include "hpe_refine_body.inc"
-}
-
-// k_prepare_ring_b / _wb for the begin: only the lanes given a first frame prepare one
-__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_bi(const PrepArgs *__restrict__ tab,
-                                                             const int *__restrict__ act) {
-    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
-    if (!(act[blockIdx.y] & HPE_ACT_PREP)) return;
-    prep_workgroup(tab[blockIdx.y], blockIdx.x, lds);
-}
-
-__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_wbi(const PrepArgs *__restrict__ tab,
-                                                              const DevWindow *__restrict__ wtab,
-                                                              const int *__restrict__ act) {
-    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
-    if (!(act[blockIdx.y] & HPE_ACT_PREP)) return;
-    const DevWindow pw = wtab[blockIdx.y];
-    prep_workgroup<true>(tab[blockIdx.y], blockIdx.x, lds, nullptr, &pw);
-}
-
-// k_window_b<true> (its lane dimension is x): the window of a lane that accepts no frame in
-// this call stays as it was, and its state row -- a joining lane's may hold anything -- is not read.
-__global__ __launch_bounds__(64) void k_window_bi(const double *__restrict__ states,
-                                                  const DevHand *__restrict__ Hg,
-                                                  const WinPar *__restrict__ par,
-                                                  DevWindow *__restrict__ wout,
-                                                  const int *__restrict__ act) {
-    if (!(act[blockIdx.x] & HPE_ACT_PREP)) return;
-    constexpr bool HANDS = true;
-#include "hpe_window_body.inc"
-}
-
-// ------------------------------------------------------------------ lane input
-// hpe_batch_pipeline_begin_u16: the eight ring kernels above on lanes whose pinned buffers hold
-// 16-bit pixels.  The preparation workgroups read them in place, as unsigned 16-bit values, and
-// multiply by the batch's depth unit *unit -- device memory written at the begin, never a
-// captured argument -- so half the bytes cross the host link and no launch is added
-// (PrepArgsU16, hpe_prep.hpp).  One template for each of the two kernels: WIN and PACED select
-// the form mirrored (k_*_ring_b, _wb, _bi, _wbi), whose statements these are; wtab is read under
-// WIN and act under PACED alone (null otherwise).  PACED is built in the HANDS shape only, as
-// the idle-aware forms are.
-__device__ __forceinline__ PrepArgsU16 lane_prep_u16(const PrepArgs *__restrict__ tab,
-                                                     const float *__restrict__ unit) {
-    PrepArgsU16 a;
-    static_cast<PrepArgs &>(a) = tab[blockIdx.y];
-    a.unit = *unit;
-    return a;
-}
-
-template <bool WIN, bool PACED>
-__global__ __launch_bounds__(PREP_NT) void k_prepare_ring_u16(const PrepArgs *__restrict__ tab,
-                                                              const DevWindow *__restrict__ wtab,
-                                                              const int *__restrict__ act,
-                                                              const float *__restrict__ unit) {
-    __shared__ __align__(16) unsigned char lds[prep_lds_bytes()];
-    if (PACED && !(act[blockIdx.y] & HPE_ACT_PREP)) return;
-    DevWindow pw{};
-    if (WIN) pw = wtab[blockIdx.y];
-    prep_workgroup<WIN>(lane_prep_u16(tab, unit), blockIdx.x, lds, nullptr, &pw);
-}
-
-template <bool RIGID, bool HANDS, bool WIN, bool PACED, bool STAGED = true, bool MW = false>
-__global__ __launch_bounds__(RF_NT) void k_refine_ring_u16(double *__restrict__ states,
-                                                           const DevObs *__restrict__ obs,
-                                                           const DevHand *__restrict__ hands,
-                                                           int *__restrict__ evals_b, int do_refine,
-                                                           const PrepArgs *__restrict__ tab,
-                                                           const DevWindow *__restrict__ wtab,
-                                                           const int *__restrict__ act,
-                                                           const float *__restrict__ unit) {
-    static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
-    if (PACED && !(act[blockIdx.y] & (blockIdx.x == 0 ? HPE_ACT_TRACK : HPE_ACT_PREP))) return;
-    const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
-    double *__restrict__ const x0g = states + (size_t)HPE_STATE_N * blockIdx.y;
-    const DevObs *__restrict__ const og = obs + blockIdx.y;
-    int32_t *const match_g = nullptr;  // the staged form keeps matchId in LDS
-    int *__restrict__ const evals_out = evals_b + HPE_EVALS_N * blockIdx.y;
-    PrepArgsU16 pa{};
-    DevWindow pw{};
-    if (blockIdx.x >= 1) {
-        pa = lane_prep_u16(tab, unit);
-        if (WIN) pw = wtab[blockIdx.y];
-    }
-    const DevMw mw{};
-    const DevPick pk{};
-    const PrepSplit ps{};
-#include "hpe_refine_body.inc"
 }
 
 // ------------------------------------------------------------------ lane reports

@@ -1,5 +1,5 @@
 // hpe_refine_body.inc -- the body of k_refine, included as text by k_refine and by its batched
-// form k_refine_b (hpe_kernels.hip), so both compile the same statements.  Names it expects in
+// form k_refine_lane (hpe_kernels.hip), so both compile the same statements.  Names it expects in
 // scope: STAGED, MW, RIGID (compile-time), x0g, og, Hg, match_g, evals_out, do_refine, pa, mw,
 // pk, ps (k_refine's parameters), and WIN (compile-time) with pw, the window the preparation
 // workgroups read the next frame through (the batch calls' windowed kernels; elsewhere false

@@ -1,6 +1,6 @@
-// hpe_window_body.inc -- the body of k_window_b, included as text by k_window_b and by its
-// idle-aware form k_window_bi (hpe_kernels.hip), so both compile the same statements.  Names it
-// expects in scope: HANDS (compile-time), states, Hg, par, wout (k_window_b's parameters).
+// hpe_window_body.inc -- the body of k_window_b (hpe_kernels.hip), text of its own as the other
+// lane kernels' bodies are.  Names it expects in scope: HANDS (compile-time), states, Hg, par,
+// wout (k_window_b's parameters).
     __shared__ DevHand hs;
     __shared__ FkSm fk;
     const int l = threadIdx.x;

@@ -344,8 +344,10 @@ def main():
     ap.add_argument("--in-place", action="store_true")
     a = ap.parse_args()
     quantised = a.input == "u16" or a.unit is not None
-    if (quantised or a.in_place) and (not a.live or a.drop or a.hands != "shared"):
-        ap.error("--input, --unit and --in-place need --live without --drop and --hands distinct")
+    if (quantised or a.in_place) and (not a.live or a.drop):
+        ap.error("--input, --unit and --in-place need --live without --drop")
+    if a.in_place and a.hands != "shared":
+        ap.error("--in-place needs --hands shared")
     if a.unit is not None and not (np.isfinite(a.unit) and a.unit > 0):
         ap.error("--unit MM: finite and > 0")
     unit = np.float32(1.0 if a.unit is None else a.unit)
@@ -421,8 +423,15 @@ def main():
             if a.live:
                 host = [[np.ascontiguousarray(render[b].render_depth(th), dtype=np.float32)
                          for th in synth.trajectory(n, b, revert=0.02)] for b in range(B)]
+                feed = host  # the timed runs feed the lanes' own frames too
+                if quantised:  # ... quantised as the shared ones above
+                    q16 = [[np.ascontiguousarray(np.rint(f / unit).clip(0, 65535).astype(np.uint16))
+                            for f in fr] for fr in host]
+                    host = [[hpe.depth_u16_to_mm(q, unit) for q in fr] for fr in q16]
+                    feed = q16 if a.input == "u16" else host
                 if checked:
-                    check_live_against_alone(ctx, torch, hpe.X0, host, alone=render)
+                    check_live_against_alone(ctx, torch, hpe.X0, host, alone=render, feed=feed,
+                                             begin_kw=begin_kw)
             elif a.raw:
                 raws = make_raw_lanes(ctx, torch, B, n, render)
                 if checked:
