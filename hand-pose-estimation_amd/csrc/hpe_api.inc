@@ -431,6 +431,12 @@ struct hpe_ctx {
     int mw_fits = -1;  // the multi-workgroup launch fits co-resident (occupancy), -1 unknown
     bool refine_mw = true;
     bool refine_exact = false;  // refine spheres by the reference's chain (else hand frame)
+    // speculated translation block (hpe_set_refine_spec): the staged refine's second workgroup
+    bool refine_spec = true;
+    unsigned long long *d_spec_g = nullptr;  // DevSpec::g
+    unsigned *d_spec_ep = nullptr;           // DevSpec::epoch
+    int spec_spin = SPEC_SPIN_MAX;  // HPE_SPEC_SPIN: the leader's polls for a result (tests: 0)
+    int spec_fits = -1;  // both refine workgroups and the preparation fit co-resident, -1 unknown
     unsigned long long captures = 0;  // graphs captured so far (hpe_graph_captures)
     // opt-in per-generation exchange (hpe_set_exchange)
     int xch_every = 0;
@@ -1155,6 +1161,10 @@ int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
         dalloc(&c->d_mw_ctr, MW_CTR_WORDS) != hipSuccess ||
         hipMemset(c->d_mw_ctr, 0, MW_CTR_WORDS * sizeof(unsigned)) != hipSuccess ||
         dalloc(&c->d_mw_err, 1) != hipSuccess || hipMemset(c->d_mw_err, 0, sizeof(int)) != hipSuccess ||
+        dalloc(&c->d_spec_g, SPEC_GRAN) != hipSuccess ||
+        hipMemset(c->d_spec_g, 0, SPEC_GRAN * sizeof(unsigned long long)) != hipSuccess ||
+        dalloc(&c->d_spec_ep, 64) != hipSuccess ||
+        hipMemset(c->d_spec_ep, 0, 64 * sizeof(unsigned)) != hipSuccess ||
         hipHostMalloc((void **)&c->h_pinned, sizeof(double) * 256, 0) != hipSuccess ||
         hipHostMalloc((void **)&c->h_mw_err, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void **)&c->h_mw_err_dev, c->h_mw_err, 0) != hipSuccess) {
@@ -1172,6 +1182,8 @@ int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
     if (const char *rm = std::getenv("HPE_REFINE_MW")) c->refine_mw = rm[0] != '0';
     if (const char *re = std::getenv("HPE_REFINE_EXACT")) c->refine_exact = re[0] == '1';
     if (const char *sp = std::getenv("HPE_MW_SPIN")) c->mw_spin = std::max(0, std::atoi(sp));
+    if (const char *rs = std::getenv("HPE_REFINE_SPEC")) c->refine_spec = rs[0] != '0';
+    if (const char *ss = std::getenv("HPE_SPEC_SPIN")) c->spec_spin = std::max(0, std::atoi(ss));
     if (const char *ps = std::getenv("HPE_PREP_SPLIT")) c->prep_split = ps[0] != '0';
     *c->h_mw_err = 0;
     const char *ng = std::getenv("HPE_NO_GRAPH");
@@ -1227,6 +1239,8 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->d_mw_part);
     dfree(c->d_mw_ctr);
     dfree(c->d_mw_err);
+    dfree(c->d_spec_g);
+    dfree(c->d_spec_ep);
     dfree(c->d_render);
     dfree(c->d_obs);
     dfree(c->d_obs_active);
@@ -1788,6 +1802,21 @@ static bool mw_fits(hpe_ctx *c) {
     return c->mw_fits == 1;
 }
 
+// The speculated translation block gains only with the leader, the runner and the preparation
+// workgroups resident at once (a runner that starts late only costs the leader its bounded
+// wait): checked once per context and refine form, as mw_fits; else the one-workgroup form.
+static bool spec_fits(hpe_ctx *c) {
+    if (c->spec_fits < 0) {
+        int per_cu = 0, cus = 0;
+        auto k = c->refine_exact ? k_refine<true, false, false, true> : k_refine<true, false, true, true>;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, RF_NT, RF_DYN_LDS) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess)
+            per_cu = cus = 0;
+        c->spec_fits = (long)per_cu * cus >= 2 + PREP_WG ? 1 : 0;
+    }
+    return c->spec_fits == 1;
+}
+
 // refine_init_pose on io's frame (do_refine) and, when pa != NULL, the next frame's
 // preparation in the same launch (workgroups 1, 2).  *pick: the previous frame's exchange
 // pick, which this launch takes (and empties: do_refine is the chunk loops' rule).
@@ -1804,14 +1833,24 @@ static int refine_launch(hpe_ctx *c, const FrameIo &io, int do_refine, const Pre
     std::memset(&mw, 0, sizeof(mw));
     const DevPick pk = pick ? *pick : DevPick{};
     if (pick) *pick = DevPick{};
-    if (io.n_max <= RF_STAGE_MAX) {
+    const DevSpec nosp{};
+    if (io.n_max <= RF_STAGE_MAX && c->refine_spec && spec_fits(c)) {
+        // two refine workgroups (the leader and the translation block's runner), each with the
+        // padded dynamic LDS below and so a CU of its own; the preparation workgroups follow
+        const DevSpec sp{c->d_spec_g, c->d_spec_ep, c->spec_spin};
+        const dim3 grid(pa ? 2 + PREP_WG : 2);
+        launch(c, HPE_PROF_REFINE,
+               c->refine_exact ? k_refine<true, false, false, true> : k_refine<true, false, true, true>,
+               grid, dim3(RF_NT), RF_DYN_LDS, d_x0, io.obs, (const DevHand *)c->d_hand,
+               c->d_match, c->d_evals, do_refine, a, mw, pk, ps, sp);
+    } else if (io.n_max <= RF_STAGE_MAX) {
         // The dynamic LDS is padded to (almost) the whole CU: no other workgroup can share
         // the CU of this single-workgroup, latency-bound kernel.  Fixed size: the launch is
         // identical for every frame.
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<true> : k_refine<true, false, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0, io.obs, (const DevHand *)c->d_hand,
-               c->d_match, c->d_evals, do_refine, a, mw, pk, ps);
+               c->d_match, c->d_evals, do_refine, a, mw, pk, ps, nosp);
     } else if (c->refine_mw && mw_fits(c)) {  // multi-workgroup form: MW_MAX_Q helpers own cloud slices
         mw.job = c->d_mw_job;
         mw.part = c->d_mw_part;
@@ -1824,13 +1863,13 @@ static int refine_launch(hpe_ctx *c, const FrameIo &io, int do_refine, const Pre
         launch(c, HPE_PROF_REFINE,
                c->refine_exact ? k_refine<false, true> : k_refine<false, true, true>, grid,
                dim3(RF_NT), (unsigned)prep_lds_bytes(), d_x0, io.obs, (const DevHand *)c->d_hand,
-               c->d_match, c->d_evals, do_refine, a, mw, pk, ps);
+               c->d_match, c->d_evals, do_refine, a, mw, pk, ps, nosp);
     } else {
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<false> : k_refine<false, false, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0,
                io.obs, (const DevHand *)c->d_hand, c->d_match, c->d_evals, do_refine, a,
-               mw, pk, ps);
+               mw, pk, ps, nosp);
     }
     HIPCHK(c, hipGetLastError());
     return HPE_OK;
@@ -2086,10 +2125,22 @@ int hpe_set_refine_exact(hpe_ctx *c, int exact) {
     if (c->refine_exact != (exact != 0)) {
         c->refine_exact = exact != 0;
         c->mw_fits = -1;
+        c->spec_fits = -1;
         ++c->epoch;  // the captured tracking graphs hold the other refine kernel
     }
     return HPE_OK;
 }
+
+int hpe_set_refine_spec(hpe_ctx *c, int on) {
+    if (!c) return HPE_E_ARG;
+    if (c->refine_spec != (on != 0)) {
+        c->refine_spec = on != 0;
+        ++c->epoch;  // the captured tracking graphs hold the other refine launch
+    }
+    return HPE_OK;
+}
+
+int hpe_get_refine_spec(const hpe_ctx *c) { return c && c->refine_spec ? 1 : 0; }
 
 int hpe_get_refine_exact(const hpe_ctx *c) { return c && c->refine_exact ? 1 : 0; }
 

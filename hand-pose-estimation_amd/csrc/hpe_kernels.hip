@@ -992,6 +992,139 @@ __device__ __forceinline__ void mw_helper(const DevMw &mw, int h, const DevObs *
     }
 }
 
+// ---------------------------------------------------------------- speculated translation block
+// The two-workgroup form of the staged refine (DevSpec, hpe_layout.hpp).  The
+// leader (workgroup 0) runs the serial algorithm and only ever stores: before each line search
+// of the rotation block, wave SPEC_PW sends x0 as granules and goes on.  The runner (workgroup
+// 1) runs the translation block from the newest x0 with the body's own statements; one of its
+// waves loads the granules at the start of a round and looks at them at the round's end, so a
+// newer x0 restarts it and an abort ends it without a wait of its own.  Only when the rotation
+// block ends on a failing search (x0 unchanged: the runner started from the block's final
+// pose) does the leader wait, bounded by DevSpec::spin polls, for the runner's x0[3..5] and
+// evaluation count; otherwise, or when that wait runs out, it aborts the runner and runs the
+// block itself.  A granule is one aligned 8-byte agent-scope store ({tag, 32-bit value}): a
+// reader takes a message only when all its tags agree, so no fence orders anything.
+#define SPEC_SPIN_MAX 1024       // the leader's polls for a committed result (~1 ms)
+#define SPEC_IDLE_SPIN (1 << 20) // the runner's polls for its next word (the leader always sends one)
+#define SPEC_PW (RF_NW - 1)      // the wave that sends (leader) and polls (runner)
+
+struct SpecSm {
+    unsigned half[SPEC_X0_GRAN];  // the newer x0 a poll found
+    int verdict;                  // runner: 0 go on, > 0 restart from message `verdict`, -1 exit;
+                                  // leader: 1 = the runner's result is in res / evals
+    int evals;
+    double res[3];
+};
+struct SpecPoll {  // the runner's view of the leader's words (gold_tree polls through it)
+    DevSpec sp;
+    SpecSm *sm;
+    unsigned ep;  // this launch's epoch
+    int seq;      // the message the runner works on
+};
+
+__device__ __forceinline__ unsigned long long spec_load(const unsigned long long *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void spec_store(unsigned long long *p, unsigned tag, unsigned v) {
+    __hip_atomic_store(p, ((unsigned long long)tag << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned spec_half(double x, int hi) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return hi ? (unsigned)(b >> 32) : (unsigned)b;
+}
+// Leader, one wave: message tag & 31 = x0 (26 doubles in LDS).  Stores only.
+__device__ __forceinline__ void spec_send(const DevSpec &sp, unsigned tag, const double *x0) {
+    const int l = threadIdx.x & 63;
+    if (l < SPEC_X0_GRAN) spec_store(sp.g + l, tag, spec_half(x0[l >> 1], l & 1));
+}
+// Runner, one whole wave: load the message and the control granule ...
+__device__ __forceinline__ unsigned long long spec_poll_issue(const DevSpec &sp) {
+    const int l = threadIdx.x & 63;
+    return spec_load(sp.g + (l < SPEC_CTL ? l : SPEC_CTL));
+}
+// ... and judge them: -1 the leader aborted, s > seq a whole message s of this launch (its x0
+// into sm.half), else 0; *commit = the message the leader committed to (0: none).  The verdict
+// goes to sm.verdict for the other waves (read behind the caller's barrier).
+__device__ __forceinline__ int spec_poll_take(SpecSm &sm, unsigned long long g, unsigned ep,
+                                              int seq, int *commit = nullptr) {
+    const int l = threadIdx.x & 63;
+    const unsigned tag = (unsigned)(g >> 32), val = (unsigned)g;
+    const unsigned t0 = (unsigned)__builtin_amdgcn_readlane((int)tag, 0);
+    const unsigned ct = (unsigned)__builtin_amdgcn_readlane((int)tag, SPEC_CTL);
+    const unsigned cv = (unsigned)__builtin_amdgcn_readlane((int)val, SPEC_CTL);
+    const bool whole = __all(l >= SPEC_X0_GRAN || tag == t0) != 0;
+    const bool mine = (ct >> 5) == ep;
+    int v = 0;
+    if (mine && cv == SPEC_ABORT) {
+        v = -1;
+    } else if (whole && (t0 >> 5) == ep && (int)(t0 & 31u) > seq) {
+        v = (int)(t0 & 31u);
+        if (l < SPEC_X0_GRAN) sm.half[l] = val;
+    }
+    if (commit) *commit = (mine && cv == SPEC_COMMIT) ? (int)(ct & 31u) : 0;
+    if (l == 0) sm.verdict = v;
+    return v;
+}
+// Runner, every thread: wait for the next word that concerns it -- a message newer than seq,
+// an abort, or (done: the block of message seq is finished) the commit of seq.  Returns the
+// new message's number, 0 for the commit, -1 to exit (abort, or the polls ran out: the leader
+// always sends an abort or a commit, so only a leader that never ran gets there).  Barriers
+// at both ends: sm is free on entry and read by everyone on exit.
+__device__ __forceinline__ int spec_wait(const DevSpec &sp, SpecSm &sm, unsigned ep, int seq, bool done) {
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        int v = -1;
+        for (int i = 0; i < SPEC_IDLE_SPIN; ++i) {
+            int commit = 0;
+            const int r = spec_poll_take(sm, spec_poll_issue(sp), ep, seq, &commit);
+            if (r != 0 || (done && commit == seq)) {
+                v = r;
+                break;
+            }
+            __builtin_amdgcn_s_sleep(2);
+        }
+        if (threadIdx.x == 0) sm.verdict = v;
+    }
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(sm.verdict);  // decides exits and barriers (§7)
+}
+// Runner, every thread: x0 = the message a poll left in sm.half.  Ends with a barrier.
+__device__ __forceinline__ void spec_take_x0(const SpecSm &sm, double *x0) {
+    const int t = threadIdx.x;
+    if (t < HPE_DOF)
+        x0[t] = __longlong_as_double((long long)(((unsigned long long)sm.half[2 * t + 1] << 32) | sm.half[2 * t]));
+    __syncthreads();
+}
+// Runner, wave 0: the finished block's x0[3..5] and evaluation count, tagged with the message.
+__device__ __forceinline__ void spec_result(const DevSpec &sp, unsigned tag, const double *x0, int evals) {
+    const int l = threadIdx.x & 63;
+    if (l < 6) spec_store(sp.g + SPEC_RES + l, tag, spec_half(x0[3 + (l >> 1)], l & 1));
+    else if (l == 6) spec_store(sp.g + SPEC_RES + 6, tag, (unsigned)evals);
+}
+// Leader, wave 0: commit to message tag & 31 and wait, at most sp.spin polls, for its result;
+// on any other end tell the runner to stop.  true: sm.res / sm.evals hold the result.
+__device__ __forceinline__ bool spec_commit(const DevSpec &sp, SpecSm &sm, unsigned tag, bool failed) {
+    const int l = threadIdx.x & 63;
+    bool ok = false;
+    if (failed && sp.spin > 0) {
+        if (l == 0) spec_store(sp.g + SPEC_CTL, tag, SPEC_COMMIT);
+        for (int i = 0; i < sp.spin && !ok; ++i) {
+            const unsigned long long g = spec_load(sp.g + SPEC_RES + (l < 7 ? l : 6));
+            ok = __all((unsigned)(g >> 32) == tag) != 0;
+            if (ok) {
+                const unsigned lo = (unsigned)__shfl((int)(unsigned)g, (l << 1) & 63);
+                const unsigned hi = (unsigned)__shfl((int)(unsigned)g, ((l << 1) + 1) & 63);
+                if (l < 3) sm.res[l] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+                if (l == 6) sm.evals = (int)(unsigned)g;
+            } else {
+                __builtin_amdgcn_s_sleep(2);
+            }
+        }
+    }
+    if (!ok && l == 0) spec_store(sp.g + SPEC_CTL, tag, SPEC_ABORT);
+    return ok;
+}
+
 // Speculation shapes of the Goldstein search.  A round evaluates the nodes of a small
 // tree of decision prefixes, relative to the bracket state (a, b, alpha) at the round's
 // start: node j lies len decisions below it, decision k = bit k of bits (1 = "up": Armijo
@@ -1054,7 +1187,11 @@ __device__ __forceinline__ GoldShape gold_shape(int ctx) {
 // after 30 rejected trials); the accepted node's spheres are copied into rs.base and its
 // cost to *f_acc.  UPD: the search also applies x0 = x0 - tk * g (PSO.cpp:256; gl =
 // component threadIdx.x of g) before its last barrier.  evals grows by the serial count.
-template <bool MW = false, int POL = GOLD_BALANCED, bool UPD = false, bool RIGID = false, class CV>
+// POLL with poll (the speculated refine's runner): wave SPEC_PW loads the leader's words at the start of
+// every round and judges them at its end; a verdict other than 0 goes to *drop and ends the
+// search at once, its result void (the caller restarts or exits).
+template <bool MW = false, int POL = GOLD_BALANCED, bool UPD = false, bool RIGID = false,
+          bool POLL = false, class CV>
 __device__ __forceinline__ double gold_tree(RefineSm &rs, const DevObs &o, const CV &cv,
                                             const DevHand *__restrict__ H,
                                             const int32_t *__restrict__ match, double fk,
@@ -1062,7 +1199,8 @@ __device__ __forceinline__ double gold_tree(RefineSm &rs, const DevObs &o, const
                                             double *f_acc, FkX *Xt = nullptr,
                                             MwLeader *ml = nullptr, int *flag = nullptr,
                                             const FrozenPts *fp = nullptr, int rblk = 0,
-                                            const double *md2p = nullptr) {
+                                            const double *md2p = nullptr,
+                                            const SpecPoll *poll = nullptr, int *drop = nullptr) {
     const int t = threadIdx.x, w = t >> 6, l = t & 63;
     StampClock sc;
     sc.start();
@@ -1074,6 +1212,8 @@ __device__ __forceinline__ double gold_tree(RefineSm &rs, const DevObs &o, const
         const GoldShape sh = gold_shape<POL>(ctx);
         const int nn = sh.n;
         double thl = 0.0;  // theta[l] of this wave's node (FK's trig reads it in a register)
+        [[maybe_unused]] unsigned long long pg = 0;
+        if constexpr (POLL) if (w == SPEC_PW) pg = spec_poll_issue(poll->sp);
         if (w < nn) {
             const int nbw = (int)((sh.nb >> (8 * w)) & 0xff), len = nbw >> 5, bits = nbw & 31;
             double ga = A, gb = B, gal = alpha;
@@ -1129,7 +1269,15 @@ __device__ __forceinline__ double gold_tree(RefineSm &rs, const DevObs &o, const
                 ((double *)&rs.base)[q] = ((const double *)&rs.w[accepted])[q];
             if (f_acc) *f_acc = rs.f[accepted];
         }
+        if constexpr (POLL) if (w == SPEC_PW) spec_poll_take(*poll->sm, pg, poll->ep, poll->seq);
         __syncthreads();
+        if constexpr (POLL) {  // (sm.verdict is next written behind the next round's first barrier)
+            const int v = __builtin_amdgcn_readfirstlane(poll->sm->verdict);  // decides exits (§7)
+            if (v != 0) {
+                *drop = v;
+                break;
+            }
+        }
         REF_TS(rs.ts_n, 4);
         sc.lap(19);  // one speculated round
     }
@@ -1140,7 +1288,7 @@ __device__ __forceinline__ double gold_tree(RefineSm &rs, const DevObs &o, const
         hpe_stamps[32 + 9] += 1;
     }
 #if HPE_STAMPS
-    if (t == 0) {  // every search of every block: {path bits, trials << 32, accepted << 40}
+    if (t == 0 && !POLL) {  // every search of every block: {path bits, trials << 32, accepted << 40}
         const unsigned long long k = atomicAdd(&hpe_gold_log[0], 1ull);
         if (k < HPE_GOLD_LOG)
             hpe_gold_log[1 + k] = path | ((unsigned long long)it << 32) |
@@ -1159,15 +1307,39 @@ __device__ __forceinline__ double gold_tree(RefineSm &rs, const DevObs &o, const
 // RIGID: the hand-frame refine (rigid_wave, hpe_device.hpp): every evaluation of the call
 // places its spheres as Rg q + u from centres q built once from x0's digit angles, the
 // collision a constant of the call; HPE_REFINE_EXACT=1 selects the reference's chain.
-template <bool STAGED, bool MW = false, bool RIGID = false>
+// SPEC (STAGED, not MW): workgroup 1 is the runner of the speculated translation block (above)
+// and the preparation workgroups follow it: grid 2 or 2 + PREP_WG.
+template <bool STAGED, bool MW = false, bool RIGID = false, bool SPEC = false>
 __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, const DevObs *__restrict__ og,
                                                   const DevHand *__restrict__ Hg,
                                                   int32_t *__restrict__ match_g,
                                                   int *__restrict__ evals_out, int do_refine,
-                                                  PrepArgs pa, DevMw mw, DevPick pk, PrepSplit ps) {
+                                                  PrepArgs pa, DevMw mw, DevPick pk, PrepSplit ps,
+                                                  DevSpec sp) {
+    static_assert(!SPEC || (STAGED && !MW), "the runner stages the cloud; no helpers");
     constexpr bool WIN = false;
     const DevWindow pw{};
+    if constexpr (!SPEC) {
+        constexpr bool RUNNER = false;
+        SpecSm *const ssm_p = nullptr;
 #include "hpe_refine_body.inc"
+    } else {
+        extern __shared__ __align__(16) unsigned char dyn[];  // staged cloud + matchId / prep
+        __shared__ RefineSm rs;
+        __shared__ DevHand hs;  // hand constants in LDS: keeps them out of the loop's registers
+        __shared__ int mwflag;
+        __shared__ SpecSm ssm;
+        SpecSm *const ssm_p = &ssm;
+        // the body once per role: the runner's copy, and the leader's and the preparation's
+        auto body = [&](auto role) {
+            constexpr bool RUNNER = decltype(role)::value;
+#define HPE_REFINE_BODY_NO_DECLS
+#include "hpe_refine_body.inc"
+#undef HPE_REFINE_BODY_NO_DECLS
+        };
+        if (blockIdx.x == 1) body(std::true_type{});
+        else body(std::false_type{});
+    }
 }
 
 // ------------------------------------------------------------------ batched lanes
@@ -1426,6 +1598,9 @@ __global__ __launch_bounds__(RF_NT) void k_refine_lane(double *__restrict__ stat
     const DevMw mw{};
     const DevPick pk{};
     const PrepSplit ps{};
+    constexpr bool SPEC = false, RUNNER = false;  // lanes keep the one-workgroup body
+    const DevSpec sp{};
+    SpecSm *const ssm_p = nullptr;
 #include "hpe_refine_body.inc"
 }
 static_assert(PREP_NT == RF_NT, "the preparation workgroups ride in the refine launch");

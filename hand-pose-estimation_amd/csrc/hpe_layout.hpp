@@ -151,3 +151,23 @@ struct DevMw {
     int Q;
     int spin;        // polls per wait before it counts as timed out (MW_SPIN_MAX; tests)
 };
+
+// Speculated translation block (k_refine<STAGED, false, RIGID, SPEC>): workgroup 1 (the runner)
+// runs the refine's second block from the pose of every rotation-block line search while
+// workgroup 0 (the leader) runs that search; a failing search leaves the pose unchanged, so the
+// leader then takes the runner's result instead of running the block itself.  All words are
+// 8-byte {tag, value} granules, each written by one agent-scope store: tag = launch epoch << 5 |
+// message number (1..15, the rotation block's line searches), so no word of an earlier launch
+// is ever taken for this launch's.
+#define SPEC_X0_GRAN (2 * HPE_DOF)  // g[0..52): x0 as 32-bit halves (leader -> runner)
+#define SPEC_CTL SPEC_X0_GRAN       // g[52]: SPEC_COMMIT / SPEC_ABORT of message tag & 31
+#define SPEC_RES 64                 // g[64..71): x0[3..5] halves, evaluations (runner -> leader)
+#define SPEC_GRAN 96
+#define SPEC_EP_MASK 0x7ffffffu
+enum { SPEC_COMMIT = 1, SPEC_ABORT = 2 };
+struct DevSpec {
+    unsigned long long *g;  // [SPEC_GRAN] the granules
+    unsigned *epoch;        // [0] launches the leader finished, [32] the runner: each workgroup
+                            // counts its own, so both name a launch alike without a host reset
+    int spin;               // polls of the leader's wait for the result (SPEC_SPIN_MAX; tests: 0)
+};

@@ -3,14 +3,25 @@
 // scope: STAGED, MW, RIGID (compile-time), x0g, og, Hg, match_g, evals_out, do_refine, pa, mw,
 // pk, ps (k_refine's parameters), and WIN (compile-time) with pw, the window the preparation
 // workgroups read the next frame through (the batch calls' windowed kernels; elsewhere false
-// and an unread DevWindow).
+// and an unread DevWindow); SPEC, RUNNER (compile-time) with sp, the speculated translation
+// block's words and ssm_p, its workgroup's SpecSm in LDS (hpe_kernels.hip; elsewhere false, an
+// unread DevSpec and a null pointer): k_refine<..., SPEC>
+// compiles the body twice, once as the runner's (RUNNER: workgroup 1) and once as everyone
+// else's, so neither role carries the other's registers or branches in its loops.  There the
+// body runs inside a lambda (its returns end the workgroup) and the kernel declares the shared
+// variables once (HPE_REFINE_BODY_NO_DECLS).  Every statement of the speculated form sits
+// behind `if constexpr`: without SPEC the body is the one-workgroup form's, statement for
+// statement.
+#ifndef HPE_REFINE_BODY_NO_DECLS
     extern __shared__ __align__(16) unsigned char dyn[];  // staged cloud + matchId / prep
-    const int nhelp = MW ? mw.Q : 0;
+#endif
+    const int nhelp = MW ? mw.Q : SPEC ? 1 : 0;  // workgroups between the leader and preparation
+    constexpr bool runner = SPEC && RUNNER;  // runs the translation block ahead of the leader
     if (MW && blockIdx.x >= 1 && (int)blockIdx.x <= nhelp) {
         if (do_refine) mw_helper<RIGID>(mw, blockIdx.x - 1, og, Hg, match_g);
         return;
     }
-    if (blockIdx.x >= 1) {
+    if (blockIdx.x >= 1 && !runner) {
         const unsigned long long t0 = HPE_STAMPS ? __builtin_amdgcn_s_memtime() : 0;
         prep_workgroup<WIN>(pa, blockIdx.x - 1 - nhelp, dyn, &ps, &pw);
         if (HPE_STAMPS && threadIdx.x == 0) {  // diagnostic build: prep workgroup spans
@@ -21,9 +32,16 @@
         return;
     }
     if (!do_refine) return;
+    // the speculated form: this launch's epoch (each workgroup counts the launches it finished)
+    unsigned sp_ep = 0;
+    if constexpr (SPEC)
+        sp_ep = (__hip_atomic_load(sp.epoch + (runner ? 32 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u) &
+                SPEC_EP_MASK;
     const DevObs o = *og;  // the selected frame (device-resident: graph-stable args)
+#ifndef HPE_REFINE_BODY_NO_DECLS
     __shared__ RefineSm rs;
     __shared__ DevHand hs;  // hand constants in LDS: keeps them out of the loop's registers
+#endif
     const int t = threadIdx.x, w = t >> 6, l = t & 63;
     stage_hand<RF_NT>(hs, Hg);
     const DevHand *__restrict__ H = &hs;
@@ -41,7 +59,19 @@
         match = (int32_t *)(cz + o.n);
     }
     if constexpr (!STAGED) cv = obs_cloud(o);
-    if (pk.gath) {
+    // the speculated form's leader: the messages sent; runner: the message it works on
+    [[maybe_unused]] int sp_seq = 0;
+    if constexpr (runner) {
+        // x0 comes with the first message (the exchange pick stays with the leader); none: the
+        // leader is already past its rotation block, or never ran
+        sp_seq = spec_wait(sp, *ssm_p, sp_ep, 0, false);
+        if (sp_seq <= 0) {
+            if (t == 0)
+                __hip_atomic_store(sp.epoch + 32, sp_ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        spec_take_x0(*ssm_p, rs.x0);
+    } else if (pk.gath) {
         // the previous frame's subswarm exchange: x0 = the best all-gathered state (k_pick_best's
         // rule), also stored to d_state and the previous frame's history row
         if (w == 0) {
@@ -54,10 +84,12 @@
     }
     if (t == 0) rs.ts_n = 0;
     REF_TS(rs.ts_n, 0);
+#ifndef HPE_REFINE_BODY_NO_DECLS
     __shared__ int mwflag;
+#endif
     MwLeader ml{mw, 0u, false};
     __syncthreads();
-    if (RIGID) {
+    if (RIGID) {  // (runner: from the first message -- x0's digits never change in a call)
         // hand-frame centres q (x0's digits, theta0 = -180, theta1..5 = 0: Tgb = I, u = 0)
         // and the call's constant self-collision penalty
         if (w == 0) {
@@ -97,7 +129,12 @@
     // the lane's sphere (lane l, clamped) off-image depth value, the same for every
     // evaluation of the call (depth_finish's md * md, computed once)
     const double md2_l = depth_off_sq(o, H->radii[l < HPE_NS ? l : HPE_NS - 1]);
-    for (int blk = 0; blk < 2; ++blk) {
+    [[maybe_unused]] int verdict = 0;  // runner: the leader's word that ended a speculation early
+    [[maybe_unused]] SpecPoll spoll{};
+spec_again:  // the runner comes back here with every newer x0
+    __attribute__((unused));
+    if constexpr (runner) spoll = SpecPoll{sp, ssm_p, sp_ep, sp_seq};
+    for (int blk = runner ? 1 : 0; blk < 2; ++blk) {
         const int lo = 3 * blk;  // start_idx (PSO.cpp:226-227); end_idx = lo + 2
         // Block 2 moves only the global position u = x0[3..5]: every FK of the block is
         // the stored rotation terms of x0 plus u (FK_TRANSLATE, bit-identical).
@@ -117,6 +154,12 @@
         double tol = 1;
         int cnt = 0, iter = 0;
         while (tol > 1e-6 && iter < 15 && cnt < 1 && !(MW && ml.failed)) {
+            if constexpr (SPEC && !runner) if (blk == 0) {
+                // this search's x0 to the runner (stores only): should the search fail, the
+                // translation block is already under way from the pose it leaves
+                sp_seq += 1;
+                if (w == SPEC_PW) spec_send(sp, (sp_ep << 5) | (unsigned)sp_seq, rs.x0);
+            }
             // f_k = cal_cost2(x0, matchId, true).  The spheres of x0 are already in rs.base
             // when x0 is the accepted Goldstein point of the previous iteration
             // (x0 + tk*p == x0 - tk*g bitwise) or an unchanged x0.
@@ -190,6 +233,9 @@
                 const double dep = depth_finish(dgc, o, t < HPE_NS);
                 const double tot = wave_sum((al * o.lambda + dep) + co);  // as block_sum1
                 if (l == 0) rs.red[w][0] = tot;
+                // runner: the polling wave has no gradient point; its load returns meanwhile
+                [[maybe_unused]] unsigned long long pg = 0;
+                if constexpr (runner) if (w == SPEC_PW) pg = spec_poll_issue(sp);
                 head();
                 __syncthreads();  // matchId complete, the corr partial sums in red
                 if (small) load_frozen_pts(fpts, cv, match, l);
@@ -205,7 +251,12 @@
                     if (RIGID) f = f + rs.rg.C;
                     if (l == 0) rs.fg[w] = f;
                 }
+                if constexpr (runner) if (w == SPEC_PW) spec_poll_take(*ssm_p, pg, sp_ep, sp_seq);
                 __syncthreads();
+                if constexpr (runner) {
+                    verdict = __builtin_amdgcn_readfirstlane(ssm_p->verdict);  // decides exits (§7)
+                    if (verdict != 0) break;
+                }
             }
             ++evals;
             sc.lap(20);
@@ -233,9 +284,10 @@
             const double gp = (blk == 0) ? (q0 + q2) + q1 : q1 + (q0 + q2);
             // goldstein(x0, grad, matchId, f_k, optfunc, tk, 30)
             // goldstein(x0, grad, matchId, f_k, optfunc, tk, 30), then x0 = x0 - tk*grad
-            const double tk = gold_tree<MW, HPE_GOLD_POLICY, true, RIGID>(
+            const double tk = gold_tree<MW, HPE_GOLD_POLICY, true, RIGID, runner>(
                 rs, o, cv, H, match, fk, gp, pl, gl, evals, nullptr, Xt, &ml, &mwflag,
-                small ? &fpts : nullptr, blk, &md2_l);
+                small ? &fpts : nullptr, blk, &md2_l, &spoll, &verdict);
+            if constexpr (runner) if (verdict != 0) break;  // (uniform: gold_tree's readfirstlane)
             sc.lap(22);
             if (tk == 0) cnt += 1;
             // tol = sqrt(sum(grad % grad)): arrayops::accumulate (two accumulators)
@@ -246,7 +298,43 @@
             REF_TS(rs.ts_n, 5);
             sc.lap(23);
         }
+        if constexpr (SPEC && !runner) if (blk == 0) {
+            // the rotation block is over.  Its last search failed (cnt): x0 is the pose the
+            // runner got with that search's message, so its translation block is this one's
+            REF_TS(rs.ts_n, 6);
+            if (w == 0) {
+                const bool ok = spec_commit(sp, *ssm_p, (sp_ep << 5) | (unsigned)sp_seq, cnt >= 1);
+                if (l == 0) ssm_p->verdict = ok ? 1 : 0;
+            }
+            __syncthreads();
+            if (__builtin_amdgcn_readfirstlane(ssm_p->verdict)) {  // decides the block below (§7)
+                if (t < 3) rs.x0[3 + t] = ssm_p->res[t];
+                evals += __builtin_amdgcn_readfirstlane(ssm_p->evals);
+                __syncthreads();
+                break;
+            }
+        }
     }
+    if constexpr (runner) {
+        // a finished block waits for the leader's word; a dropped one has it already
+        if (verdict == 0) verdict = spec_wait(sp, *ssm_p, sp_ep, sp_seq, true);
+        if (verdict > 0) {  // a newer x0: start over from it
+            __syncthreads();
+            spec_take_x0(*ssm_p, rs.x0);
+            sp_seq = verdict;
+            verdict = 0;
+            evals = 0;
+            base_valid = false;
+            goto spec_again;
+        }
+        if (verdict == 0 && w == 0)  // committed: hand the block back
+            spec_result(sp, (sp_ep << 5) | (unsigned)sp_seq, rs.x0, evals);
+    }
+    if constexpr (SPEC) {  // this workgroup's launch is over (visible at the kernel's end)
+        if (t == 0)
+            __hip_atomic_store(sp.epoch + (runner ? 32 : 0), sp_ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (runner) return;  // the leader alone writes the call's outputs
     if (MW) mw_publish(ml, rs, MW_JOB_EXIT, 0);
     REF_TS(rs.ts_n, 7);
     // a timed-out multi-workgroup refine has no defined result: the pose becomes NaN, so

@@ -114,6 +114,18 @@ class Context:
     def refine_exact(self, exact: bool):
         self.check(self.lib.hpe_set_refine_exact(self.h, 1 if exact else 0))
 
+    @property
+    def refine_spec(self) -> bool:
+        """True (default): the refine launch of clouds of at most 2048 points carries a second
+        workgroup that runs the translation block ahead of a failing rotation search
+        (hpe_set_refine_spec); False: the one-workgroup form.  The results are the same bit
+        for bit."""
+        return bool(self.lib.hpe_get_refine_spec(self.h))
+
+    @refine_spec.setter
+    def refine_spec(self, on: bool):
+        self.check(self.lib.hpe_set_refine_spec(self.h, 1 if on else 0))
+
     def store_frame(self, slot, depth_cm, dt, cloud, scale, dtmax, K):
         depth_cm = np.ascontiguousarray(depth_cm, dtype=np.float64)
         dt = np.ascontiguousarray(dt, dtype=np.float32)

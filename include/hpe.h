@@ -248,6 +248,18 @@ int hpe_refine_init_pose(hpe_ctx *ctx, double x0[26], int32_t *evals_out);
 int hpe_set_refine_exact(hpe_ctx *ctx, int exact);
 int hpe_get_refine_exact(const hpe_ctx *ctx);
 
+/* Speculated translation block of refine_init_pose on clouds of at most 2048 points (every
+ * refine of this context, the tracking loops included).  on = 1 (default): the refine launch
+ * carries a second workgroup that runs the translation block (theta3..5) from the pose of
+ * every rotation-block line search while that search runs; when the rotation block ends on a
+ * failing search, which leaves the pose unchanged, the result is taken from it instead of
+ * being computed after the search.  The pose and the evaluation count are bit for bit those
+ * of on = 0, the one-workgroup form; every wait is bounded and falls back to it (DESIGN.md
+ * §4.3).  The environment variable HPE_REFINE_SPEC=0/1 sets the default at hpe_create.
+ * Cached tracking graphs are rebuilt on change. */
+int hpe_set_refine_spec(hpe_ctx *ctx, int on);
+int hpe_get_refine_spec(const hpe_ctx *ctx);
+
 /* One tracked frame of test_full (testmodel.cpp:124-138) on the selected frame:
  * [refine_init_pose] -> pso_evolve -> cost = cal_cost(bestp) -> x0 = bestp.
  * x0_inout: 26 doubles (host).  cost_out optional. */

@@ -2,7 +2,13 @@
 timelines build (libhpe_rts.so, s_memrealtime at 100 MHz), over pipelined frames.
 Phases: corr = cal_cost2 with new correspondences, grad = the six central differences,
 gold = one speculated Goldstein round, glue = the rest of an iteration.
-Usage: python tools/ref_ts.py [frames] [P]"""
+Per frame it also reports how the rotation block (dims 0..2) ended, how long its last line
+search took (the whole iteration, and its Goldstein rounds alone) and how long the
+translation block after it took.  The block boundary is the timeline's phase-6 entry where
+the build logs one; otherwise it is inferred from the build's Goldstein decision log (a block
+ends at its first failing search, and the translation block always runs at least one search),
+which leaves the boundary unknown in frames whose rotation block ended on tol / iter.
+Usage: python tools/ref_ts.py [frames] [P] [library file in the package directory]"""
 import ctypes as C
 import sys
 from collections import defaultdict
@@ -17,10 +23,13 @@ sys.path.insert(0, str(ROOT / "hand-pose-estimation_amd"))
 import hpe  # noqa: E402
 from hpe import _lib, synth  # noqa: E402
 
-lib = _lib.load(ROOT / "hand-pose-estimation_amd" / "libhpe_rts.so")  # make timelines
+LIBNAME = sys.argv[3] if len(sys.argv) > 3 else "libhpe_rts.so"  # make timelines
+lib = _lib.load(ROOT / "hand-pose-estimation_amd" / LIBNAME)
 _lib._lib = lib
 lib.hpe_debug_ref_ts.restype = C.c_int
 lib.hpe_debug_ref_ts.argtypes = [C.POINTER(C.c_uint64)]
+lib.hpe_debug_gold_log.restype = C.c_int
+lib.hpe_debug_gold_log.argtypes = [C.POINTER(C.c_uint64), C.c_int]
 nfr = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 P = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 RT = 16384
@@ -35,12 +44,16 @@ st = torch.zeros(27, dtype=torch.float64, device="cuda:0")
 st[:26] = torch.from_numpy(poses[0])
 ctx.pipeline_begin(raw[0])
 buf = np.zeros(RT, dtype=np.uint64)
+glog = np.zeros(257, dtype=np.uint64)
+blocks = []  # per frame: (how the rotation block ended, its last search us, Goldstein part us,
+             #             translation block us or None)
 dur = defaultdict(list)
 per_frame = []
 for f in range(nfr + 3):
     ctx.track_pipelined(P, 1, st.data_ptr(), raw[f + 1])
     ctx.check(lib.hpe_sync(ctx.h))
     lib.hpe_debug_ref_ts(buf.ctypes.data_as(C.POINTER(C.c_uint64)))
+    lib.hpe_debug_gold_log(glog.ctypes.data_as(C.POINTER(C.c_uint64)), len(glog))
     if f < 3:
         continue
     ent = [(int(v) >> 8, int(v) & 0xff) for v in buf if v]
@@ -71,6 +84,35 @@ for f in range(nfr + 3):
             dur["glue"].append((t - last[4]) / 100.0 if 4 in last else 0.0)
         last[ph] = t
     per_frame.append(((ent[-1][0] - ent[0][0]) / 100.0, iters, rounds))
+    # the line searches of the frame: (iteration start, gradient done, iteration end)
+    its, cur, mark = [], None, None
+    for t, ph in ent:
+        if ph == 1:
+            cur = [t, None, None]
+        elif ph == 3 and cur:
+            cur[1] = t
+        elif ph == 5 and cur:
+            cur[2] = t
+            its.append(cur)
+            cur = None
+        elif ph == 6 and mark is None:
+            mark = len(its)  # searches of the rotation block
+    ns = min(int(glog[0]), len(glog) - 1)
+    acc = [(int(v) >> 40) & 1 for v in glog[1:1 + ns]]
+    fails = [i for i, a in enumerate(acc) if not a]
+    k = None  # index of the rotation block's last search
+    if mark is not None and 0 < mark <= len(acc):
+        k = mark - 1
+        how = "fail" if not acc[k] else "tol/iter"
+    elif len(acc) == len(its) and (len(fails) == 2 or (len(fails) == 1 and fails[0] != len(acc) - 1)):
+        k, how = fails[0], "fail"
+    else:
+        how = "tol/iter"
+    if k is not None and k < len(its):
+        t1, t3, t5 = its[k]
+        blocks.append((how, (t5 - t1) / 100.0, (t5 - t3) / 100.0, (ent[-1][0] - t5) / 100.0))
+    else:
+        blocks.append((how, None, None, None))
 for k, v in dur.items():
     v = np.array(v)
     print(f"{k:11s} n {len(v):5d}  median {np.median(v):7.2f} us  mean {v.mean():7.2f} us  "
@@ -78,3 +120,14 @@ for k, v in dur.items():
 pf = np.array(per_frame)
 print(f"refine per frame: {pf[:, 0].mean():.1f} us, {pf[:, 1].mean():.1f} iterations, "
       f"{pf[:, 2].mean():.1f} Goldstein rounds")
+print("frame  rotation block ended  last search us  (Goldstein part)  translation block us")
+for i, (how, ls, gs, tb) in enumerate(blocks):
+    print(f"{i:5d}  {how:20s}  " + (f"{ls:14.2f}  {gs:16.2f}  {tb:20.2f}" if ls is not None
+                                    else f"{'n/a':>14s}  {'n/a':>16s}  {'n/a':>20s}"))
+fl = np.array([b[1:] for b in blocks if b[0] == "fail" and b[1] is not None])
+nf = len(fl)
+print(f"rotation block ended on a failing search in {nf} of {len(blocks)} frames")
+if nf:
+    print(f"  its last search: mean {fl[:, 0].mean():.2f} us (Goldstein rounds {fl[:, 1].mean():.2f} us); "
+          f"over all frames {fl[:, 0].sum() / len(blocks):.2f} us per frame")
+    print(f"  the translation block after it: mean {fl[:, 2].mean():.2f} us")
