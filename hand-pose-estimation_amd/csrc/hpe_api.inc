@@ -369,6 +369,7 @@ struct hpe_ctx {
         // in a depth unit (mm per count) that the begin writes to d_unit; a u16 frame fills the
         // first half of the lane's pinned buffer
         bool u16 = false;
+        float unit_mm = 1.f;  // the host's copy of *d_unit (the locate kernel takes it by value)
         float *d_unit = nullptr;
         size_t frame_bytes() const {
             return (u16 ? sizeof(uint16_t) : sizeof(float)) * (size_t)HPE_IMG_H * HPE_IMG_W;
@@ -390,6 +391,23 @@ struct hpe_ctx {
         int *d_streak = nullptr;                   // [HPE_BATCH_MAX]
         RepPar *d_par = nullptr;
     } rep;
+    // lane location (hpe_locate_depth, hpe_batch_pipeline_locate): allocated by the first begin
+    // with the windows on, or by the first hpe_locate_depth.
+    // Entries [0, HPE_BATCH_MAX) of d_res and d_act are the live batch's lanes, entry
+    // HPE_BATCH_MAX is hpe_locate_depth's own.  d_act is the locate-owned activity table: the
+    // locate kernel fills it, the preparation and the placement that follow are gated by it.
+    // h_tab: a slot per lane in pinned, mapped, coherent host memory (LOC_SLOT bytes: begin
+    // word, hpe_locate, end word), d_seq the lanes' locate counters; B, enq: the lane count of
+    // the last live batch begun and the locates enqueued per lane since that begin.
+    struct Locate {
+        hpe_locate *d_res = nullptr;         // [HPE_BATCH_MAX + 1]
+        int *d_act = nullptr;                // [HPE_BATCH_MAX + 1]
+        unsigned long long *d_seq = nullptr; // [HPE_BATCH_MAX]
+        char *h_tab = nullptr, *h_tab_dev = nullptr;
+        float *d_frame = nullptr;            // hpe_locate_depth's staging buffer, one frame
+        int B = 0;
+        unsigned long long enq[HPE_BATCH_MAX] = {};
+    } loc;
     // lane windows (hpe_set_batch_window): the mode, and what the next raw batch call or live
     // begin writes to the device -- init into both parities of the window table d_tab (next to
     // rb.d_tab, allocated with it), the margins and the call's focal into d_par -- after the
@@ -1273,6 +1291,11 @@ int hpe_destroy(hpe_ctx *c) {
     dfree(c->rep.d_lane_seq);
     dfree(c->rep.d_streak);
     dfree(c->rep.d_par);
+    if (c->loc.h_tab) (void)hipHostFree(c->loc.h_tab);
+    dfree(c->loc.d_res);
+    dfree(c->loc.d_act);
+    dfree(c->loc.d_seq);
+    dfree(c->loc.d_frame);
     dfree(c->d_raw);
     dfree(c->d_tmp);
     dfree(c->d_ctb);
@@ -3398,6 +3421,44 @@ int hpe_lane_joints_dev(hpe_ctx *c, int B, int n, const double *d_hist, double f
     return HPE_OK;
 }
 
+// Lane location's buffers (allocated by the first begin with the windows on, or by the first
+// hpe_locate_depth; zeroed, as a begin leaves them).
+static int ensure_locate(hpe_ctx *c) {
+    hpe_ctx::Locate &lo = c->loc;
+    if (lo.d_frame) return HPE_OK;
+    const size_t M = HPE_BATCH_MAX;
+    if (!lo.h_tab) {
+        HIPCHK(c, hipHostMalloc((void **)&lo.h_tab, (size_t)LOC_SLOT * M,
+                                hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(c, hipHostGetDevicePointer((void **)&lo.h_tab_dev, lo.h_tab, 0));
+        std::memset(lo.h_tab, 0, (size_t)LOC_SLOT * M);
+    }
+    if (!lo.d_res) HIPCHK(c, dalloc(&lo.d_res, M + 1));
+    // (zeroed on the stream: the launches that read them follow it there)
+    if (!lo.d_act) {
+        HIPCHK(c, dalloc(&lo.d_act, M + 1));
+        HIPCHK(c, hipMemsetAsync(lo.d_act, 0, sizeof(int) * (M + 1), c->stream));
+    }
+    if (!lo.d_seq) {
+        HIPCHK(c, dalloc(&lo.d_seq, M));
+        HIPCHK(c, hipMemsetAsync(lo.d_seq, 0, sizeof(unsigned long long) * M, c->stream));
+    }
+    HIPCHK(c, dalloc(&lo.d_frame, (size_t)HPE_IMG_H * HPE_IMG_W));  // the last: see hpe_set_batch_report
+    return HPE_OK;
+}
+
+// The begin's part (the stream drained): every lane's locate counter to 0, the host table cleared.
+static int begin_locates(hpe_ctx *c, int B) {
+    hpe_ctx::Locate &lo = c->loc;
+    lo.B = B;
+    std::memset(lo.enq, 0, sizeof(lo.enq));
+    if (!lo.d_frame) return HPE_OK;  // nothing allocated yet: ensure_locate zeroes what it makes
+    HIPCHK(c, hipMemsetAsync(lo.d_seq, 0, sizeof(unsigned long long) * HPE_BATCH_MAX, c->stream));
+    std::memset(lo.h_tab, 0, (size_t)LOC_SLOT * HPE_BATCH_MAX);
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+    return HPE_OK;
+}
+
 // The begin of a live batch in either frame format: u16 false, float mm frames; true, 16-bit
 // frames of unit_mm each.
 static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool u16, float unit_mm,
@@ -3440,11 +3501,15 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
     // the depth unit, as the windows' parameters: device memory, not the graphs, holds it (the
     // stream has drained)
     if (u16) HIPCHK(c, hipMemcpy(lv.d_unit, &unit_mm, sizeof(float), hipMemcpyHostToDevice));
+    lv.unit_mm = u16 ? unit_mm : 1.f;
     HIPCHK(c, hipMemsetAsync(lv.d_seq, 0, sizeof(unsigned long long), c->stream));
     __atomic_store_n(lv.h_done, 0ull, __ATOMIC_RELEASE);
     lv.enq = 0;
     lv.used_seq[0] = lv.used_seq[1] = 0;
-    if ((rc = begin_reports(c, B, focal))) return rc;
+    // lane location's buffers, while nothing is in flight: a locate call of this batch (it needs
+    // the windows on) then allocates nothing and stays asynchronous
+    if (c->win.mode != HPE_WINDOW_OFF && (rc = ensure_locate(c))) return rc;
+    if ((rc = begin_reports(c, B, focal)) || (rc = begin_locates(c, B))) return rc;
     // frame 0 of every lane: into its pinned buffer of parity 0, prepared from there
     for (int b = 0; b < B; ++b)
         if ((given >> b & 1) && depth_mm[b] != lv.h_raw[0][b])
@@ -3772,6 +3837,158 @@ int hpe_batch_pipeline_optimise(hpe_ctx *c, int P, int B, double *d_states, uint
     if ((rc = enqueue_report(c, B, d_states, lv.cur, nullptr, lanes, HPE_REPORT_INIT))) return rc;
     for (int b = 0; b < B; ++b) c->rep.enq[b] += lanes >> b & 1;
     return HPE_OK;
+}
+
+// ---------------------------------------------------------------- lane location
+static const hpe_locate_params LOC_DEFAULTS = {
+    {0, HPE_IMG_H - 1, 0, HPE_IMG_W - 1, -HUGE_VAL, HUGE_VAL}, 0.5, 12.0, 11.0, 11.0, 20, 200};
+
+int hpe_locate_defaults(hpe_locate_params *p) {
+    if (!p) return HPE_E_ARG;
+    *p = LOC_DEFAULTS;
+    return HPE_OK;
+}
+
+// One lane's parameters checked and in the kernel's form (sb = ceil(slab / bin), at most LOC_K).
+static int locate_par(hpe_ctx *c, const hpe_locate_params &p, int lane, LocPar *out) {
+    if (!(p.bin > 0) || std::isinf(p.bin))
+        return fail(c, HPE_E_ARG, "lane %d: locate bin %g is not positive and finite", lane, p.bin);
+    if (!(p.slab >= 0) || !(p.half_xy >= 0) || !(p.half_z >= 0) || std::isinf(p.slab) ||
+        std::isinf(p.half_xy) || std::isinf(p.half_z))
+        return fail(c, HPE_E_ARG, "lane %d: locate slab %g or half sizes %g, %g: negative or not "
+                    "finite", lane, p.slab, p.half_xy, p.half_z);
+    if (p.skip < 0 || p.min_pixels < 0)
+        return fail(c, HPE_E_ARG, "lane %d: locate skip %d or min_pixels %d is negative", lane,
+                    p.skip, p.min_pixels);
+    const double sb = std::ceil(p.slab / p.bin);
+    *out = LocPar{p.search.row_lo, p.search.row_hi, p.search.col_lo, p.search.col_hi,
+                  p.search.z_lo, p.search.z_hi, p.bin, p.half_xy, p.half_z,
+                  sb < (double)LOC_K ? (int)sb : LOC_K, p.skip, p.min_pixels, 0};
+    return HPE_OK;
+}
+
+int hpe_locate_depth(hpe_ctx *c, const void *frame, int u16, float unit_mm, int to_cm, double focal,
+                     const hpe_locate_params *params, hpe_locate *out) {
+    if (!c) return HPE_E_ARG;
+    if (!frame || !out) return fail(c, HPE_E_ARG, "null frame or result");
+    if (!(focal > 0) || std::isinf(focal)) return fail(c, HPE_E_ARG, "focal %g is not positive and finite", focal);
+    if (u16 && !(std::isfinite(unit_mm) && unit_mm > 0))
+        return fail(c, HPE_E_ARG, "depth unit %g mm is not finite and positive", (double)unit_mm);
+    LocLanes ln{};
+    if (int rc = locate_par(c, params ? *params : LOC_DEFAULTS, 0, &ln.par[0])) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_locate(c)) return rc;
+    hpe_ctx::Locate &lo = c->loc;
+    const size_t bytes = (u16 ? sizeof(uint16_t) : sizeof(float)) * (size_t)HPE_IMG_H * HPE_IMG_W;
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier call's kernel may still read the buffer
+    HIPCHK(c, hipMemcpy(lo.d_frame, frame, bytes, hipMemcpyHostToDevice));
+    ln.raw[0] = lo.d_frame;
+    const float unit = u16 ? unit_mm : 1.f;
+    // (entry HPE_BATCH_MAX of the record and activity tables: a live batch's entries stay as they are)
+    const auto k_locate = u16 ? k_locate_b<true> : k_locate_b<false>;
+    hipLaunchKernelGGL(k_locate, dim3(1), dim3(LOC_NT), 0, c->stream, ln, 1u, unit, to_cm ? 1 : 0, focal, (DevWindow *)nullptr, (DevWindow *)nullptr,
+                       lo.d_act + HPE_BATCH_MAX, lo.d_res + HPE_BATCH_MAX,
+                       (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, lo.d_res + HPE_BATCH_MAX, sizeof(*out), hipMemcpyDeviceToHost));
+    return HPE_OK;
+}
+
+int hpe_batch_pipeline_locate(hpe_ctx *c, int B, double *d_states, uint32_t lanes,
+                              const double *tmpl, const hpe_locate_params *params) {
+    if (!c) return HPE_E_ARG;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!d_states || !tmpl) return fail(c, HPE_E_ARG, "null device states or pose templates");
+    if (!lanes || (B < 32 && lanes >> B))
+        return fail(c, HPE_E_ARG, "lane mask 0x%x: empty, or a bit at or above B = %d", lanes, B);
+    LocLanes ln{};
+    for (int b = 0; b < B; ++b)  // the selected lanes' entries alone are read
+        if (lanes >> b & 1)
+            if (int rc = locate_par(c, params ? params[b] : LOC_DEFAULTS, b, &ln.par[b])) return rc;
+    hpe_ctx::LiveBatch &lv = c->live;
+    if (lv.cur < 0)
+        return fail(c, HPE_E_STATE, "no live batch: hpe_batch_pipeline_begin not called, or the "
+                    "batch ended");
+    if (B != lv.B) return fail(c, HPE_E_STATE, "%d lanes, the batch began with %d", B, lv.B);
+    if (c->win.mode == HPE_WINDOW_OFF)
+        return fail(c, HPE_E_STATE, "the lane windows are off: the located window would not be read "
+                    "(hpe_set_batch_window before the begin)");
+    if (lanes & ~lv.pending)
+        return fail(c, HPE_E_STATE, "lane mask 0x%x: lanes 0x%x hold no prepared frame "
+                    "(hpe_batch_pending)", lanes, lanes & ~lv.pending);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = ensure_locate(c)) return rc;
+    hpe_ctx::Locate &lo = c->loc;
+    const int cur = lv.cur, M = HPE_BATCH_MAX;
+    // the lanes' current raw frames: the pinned buffers of the parity the next track call tracks
+    for (int b = 0; b < B; ++b)
+        if (lanes >> b & 1) ln.raw[b] = lv.h_raw_dev[cur][b];
+    DevWindow *const wcur = c->win.d_tab + cur * M;
+    DevWindow *const woth = c->win.mode == HPE_WINDOW_FIXED ? c->win.d_tab + (cur ^ 1) * M : nullptr;
+    const auto k_locate = lv.u16 ? k_locate_b<true> : k_locate_b<false>;
+    hipLaunchKernelGGL(k_locate, dim3(B), dim3(LOC_NT), 0, c->stream, ln, (unsigned)lanes,
+                       lv.unit_mm, lv.to_cm, lv.focal, wcur, woth,
+                       lo.d_act, lo.d_res, lo.d_seq, (unsigned long long *)lo.h_tab_dev);
+    HIPCHK(c, hipGetLastError());
+    // the locate kernel is enqueued: it advances the selected lanes' device counters, and it and
+    // the preparation below read the pinned buffers of parity cur in place, behind everything
+    // already on the stream.  So those buffers stay in use until the NEXT track call's frame
+    // (number enq + 1, whose launches follow these) has completed: the track call after it and
+    // hpe_batch_frame_buffer wait for that number before the host refills them.
+    for (int b = 0; b < B; ++b) lo.enq[b] += lanes >> b & 1;
+    lv.used_seq[cur] = lv.enq + 1;
+    // the found lanes' current frames prepared again through their new windows: the begin's
+    // kernel in its windowed, idle-aware form, gated by the table the locate kernel filled
+    hipLaunchKernelGGL(lane_prepare_kernel(lv.u16 ? LANE_SRC_U16 : LANE_SRC_RING, true, true),
+                       dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
+                       (const PrepArgs *)lv.d_tab + cur * M, (const DevWindow *)wcur,
+                       (const int *)lo.d_act, (const float *)(lv.u16 ? lv.d_unit : nullptr),
+                       (const float *const *)nullptr, (const int *)nullptr);
+    LocTmpl tp{};
+    std::memcpy(tp.th, tmpl, sizeof(double) * HPE_DOF * (size_t)B);
+    hipLaunchKernelGGL(k_locate_place_b, dim3(B), dim3(64), 0, c->stream, tp,
+                       (const DevHand *)c->d_lane_hands, (const hpe_locate *)lo.d_res,
+                       (const int *)lo.d_act, d_states);
+    HIPCHK(c, hipGetLastError());
+    return HPE_OK;
+}
+
+// Result `seq` (>= 1) of a lane's host slot into *out: true iff the slot held exactly that
+// result, complete, for the whole copy (hpe_report::read_seq's order).
+static bool locate_read(const char *slot, uint64_t seq, hpe_locate *out) {
+    const uint64_t *w = (const uint64_t *)slot;
+    if (__atomic_load_n(w + 1 + LOC_WORDS, __ATOMIC_ACQUIRE) != seq) return false;
+    uint64_t *o = (uint64_t *)out;
+    for (int k = 0; k < LOC_WORDS; ++k) o[k] = __atomic_load_n(w + 1 + k, __ATOMIC_RELAXED);
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return __atomic_load_n(w, __ATOMIC_RELAXED) == seq;
+}
+
+int hpe_batch_locate_result(hpe_ctx *c, int lane, int timeout_ms, hpe_locate *out) {
+    if (!c) return HPE_E_ARG;
+    if (!out) return fail(c, HPE_E_ARG, "null result");
+    const hpe_ctx::Locate &lo = c->loc;
+    if (!lo.B) return fail(c, HPE_E_STATE, "no live batch has begun (hpe_batch_pipeline_begin)");
+    if (lane < 0 || lane >= lo.B)
+        return fail(c, HPE_E_ARG, "lane %d outside the batch's %d lanes", lane, lo.B);
+    const uint64_t seq = lo.enq[lane];
+    if (!seq) {  // nothing was enqueued for the lane since the begin
+        std::memset(out, 0, sizeof(*out));
+        return HPE_OK;
+    }
+    const char *slot = lo.h_tab + (size_t)LOC_SLOT * lane;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned it = 0;; ++it) {
+        if (locate_read(slot, seq, out)) return HPE_OK;
+        if ((it & 255) == 255) {
+            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(timeout_ms > 0 ? timeout_ms : 0))
+                return fail(c, HPE_E_HIP, "lane %d: locate result %llu did not complete in %d ms", lane,
+                            (unsigned long long)seq, timeout_ms);
+            std::this_thread::yield();
+        }
+    }
 }
 
 int hpe_profile_enable(hpe_ctx *c, int on) {

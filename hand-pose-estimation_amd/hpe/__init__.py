@@ -14,7 +14,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _lib, report, window
+from . import _lib, locate, report, window
 from ._lib import HpeError, ptr
 
 __all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "scaled_hand",
@@ -390,6 +390,73 @@ class Context:
         self.check(self.lib.hpe_batch_pipeline_optimise(
             self._h, int(num_p), B, C.c_void_p(d_states_ptr), int(lanes),
             C.c_void_p(d_trace_ptr) if d_trace_ptr else None))
+
+    # ---- lane location (hpe_locate_depth, hpe_batch_pipeline_locate)
+    @staticmethod
+    def _locate_params(params):
+        p = locate.as_params(params)
+        return _lib.LocateParams(_lib.Window(*p.search), p.bin, p.slab, p.half_xy, p.half_z,
+                                 p.skip, p.min_pixels)
+
+    @staticmethod
+    def _locate_result(r, raw):
+        if raw:
+            return r
+        return locate.Result(int(r.found), int(r.k_near), int(r.m1), int(r.m2), tuple(r.px),
+                             tuple(r.centre), window.as_window(r.window))
+
+    def locate_depth(self, depth, focal=241.42, params=None, to_cm=True, unit_mm=None, raw=False):
+        """The location rule on one host frame, on the device (hpe_locate_depth; synchronises):
+        float32 mm pixels, or uint16 pixels of unit_mm each.  params: an hpe.locate.Params (None:
+        the library's defaults).  Returns an hpe.locate.Result, which equals
+        hpe.locate.locate(...) on the same arguments bit for bit (raw: the hpe._lib.Locate)."""
+        d = np.asarray(depth)
+        u16 = unit_mm is not None
+        if u16 != (d.dtype == np.uint16):
+            raise TypeError("locate_depth: uint16 frames come with their unit_mm, float frames "
+                            "without one (nothing is converted silently)")
+        d = np.ascontiguousarray(d, dtype=np.uint16 if u16 else np.float32).reshape(IMG_H, IMG_W)
+        lp = self._locate_params(params) if params is not None else None
+        r = _lib.Locate()
+        self.check(self.lib.hpe_locate_depth(
+            self._h, C.c_void_p(d.ctypes.data), int(u16), float(unit_mm) if u16 else 1.0,
+            int(to_cm), float(focal), C.byref(lp) if lp is not None else None, C.byref(r)))
+        return self._locate_result(r, raw)
+
+    def batch_pipeline_locate(self, d_states_ptr, templates, lanes=None, params=None):
+        """Locate the hand of the selected pending lanes of the live batch in their current raw
+        frames, on the device and asynchronously (hpe_batch_pipeline_locate): a found lane gets
+        its window (the table's current parity; both under "fixed"), its current frame prepared
+        again through it, and its row of d_states_ptr = its template (one 26-pose per lane, or
+        one for all) moved onto the located centre (hpe.locate.place).  A lane that is not
+        found, or not selected, stays untouched.  lanes: bit b = lane b; None: every lane in
+        lockstep, batch_pending() under the "free" pacing.  params: None (the defaults), one
+        hpe.locate.Params for all lanes, or a list of one per lane."""
+        if not d_states_ptr:
+            raise ValueError("batch_pipeline_locate needs the device states")
+        B = getattr(self, "_live_lanes", 0) or 1  # (1 without a begin: the library reports it)
+        if lanes is None:
+            free = getattr(self, "_pacing", _lib.PACING_LOCKSTEP) == _lib.PACING_FREE
+            lanes = self.batch_pending() if free else (1 << B) - 1
+        t = np.asarray(templates, dtype=np.float64)
+        t = np.ascontiguousarray(np.broadcast_to(t.reshape(-1, 26) if t.ndim > 1 else t[:26], (B, 26)))
+        arr = None
+        if params is not None:
+            ps = ([params] * B if isinstance(params, locate.Params) else list(params))
+            if len(ps) != B:
+                raise ValueError(f"batch_pipeline_locate: {len(ps)} parameter sets for {B} lanes")
+            arr = (_lib.LocateParams * B)(*[self._locate_params(p) for p in ps])
+        self.check(self.lib.hpe_batch_pipeline_locate(
+            self._h, B, C.c_void_p(d_states_ptr), int(lanes), ptr(t, C.c_double), arr))
+
+    def batch_locate_result(self, lane, timeout_ms=2000, raw=False):
+        """Lane `lane`'s newest locate result (hpe_batch_locate_result): waits, at most
+        timeout_ms, for the last locate enqueued for the lane, without synchronising the stream;
+        raises on expiry (HPE_E_HIP).  Returns (seq, hpe.locate.Result) -- seq counts the lane's
+        locates since the begin, 0: none yet -- or the hpe._lib.Locate with raw."""
+        r = _lib.Locate()
+        self.check(self.lib.hpe_batch_locate_result(self._h, int(lane), int(timeout_ms), C.byref(r)))
+        return r if raw else (int(r.seq), self._locate_result(r, False))
 
     def set_batch_form(self, form):
         """The form of pso_evolve in track_batch, track_raw_batch and the live batch

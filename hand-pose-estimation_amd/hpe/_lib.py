@@ -62,6 +62,20 @@ class ReportWatch(C.Structure):
     _fields_ = [("cost_max", C.c_double), ("n_min", C.c_int32), ("streak", C.c_int32)]
 
 
+class LocateParams(C.Structure):
+    """hpe_locate_params: 72 bytes."""
+    _fields_ = [("search", Window), ("bin", C.c_double), ("slab", C.c_double),
+                ("half_xy", C.c_double), ("half_z", C.c_double), ("skip", C.c_int32),
+                ("min_pixels", C.c_int32)]
+
+
+class Locate(C.Structure):
+    """hpe_locate: 104 bytes, every field naturally aligned."""
+    _fields_ = [("seq", C.c_uint64), ("lane", C.c_int32), ("found", C.c_int32),
+                ("k_near", C.c_int32), ("m1", C.c_int32), ("m2", C.c_int32), ("pad", C.c_int32),
+                ("px", C.c_double * 2), ("centre", C.c_double * 3), ("window", Window)]
+
+
 # name -> (restype, argtypes); the list IS the exported C ABI (tests check it against
 # include/hpe.h)
 SIGNATURES = {
@@ -121,6 +135,12 @@ SIGNATURES = {
     "hpe_batch_lost": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "hpe_lane_joints_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                       C.c_void_p, C.c_void_p]),
+    "hpe_locate_defaults": (C.c_int, [C.POINTER(LocateParams)]),
+    "hpe_locate_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                                   C.c_double, C.POINTER(LocateParams), C.POINTER(Locate)]),
+    "hpe_batch_pipeline_locate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, dp,
+                                            C.POINTER(LocateParams)]),
+    "hpe_batch_locate_result": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Locate)]),
     "hpe_build_spheres":(C.c_int, [C.c_void_p, dp, C.c_int, dp, dp]),
     "hpe_eval_costs": (C.c_int, [C.c_void_p, dp, C.c_int, C.c_int, dp, ip]),
     "hpe_cal_cost2": (C.c_int, [C.c_void_p, dp, ip, C.c_int, dp, dp]),

@@ -39,3 +39,28 @@ def load_sequence(ctx: Context, n_frames: int, seed: int = 0, downsample: bool =
                         o["dtmax"], o["K"])
         sizes.append(len(o["cloud"]))
     return poses, sizes
+
+
+def rig_scene(hand_mm, wrist_cm, focal: float = 241.42, wall_mm: float = 800.0,
+              arm_behind_cm: float = 1.0, arm_half_cm: float = 2.5, speckle: int = 15,
+              speckle_mm: float = 150.0, seed: int = 0) -> np.ndarray:
+    """What a camera of a rig sees around a rendered hand (240x320 float32 mm, 0 background): a
+    wall at wall_mm behind everything, a forearm band from the wrist (camera coordinates, cm: a
+    pose's theta 3..5) down to the bottom edge, arm_behind_cm behind the wrist and 2 *
+    arm_half_cm wide, and `speckle` single pixels at speckle_mm scattered over the background
+    (seeded).  The hand's own pixels stay as rendered: the input of the lane location's tests
+    and bench."""
+    hand = np.asarray(hand_mm, dtype=np.float32).reshape(240, 320)
+    on = hand > 0
+    out = np.where(on, hand, np.float32(wall_mm)).astype(np.float32)
+    x, y, z = (float(v) for v in wrist_cm)
+    col, row = 160.0 + focal * x / z, 120.0 + focal * y / z
+    half = focal * arm_half_cm / (z + arm_behind_cm)
+    r = np.arange(240)[:, None]
+    c = np.arange(320)[None, :]
+    arm = (r >= row) & (np.abs(c - col) <= half) & ~on
+    out[arm] = np.float32((z + arm_behind_cm) * 10.0)
+    free = np.flatnonzero(~on & ~arm)
+    rng = np.random.default_rng(seed)
+    out.ravel()[rng.choice(free, size=speckle, replace=False)] = np.float32(speckle_mm)
+    return out

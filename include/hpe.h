@@ -740,6 +740,106 @@ int hpe_batch_lost(hpe_ctx *ctx, uint32_t *mask_out);
 int hpe_lane_joints_dev(hpe_ctx *ctx, int B, int n, const double *d_hist, double focal,
                         double *d_joints, double *d_px);
 
+/* Lane location: where the hand is in a lane's raw depth frame, found on the device -- the first
+ * window and pose of a rig's lane, and both again for a lane whose report says LOST.  A camera
+ * delivers neither a segmented hand nor a pose: without this the application pulls the frame to
+ * the host, segments it there and pushes a window and a pose back.  With it the loop closes on the
+ * device: begin -> locate -> optimise -> track -> LOST -> locate -> optimise -> track.
+ *
+ * The location rule (hpe/locate.py is the same rule in numpy, and the device result equals it bit
+ * for bit, doubles included).  Input: one raw 240x320 frame, float mm or 16-bit pixels of unit_mm
+ * each (rv = (float)u * unit_mm, the u16 batch's rule), to_cm, focal and hpe_locate_params.
+ * Z = to_cm ? (double)rv / 10. : (double)rv, the preparation's own expression.  A pixel is VALID
+ * iff rv is finite, rv > 0 and it lies inside `search` in row, column and Z (the masking rule's
+ * comparisons, every bound inclusive).  Its depth bin is k = min(K-1, (int)floor(Z / bin)),
+ * K = 2048 (one fp64 division; the clamp is made in fp64, before the conversion).
+ *   1. Histogram of k over the valid pixels; k_near = the smallest k whose cumulative count
+ *      exceeds `skip` (that many nearest pixels are ignored: speckle).  None: found = 0, and
+ *      k_near = -1.
+ *   2. Pass 1: the valid pixels with k_near <= k <= k_near + sb, sb = (int)ceil(slab / bin):
+ *      integer sums m1, Sr, Sc, Sk; r1 = (double)Sr / (double)m1, c1 likewise,
+ *      z1 = ((double)Sk / (double)m1 + 0.5) * bin.
+ *   3. The box around (r, c, z): hx = (focal * half_xy) / z; rows ceil(r - hx) .. floor(r + hx),
+ *      columns likewise, each bound clamped in fp64 to the image and to `search` before its
+ *      conversion to int, as the pose rule clamps:
+ *        row_lo = (int)min(max(ceil(r - hx), max(0, search.row_lo)), 240)
+ *        row_hi = (int)min(max(floor(r + hx), -1), min(239, search.row_hi))     (columns: 320, 319)
+ *      depth max(z - half_z, search.z_lo) .. min(z + half_z, search.z_hi).
+ *   4. Pass 2: the valid pixels inside the box around (r1, c1, z1), by row, column and Z: sums m2,
+ *      Sr, Sc, Sk.  m2 < min_pixels (or m2 == 0): found = 0.  Otherwise (r2, c2, z2) as in pass 1.
+ *   5. found = 1; window = the box around (r2, c2, z2); px = {c2, r2}; centre =
+ *      {((c2 - 160.0) * z2) / focal, ((r2 - 120.0) * z2) / focal, z2}: camera coordinates, the
+ *      inverse of the reports' pixel rule.
+ * A result that is not found carries the counts it reached (k_near, m1, m2) and zeros for px,
+ * centre and window.  The rule finds the object nearest the camera inside `search`: keeping the
+ * body and the other hand out of `search` is the caller's part, as it is for the lane windows.
+ * hpe_locate_defaults fills {the whole frame, 0.5, 12, 11, 11, 20, 200} (cm with to_cm): untuned
+ * values, tried on rendered scenes only (DESIGN.md 4.7 "Lane location").
+ *
+ * The placement rule.  Given a pose T[26] -- the caller's guess of rotation and digits, the
+ * reference's x0 for instance -- the lane's row becomes T with theta 3..5 replaced by
+ * T[3..5] + (centre - cen), cen the mean of the 48 sphere centres of T under the lane's hand in
+ * camera coordinates (hpe_build_spheres' centres with y and z negated back, summed in sphere order,
+ * divided by 48).  theta 3..5 is a camera-frame translation, so the row's sphere centroid lands on
+ * centre (to the FK's 1e-9 cm).  The row's 27th entry is left as it is.
+ *
+ * hpe_locate_depth: the rule alone on one host frame (u16 != 0: 16-bit pixels), synchronous,
+ * through a staging buffer of the context; params == NULL: the defaults; out->seq and out->lane
+ * are 0.  Single-sequence users then mask with hpe/window.py: apply.
+ *
+ * hpe_batch_pipeline_locate: on a live batch, for the lanes of `lanes` (bit b = lane b), which must
+ * hold a prepared frame (hpe_batch_pending).  Asynchronous on hpe_stream(ctx), three launches:
+ *   1. k_locate_b, one workgroup per lane, on the lane's CURRENT raw frame -- the pinned buffer of
+ *      the parity the next track call tracks, read in place.  It stays intact until the track call
+ *      after that, in-place-filled buffers included: the locate call marks the buffers in use
+ *      until the next track call's frame has completed, so a host that runs ahead of the device
+ *      waits there (that track call's copy, hpe_batch_frame_buffer) exactly as it waits for a
+ *      frame that is still being prepared.
+ *   2. A found lane's window goes into the window table: both parities under HPE_WINDOW_FIXED, the
+ *      current parity under HPE_WINDOW_FOLLOW (the next call's pose rule takes over as ever).  Its
+ *      current frame is PREPARED AGAIN through that window (the begin's preparation kernel, gated
+ *      by an activity table the locate kernel filled).
+ *   3. The placed row is written to d_states + 27 b.  tmpl: host, B x 26, read before return.
+ *   params: host, B entries, or NULL for the defaults in every lane; only the selected lanes'
+ *   entries are read and checked.
+ * An unselected lane, and a selected lane that is not found, stays untouched: its window in both
+ * parities, its prepared frame, its row, its pending state and its hand-off counters, bit for bit.
+ * Nothing of the batch's own state changes (parity, pending mask, frame numbers), and no tracking
+ * graph is captured or invalidated: the windows live in device memory.
+ *
+ * hpe_batch_locate_result: lane `lane`'s newest result, from a small table in pinned mapped host
+ * memory that the locate kernel publishes with the report ring's begin / end words; seq counts the
+ * lane's locates since the begin.  It waits, at most timeout_ms, for the last locate enqueued for
+ * the lane (none since the begin: out->seq == 0 at once) and does not synchronise the stream;
+ * HPE_E_HIP on expiry.
+ *
+ * Refused, and a refusal changes nothing: a null pointer, bin <= 0 or not finite, a negative or
+ * non-finite slab or half size, a negative skip or min_pixels, focal <= 0 or not finite, a u16
+ * unit_mm not finite or <= 0, lanes == 0 or a bit at or above B, a lane outside the batch --
+ * HPE_E_ARG; no live batch or a B other than the begin's, window mode OFF (the table is not read
+ * then), a selected lane that holds no prepared frame -- HPE_E_STATE. */
+typedef struct hpe_locate_params {
+    hpe_window search;      /* where to look: rectangle and depth range, bounds inclusive */
+    double bin;             /* depth quantum in the converted unit (cm with to_cm), > 0 */
+    double slab;            /* pass 1: depth extent behind the nearest depth */
+    double half_xy, half_z; /* half sizes of the hand box */
+    int32_t skip;           /* that many nearest valid pixels are ignored (speckle), >= 0 */
+    int32_t min_pixels;     /* fewer pixels in the box: not found */
+} hpe_locate_params;
+typedef struct hpe_locate {     /* 104 bytes, every field naturally aligned */
+    uint64_t seq;               /* the lane's locates since the begin, from 1 (hpe_locate_depth: 0) */
+    int32_t lane, found, k_near, m1, m2, pad;
+    double px[2];               /* {column, row} of the located centre */
+    double centre[3];           /* camera coordinates, converted unit */
+    hpe_window window;
+} hpe_locate;
+int hpe_locate_defaults(hpe_locate_params *p);
+int hpe_locate_depth(hpe_ctx *ctx, const void *frame, int u16, float unit_mm, int to_cm,
+                     double focal, const hpe_locate_params *params, hpe_locate *out);
+int hpe_batch_pipeline_locate(hpe_ctx *ctx, int B, double *d_states, uint32_t lanes,
+                              const double *tmpl, const hpe_locate_params *params);
+int hpe_batch_locate_result(hpe_ctx *ctx, int lane, int timeout_ms, hpe_locate *out);
+
 /* Kernel timing with HIP events on the context stream (bench instrumentation).
  * While enabled, every dispatch of the profiled kernels is launched through
  * hipExtLaunchKernel with a start/stop event pair (dispatch-packet timestamps: the
