@@ -881,6 +881,12 @@ __device__ __forceinline__ void eval_nodes(RefineSm &rs, int nn, const DevObs &o
 }
 
 // f_k = cal_cost2(x0, matchId, true) with the spheres of x0 in rs.base.
+// The collision sum of a refine is one constant: the refine moves theta0..5 only, a rigid
+// motion of the whole hand, so co here, in eval_nodes' MW branch and in frozen_head as the
+// refine calls it (rs.rg.C in the rigid form) has the same value in every evaluation, cancels
+// in every Goldstein test, and the call reports no cost.  A wrong pair map at these sites
+// cannot change a result, so no test pins them; tests/test_gpu_collision.py pins collide_term
+// through eval_block and frozen_head through pso_optimise's descent.
 template <bool MW, bool RIGID = false, class CV>
 __device__ __forceinline__ double eval_corr(RefineSm &rs, const DevObs &o, const CV &cv,
                                             const DevHand *__restrict__ H, int32_t *__restrict__ match,

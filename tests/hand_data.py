@@ -44,6 +44,35 @@ def trajectory(n_frames, seed=0, revert=0.0):
     return np.array(poses)
 
 
+# (radius scale, spread, seed) of the self-collision cases.  Four of them (scale 1.5 and the
+# spread-3 pose of scale 4) are a greedy cover in which each of the 144 sphere pairs is active
+# in one case and inactive in another: spread 6 is there for the pair of the middle and ring
+# fingers' base spheres, which scale 1.5 separates only in a splayed hand.  Their alignment
+# terms are huge, so three poses near the centre follow for each of the scales 2, 3 and 4, in
+# which the collision term is at least 12 % of the cost on the frame rendered at the centre
+# (tests/test_collision_pairs.py asserts the cover, tests/test_gpu_collision.py the share).
+COLLISION_CENTRE = (3, 5, 2)  # trajectory(3, seed=5)[2]
+COLLISION_CASES = (
+    (1.5, 0.4, 1000), (1.5, 6.0, 1011), (1.5, 6.0, 1037),
+    (2.0, 0.4, 1007), (2.0, 0.4, 1016), (2.0, 0.4, 1027),
+    (3.0, 0.4, 1000), (3.0, 1.0, 1007), (3.0, 1.0, 1027),
+    (4.0, 0.4, 1000), (4.0, 1.0, 1020), (4.0, 1.0, 1039), (4.0, 3.0, 1038),
+)
+
+
+def collision_centre():
+    n, seed, k = COLLISION_CENTRE
+    return trajectory(n, seed=seed)[k]
+
+
+def collision_cases():
+    """[(radius_scale, theta), ...]: fat-sphere hands (the reference radii times radius_scale,
+    as hpe.scaled_hand(1.0, radius_scale)) in seeded poses around collision_centre()."""
+    centre = collision_centre()
+    return [(k, random_thetas(np.random.default_rng(seed), 1, x0=centre, spread=spread)[0])
+            for k, spread, seed in COLLISION_CASES]
+
+
 def tie_replay(oracle, ora_hand, obs, x0, evals, rigid, tie, pose=None, depth=2):
     """Explain a refine that took `evals` evaluations where the oracle's run from x0 took
     another number: replay the oracle with near-tie decisions (relative margin < tie)
