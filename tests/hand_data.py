@@ -21,6 +21,96 @@ def geometry_cm():
     return np.array(d["hgeo_mm"]) / 10.0, np.array(d["rad_mm"]) / 10.0
 
 
+FAMILY = ("ref", "V", "small", "large", "uneven", "mirror", "zero_sp", "right_angle")
+
+
+def hand_family():
+    """{name: (geo_cm (20,), radii_cm (48,), cmc_deg (5,), spacing_cm (5,))}: the hands that the
+    oracle comparisons of tests/test_hand_family.py and tests/test_gpu_hand_family.py run on.
+    The reference hand hides the branches the others reach: a middle finger whose spacing is not
+    0 (uneven), spacings of the other sign (mirror) and all 0 (zero_sp), CMC angles at and across
+    90 degrees (right_angle, uneven), lengths and radii that are no common multiple of the
+    reference's (uneven), and V, the hand of tests/test_gpu_batch_hands.py."""
+    import oracle_np
+    geo, rad = geometry_cm()
+    cmc, sp = np.array(oracle_np.CMC), np.array(oracle_np.SPACING)
+    return {
+        "ref": (geo, rad, cmc, sp),
+        "V": (geo * 1.05, rad * 0.95, cmc + np.array([1.5, -1.0, 0.5, 0.75, -0.5]),
+              sp + np.array([0.05, -0.04, 0.03, 0.02, -0.06])),
+        "small": (geo * 0.7, rad * 0.7, cmc, sp * 0.7),
+        "large": (geo * 1.3, rad * 1.25, cmc, sp * 1.3),
+        "uneven": (geo * np.repeat((1.2, 0.8, 1.1, 0.9, 1.15), 4) * np.tile((1, 0.9, 1.1, 1.2), 5),
+                   rad * np.linspace(0.8, 1.3, 48), cmc + np.array([-12.0, 9, -7, 6, 11]),
+                   sp + np.array([0.4, -0.3, 0.5, -0.6, 0.7])),
+        "mirror": (geo, rad, cmc, -sp),
+        "zero_sp": (geo, rad, cmc, np.zeros(5)),
+        "right_angle": (geo, rad, np.array([150.0, 90, 90, 90, 45]), sp),
+    }
+
+
+def family_gpu_hand(entry, params_only=False):
+    """A family entry as hpe.handmodel (a context of its own) or, params_only, as the
+    hpe._lib.HandParams that hpe_set_batch_hands takes (no context)."""
+    import hpe
+    geo, rad, cmc, sp = entry
+    if not params_only:
+        return hpe.handmodel(geo, sp, hpe.TB_SPHERES, hpe.FG_SPHERES, cmc, rad)
+    p = hpe._lib.HandParams()
+    p.geo_cm[:] = [float(x) for x in geo]
+    p.radii_cm[:] = [float(x) for x in rad]
+    p.cmc_deg[:] = [float(x) for x in cmc]
+    p.spacing_cm[:] = [float(x) for x in sp]
+    p.tb_spheres[:] = hpe.TB_SPHERES
+    p.fg_spheres[:] = hpe.FG_SPHERES
+    return p
+
+
+def family_oracle_hands(oracle, entry):
+    """A family entry as (C oracle hand, numpy oracle hand)."""
+    import oracle_np
+    geo, rad, cmc, sp = entry
+    return oracle.hand(geo, rad, cmc, sp), oracle_np.Hand(geo, rad, cmc, sp)
+
+
+def family_poses():
+    """The FK poses of the family tests: X0, the zero pose, a global rotation of (180, -180, 90),
+    the lower and the upper bound, and 12 seeded draws of spread 3 (17 x 26)."""
+    import oracle_np
+    ub, lb, _ = oracle_np.reference_bounds()
+    turned = oracle_np.X0.copy()
+    turned[0:3] = (180.0, -180.0, 90.0)
+    return np.vstack([oracle_np.X0, np.zeros(26), turned, lb, ub,
+                      random_thetas(np.random.default_rng(77), 12, spread=3.0)])
+
+
+# csrc/hpe_layout.hpp's DevHand as tests/cpp/dev_hand_dump.cpp writes it (2016 bytes)
+DEV_HAND = np.dtype([("Fc", "f8", 5), ("Fs", "f8", 5), ("FLc", "f8", 5), ("FLs", "f8", 5),
+                     ("T10x", "f8", 5), ("T10y", "f8", 5), ("L", "f8", (5, 4)), ("twc", "f8", 5),
+                     ("tws", "f8", 5), ("radii", "f8", 48), ("wa", "f8", 48), ("wb", "f8", 48),
+                     ("dg", "i4", 48), ("ja", "i4", 48)])
+_dump_exe = []
+
+
+def dev_hand_dump(tmp_dir, params):
+    """hpe::build_dev_hand of every hpe._lib.HandParams in params, on the host alone: a
+    stand-alone program over tests/cpp/dev_hand_dump.cpp and csrc/hpe_host.cpp, built once per
+    session into tmp_dir (a pathlib.Path).  Returns (a DEV_HAND array, the program's stdout)."""
+    import subprocess
+    if not _dump_exe:
+        csrc = ROOT / "hand-pose-estimation_amd" / "csrc"
+        exe = tmp_dir / "dev_hand_dump"
+        subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-o", str(exe),
+                        str(ROOT / "tests" / "cpp" / "dev_hand_dump.cpp"),
+                        str(csrc / "hpe_host.cpp"), f"-I{csrc}"], check=True, timeout=120)
+        _dump_exe.append(exe)
+    (tmp_dir / "in.bin").write_bytes(b"".join(bytes(p) for p in params))
+    out = subprocess.run([str(_dump_exe[0]), str(tmp_dir / "in.bin"), str(tmp_dir / "out.bin")],
+                         capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    return np.fromfile(tmp_dir / "out.bin", dtype=DEV_HAND), out.stdout
+
+
 def random_thetas(rng, P, x0=None, spread=1.0):
     import oracle_np
     x0 = oracle_np.X0 if x0 is None else x0

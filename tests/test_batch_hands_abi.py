@@ -95,31 +95,20 @@ def test_scaled_hand_parameters(scale, rscale):
 
 
 # ---- build_dev_hand on the host
-DEV_HAND = np.dtype([("Fc", "f8", 5), ("Fs", "f8", 5), ("FLc", "f8", 5), ("FLs", "f8", 5),
-                     ("T10x", "f8", 5), ("T10y", "f8", 5), ("L", "f8", (5, 4)), ("twc", "f8", 5),
-                     ("tws", "f8", 5), ("radii", "f8", 48), ("wa", "f8", 48), ("wb", "f8", 48),
-                     ("dg", "i4", 48), ("ja", "i4", 48)])
+DEV_HAND = hand_data.DEV_HAND
 
 
 @pytest.fixture(scope="module")
 def dev_hands(tmp_path_factory):
-    """DevHand of the reference hand, its scale-2 and scale-0.5 forms and scaled_hand(0.9, 0.85)."""
+    """DevHand of the reference hand, its scale-2 and scale-0.5 forms and scaled_hand(0.9, 0.85)
+    (hand_data.dev_hand_dump, shared with tests/test_hand_family.py)."""
     import hpe
-    d = tmp_path_factory.mktemp("dh")
-    exe = d / "dev_hand_dump"
-    csrc = PKG / "csrc"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-o", str(exe),
-                    str(hand_data.ROOT / "tests" / "cpp" / "dev_hand_dump.cpp"),
-                    str(csrc / "hpe_host.cpp"), f"-I{csrc}"], check=True, timeout=120)
     ps = [hpe.scaled_hand_params(1.0), hpe.scaled_hand_params(2.0), hpe.scaled_hand_params(0.5),
           hpe.scaled_hand_params(0.9, 0.85)]
-    (d / "in.bin").write_bytes(b"".join(bytes(p) for p in ps))
-    out = subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], capture_output=True,
-                         text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "4 hands of 2016 bytes" in out.stdout  # the lane table's stride
+    hands, stdout = hand_data.dev_hand_dump(tmp_path_factory.mktemp("dh"), ps)
+    assert "4 hands of 2016 bytes" in stdout  # the lane table's stride
     assert DEV_HAND.itemsize == 2016
-    return np.fromfile(d / "out.bin", dtype=DEV_HAND)
+    return hands
 
 
 @pytest.mark.parametrize("k,f", [(1, 2.0), (2, 0.5)])

@@ -7,7 +7,9 @@ whole histories and final states; never the batch itself.  A lane's frames are r
 the default yardstick context of its hand, so the tracker sees a hand of its model's size.
 
 Hands: A the reference hand, S = scaled_hand(0.9, 0.85), L = scaled_hand(1.1, 1.2), and V, which
-also moves cmc_deg and spacing_cm (no oracle mirrors V: the bit-identity yardstick alone).  Hand h
+also moves cmc_deg and spacing_cm: hand_data.hand_family()["V"].  Both oracles mirror V
+(oracle.hand / oracle_np.Hand take cmc and spacing), and tests/test_gpu_hand_family.py compares
+V's FK, costs, optimisers and lanes with them; this file keeps the bit-identity yardstick.  Hand h
 tracks hpe.synth.trajectory seed SEED[h].
 
 Small shapes: P = 32, maxiter 4 (G = 3), 250-point clouds, at most 5 frames per lane, chunks of 2
@@ -35,10 +37,8 @@ def make_hand(name):
     if name in SCALES:
         return hpe.scaled_hand(*SCALES[name])
     assert name == "V"
-    geo, rad = hpe.reference_geometry()
-    cmc = np.array(hpe.CMC) + np.array([1.5, -1.0, 0.5, 0.75, -0.5])
-    spacing = np.array(hpe.SPACING) + np.array([0.05, -0.04, 0.03, 0.02, -0.06])
-    return hpe.handmodel(geo * 1.05, spacing, hpe.TB_SPHERES, hpe.FG_SPHERES, cmc, rad * 0.95)
+    import hand_data
+    return hand_data.family_gpu_hand(hand_data.hand_family()["V"])
 
 
 class Env:
