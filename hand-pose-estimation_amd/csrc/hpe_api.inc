@@ -19,14 +19,15 @@
 
 #include "../../include/hpe.h"
 #include "hpe_host.hpp"
+#include "hpe_own.hpp"
 
 namespace {
 
 #define HPE_RAW_RING 8  // pinned staging buffers for raw depth frames in flight
 
 struct Slot {
-    double *cx = nullptr, *cy = nullptr, *cz = nullptr, *depth = nullptr;
-    float *dt = nullptr;
+    DevBuf<double> cx, cy, cz, depth;
+    DevBuf<float> dt;
     int n = 0, cap = 0;
     double scale = 0, dtmax = 0, K[9] = {0};
     bool valid = false;
@@ -34,27 +35,25 @@ struct Slot {
     // host-side call needs them (known == false); n_max bounds n without a readback
     bool dev = false, known = true;
     int n_max = 0;
-    hipEvent_t ready = nullptr;  // prep stream: frame written
-    hipEvent_t done = nullptr;   // main stream: last work that read the frame
+    Event ready;  // prep stream: frame written
+    Event done;   // main stream: last work that read the frame
     bool done_valid = false;
 };
+static_assert(std::is_nothrow_move_constructible<Slot>::value, "std::vector<Slot> grows by moving");
 
 struct Swarm {
     int P = 0, G = -1, K = 0;
     uint64_t seed = 0;
-    double *xh = nullptr, *pch = nullptr, *pb = nullptr, *inbox = nullptr, *ibtc = nullptr;
-    double *v = nullptr, *gpos = nullptr, *normals = nullptr, *bounds = nullptr;
-    unsigned long long *gmin = nullptr;
-    double *trace_g = nullptr;
-    int *trace_count = nullptr, *trace_topo = nullptr;
-    Sig *sig = nullptr;
-    int *outl = nullptr;
+    DevBuf<double> xh, pch, pb, inbox, ibtc, v, gpos, normals, bounds, trace_g;
+    DevBuf<unsigned long long> gmin;
+    DevBuf<int> trace_count, trace_topo, outl;
+    DevBuf<Sig> sig;
     std::vector<InboxCounts> kin;  // per generation 0..G (P <= KIN_MAX)
     // hpe_track_batch_dev: the mutable arrays (xh, pch, pb, v, inbox, gmin, sig, gpos, and last
     // ibtc, which only wave-form lanes touch) of `lanes` lanes, one arena per lane `stride` bytes
     // apart; off[]: the arrays within an arena.
     // The arrays above stay the single-sequence calls' own (their cached graphs keep them).
-    char *arena = nullptr;
+    DevBuf<char> arena;
     size_t stride = 0, off[9] = {0};
     int lanes = 0;
 };
@@ -99,10 +98,9 @@ const RcclApi &rccl_api() {
 struct OptState {  // pso_optimise buffers, rebuilt when P / G / seed / cloud bound grow
     int P = 0, G = -1, n_cap = 0;
     uint64_t seed = 0;
-    double *x = nullptr, *v = nullptr, *pb = nullptr, *pc = nullptr, *gbest = nullptr,
-           *trace = nullptr, *normals = nullptr, *bounds = nullptr;
-    int32_t *match = nullptr;
-    unsigned *ctr = nullptr;
+    DevBuf<double> x, v, pb, pc, gbest, trace, normals, bounds;
+    DevBuf<int32_t> match;
+    DevBuf<unsigned> ctr;
 };
 
 // The lane forms' state (hpe_pso_optimise_batch, hpe_batch_pipeline_optimise): per lane one
@@ -113,12 +111,16 @@ struct OptState {  // pso_optimise buffers, rebuilt when P / G / seed / cloud bo
 struct OptLanes {
     int P = 0, G = -1, lanes = 0;
     uint64_t seed = 0;
-    char *arena = nullptr;
+    DevBuf<char> arena;
     size_t stride = 0, off[7] = {0};
-    double *normals = nullptr, *bounds = nullptr;
+    DevBuf<double> normals, bounds;
     double bounds_h[3 * HPE_DOF] = {0};  // what `bounds` holds
     bool bounds_set = false;
-    DevObs *d_obs = nullptr;  // [HPE_BATCH_MAX]
+    DevBuf<DevObs> d_obs;  // [HPE_BATCH_MAX]
+    void reset() {  // everything but the descriptor table
+        arena.reset(), normals.reset(), bounds.reset();
+        P = 0, G = -1, lanes = 0, bounds_set = false;
+    }
 };
 
 // What a captured tracking graph depends on besides the context's seed and epoch: one key for
@@ -228,32 +230,36 @@ struct LaneFrameIo {
 
 struct hpe_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // The three streams stand before every other owner: members are destroyed in reverse order
+    // of declaration, so all memory and every event goes first, then the pipeline's copy stream,
+    // the preparation stream and, last as ever, the context stream.  Keep them first.
+    Stream stream;
+    Stream prep;       // device preprocessing (hpe_prepare_frame): one frame in flight at a time
+    Stream pipe_copy;  // the pipeline's raw upload (Pipe::zero_copy off)
     char err[512] = {0};
     DevHand hand;
-    DevHand *d_hand = nullptr;
+    DevBuf<DevHand> d_hand;
     // the batch lanes' hands (hpe_set_batch_hands): one flat table, entry b lane b's, which the
     // lane kernels' HANDS forms index by their lane; the context's hand in every entry while
     // lane_hands_B == 0, when the !HANDS forms run (they read entry 0).  The graphs hold its
     // address alone, and key whether hands are set (GraphKey::hands): rewriting the table (the
     // stream drained) captures nothing.
-    DevHand *d_lane_hands = nullptr;  // [HPE_BATCH_MAX]
+    DevBuf<DevHand> d_lane_hands;     // [HPE_BATCH_MAX]
     int lane_hands_B = 0;             // the B the lane hands were set for, 0: none
     std::vector<Slot> slots;
     int cur = -1;
     // scratch
-    double *d_theta = nullptr, *d_cost = nullptr, *d_terms = nullptr, *d_S = nullptr,
-           *d_J = nullptr;
+    DevBuf<double> d_theta, d_cost, d_terms, d_S, d_J;
     int theta_cap = 0;
-    int32_t *d_match = nullptr;
+    DevBuf<int32_t> d_match;
     size_t match_cap = 0;
-    double *d_state = nullptr;  // 27 doubles: x0/bestp + cost
+    DevBuf<double> d_state;  // 27 doubles: x0/bestp + cost
     // frame descriptors in HBM: one per slot + the selected one, which every kernel reads
     // (kernel arguments stay identical from frame to frame, so a frame replays as a graph)
-    DevObs *d_obs = nullptr, *d_obs_active = nullptr;
+    DevBuf<DevObs> d_obs, d_obs_active;
     // offline sequences: the descriptor the chunk graphs read and the cursor {slot, row}
-    DevObs *d_seq_obs = nullptr;
-    int *d_seq_cur = nullptr;
+    DevBuf<DevObs> d_seq_obs;
+    DevBuf<int> d_seq_cur;
     // (no mode of the context says which descriptor, cursor or counter a tracked frame's launches
     // use: the tracking call hands them over in a FrameIo, for B lanes a LaneFrameIo, per frame)
     // the captured graphs, a cache per tracking call:
@@ -268,70 +274,67 @@ struct hpe_ctx {
     GraphCache graphs[GC_N] = {{{}, 1, false}, {{}, 16, false}, {{}, 64, true},
                                {{}, 64, true}, {{}, 64, true}, {{}, 64, true},
                                {{}, 16, false}};
-    // device preprocessing (hpe_prepare_frame): its own stream, one frame in flight at a time
-    hipStream_t prep = nullptr;
-    float *d_raw = nullptr;
-    double *d_tmp = nullptr, *d_ctb = nullptr;
-    unsigned *d_prep_ctr = nullptr;
-    int *d_dtf = nullptr;
-    PrepInfo *d_info = nullptr;  // [HPE_MAX_SLOTS]
-    float *h_raw[HPE_RAW_RING] = {};
-    hipEvent_t raw_ev[HPE_RAW_RING] = {};
+    // device preprocessing (hpe_prepare_frame) on the stream prep
+    DevBuf<float> d_raw;
+    DevBuf<double> d_tmp, d_ctb;
+    DevBuf<unsigned> d_prep_ctr;
+    DevBuf<int> d_dtf;
+    DevBuf<PrepInfo> d_info;  // [HPE_MAX_SLOTS]
+    HostBuf<float> h_raw[HPE_RAW_RING];
+    Event raw_ev[HPE_RAW_RING];
     bool raw_ev_valid[HPE_RAW_RING] = {};
-    hipEvent_t main_mark = nullptr;
+    Event main_mark;
     int raw_k = 0;
     // pipelined tracking (hpe_pipeline_begin / hpe_track_pipelined): two frame buffers,
     // frame f+1 prepared inside frame f's refine launch
     struct Pipe {
         Slot fr[2];
-        DevObs *d_obs = nullptr;    // [2]
-        PrepInfo *d_info = nullptr; // [2]
-        float *d_raw = nullptr;  // [2][npix]: raw frame by buffer parity
-        float *h_raw[2] = {nullptr, nullptr};
+        DevBuf<DevObs> d_obs;     // [2]
+        DevBuf<PrepInfo> d_info;  // [2]
+        DevBuf<float> d_raw;  // [2][npix]: raw frame by buffer parity
         // zero copy (default): the preparation workgroups read the raw frame straight from
         // its pinned (coherent, mapped) host buffer over PCIe, inside the refine launch they
         // ride in -- no upload, no cross-queue wait between frames.  HPE_PIPE_UPLOAD=1: the
         // raw upload of the next frame runs on a copy stream (SDMA) while the previous
         // frame computes, and the frame's graph waits on raw_ready.
-        float *h_raw_dev[2] = {nullptr, nullptr};
+        HostBuf<float> h_raw[2];
         bool zero_copy = true;
         // buffer reuse without event markers on the stream: every pipelined frame's final
         // kernel bumps d_seq and stores it to the pinned word h_done (system scope); the
         // host reuses pinned buffer k once h_done >= used_seq[k], the number of the frame
         // whose refine launch read it (zero copy)
-        unsigned long long *d_seq = nullptr, *h_done = nullptr, *h_done_dev = nullptr;
+        DevBuf<unsigned long long> d_seq;
+        HostBuf<unsigned long long> h_done;
         // the split distance transform of resident raw sequences (PrepSplit): the forward
         // scans by frame parity, and {first hand row [2], sequence length, -}
-        int *d_dtf2 = nullptr;   // [2][npix]
-        int *d_split = nullptr;  // [4]
+        DevBuf<int> d_dtf2;   // [2][npix]
+        DevBuf<int> d_split;  // [4]
         unsigned long long enq = 0, used_seq[2] = {0, 0};
-        hipEvent_t used[2] = {nullptr, nullptr};
-        hipStream_t copy = nullptr;
-        hipEvent_t raw_ready[2] = {nullptr, nullptr};
+        Event used[2], raw_ready[2];
         bool used_valid[2] = {false, false};
         int cur = -1, to_cm = 1, downsample = 1;
         double focal = 241.42;
     } pipe;
     // batched lanes (hpe_track_batch_dev): per lane the current-frame descriptor the chunk
     // graphs read, the cursor {slot, history row} and the refine evaluation counter
-    DevObs *d_bobs = nullptr;  // [HPE_BATCH_MAX]
-    int *d_bcur = nullptr;     // [HPE_BATCH_MAX][2]
-    int *d_bevals = nullptr;   // [HPE_BATCH_MAX][HPE_EVALS_N]
+    DevBuf<DevObs> d_bobs;  // [HPE_BATCH_MAX]
+    DevBuf<int> d_bcur;     // [HPE_BATCH_MAX][2]
+    DevBuf<int> d_bevals;   // [HPE_BATCH_MAX][HPE_EVALS_N]
     // batched raw lanes (hpe_track_raw_batch_dev): per lane one arena holding two frame buffers
     // (depth, DT, a 250-point cloud each) and the preparation scratch (tmp, ctb, dtf); the
     // descriptors, PrepInfo and PrepArgs tables by [parity][lane]; the lane's hand-off counters
     // (a 128-byte line each), raw base and cursor {frame, history row}.  The chunk graphs hold
     // only the tables' addresses, which never change: arenas are added, never moved.
     struct RawBatch {
-        char *arena[HPE_BATCH_MAX] = {};
+        DevBuf<char> arena[HPE_BATCH_MAX];
         int lanes = 0, to_cm = -1;
         double focal = 0;
-        DevObs *d_obs = nullptr;      // [2][HPE_BATCH_MAX]
-        PrepInfo *d_info = nullptr;   // [2][HPE_BATCH_MAX]
-        PrepArgs *d_tab = nullptr;    // [2][HPE_BATCH_MAX]
-        unsigned *d_ctr = nullptr;    // [HPE_BATCH_MAX][32]
-        const float **d_raw = nullptr;  // [HPE_BATCH_MAX]
-        int *d_cur = nullptr;         // [HPE_BATCH_MAX][2]
+        DevBuf<DevObs> d_obs;         // [2][HPE_BATCH_MAX]
+        DevBuf<PrepInfo> d_info;      // [2][HPE_BATCH_MAX]
+        DevBuf<PrepArgs> d_tab;       // [2][HPE_BATCH_MAX]
+        DevBuf<unsigned> d_ctr;       // [HPE_BATCH_MAX][32]
+        DevBuf<const float *> d_raw;  // [HPE_BATCH_MAX]
+        DevBuf<int> d_cur;            // [HPE_BATCH_MAX][2]
         std::vector<PrepArgs> tab;    // d_tab's host copy, and how often it was rewritten
         unsigned tab_gen = 0;
     } rb;
@@ -343,13 +346,13 @@ struct hpe_ctx {
     // pinned word h_done, and the host refills the buffers of parity k once h_done >=
     // used_seq[k], the number of the frame whose refine launch read them.
     struct LiveBatch {
-        float *h_raw[2][HPE_BATCH_MAX] = {};
-        float *h_raw_dev[2][HPE_BATCH_MAX] = {};
+        HostBuf<float> h_raw[2][HPE_BATCH_MAX];
         int lanes = 0;  // lanes that have their pinned buffers
-        PrepArgs *d_tab = nullptr;  // [2][HPE_BATCH_MAX]
+        DevBuf<PrepArgs> d_tab;  // [2][HPE_BATCH_MAX]
         unsigned tab_gen = 0;
         int tab_lanes = 0;
-        unsigned long long *d_seq = nullptr, *h_done = nullptr, *h_done_dev = nullptr;
+        DevBuf<unsigned long long> d_seq;
+        HostBuf<unsigned long long> h_done;
         unsigned long long enq = 0, used_seq[2] = {0, 0};
         int B = 0, cur = -1, to_cm = 1;  // cur: the current frames' parity, -1: no batch
         double focal = 0;
@@ -358,7 +361,7 @@ struct hpe_ctx {
         // device memory, written on the stream ahead of a frame's graph (k_lane_act)
         int pacing = HPE_PACING_LOCKSTEP;
         uint32_t pending = 0;
-        int *d_act = nullptr;  // [HPE_BATCH_MAX]
+        DevBuf<int> d_act;  // [HPE_BATCH_MAX]
         // the words d_act holds once the stream reaches this point (act_known): a call whose
         // words are these enqueues no write -- a batch whose lanes all have every frame writes
         // them once
@@ -370,7 +373,7 @@ struct hpe_ctx {
         // first half of the lane's pinned buffer
         bool u16 = false;
         float unit_mm = 1.f;  // the host's copy of *d_unit (the locate kernel takes it by value)
-        float *d_unit = nullptr;
+        DevBuf<float> d_unit;
         size_t frame_bytes() const {
             return (u16 ? sizeof(uint16_t) : sizeof(float)) * (size_t)HPE_IMG_H * HPE_IMG_W;
         }
@@ -386,10 +389,10 @@ struct hpe_ctx {
         hpe_report_watch watch = {HUGE_VAL, 0, 0};
         int ring_depth = 0, ring_B = 0;
         unsigned long long enq[HPE_BATCH_MAX] = {};
-        char *h_ring = nullptr, *h_ring_dev = nullptr;
-        unsigned long long *d_lane_seq = nullptr;  // [HPE_BATCH_MAX]
-        int *d_streak = nullptr;                   // [HPE_BATCH_MAX]
-        RepPar *d_par = nullptr;
+        HostBuf<char> h_ring;
+        DevBuf<unsigned long long> d_lane_seq;  // [HPE_BATCH_MAX]
+        DevBuf<int> d_streak;                   // [HPE_BATCH_MAX]
+        DevBuf<RepPar> d_par;
     } rep;
     // lane location (hpe_locate_depth, hpe_batch_pipeline_locate): allocated by the first begin
     // with the windows on, or by the first hpe_locate_depth.
@@ -400,11 +403,11 @@ struct hpe_ctx {
     // word, hpe_locate, end word), d_seq the lanes' locate counters; B, enq: the lane count of
     // the last live batch begun and the locates enqueued per lane since that begin.
     struct Locate {
-        hpe_locate *d_res = nullptr;         // [HPE_BATCH_MAX + 1]
-        int *d_act = nullptr;                // [HPE_BATCH_MAX + 1]
-        unsigned long long *d_seq = nullptr; // [HPE_BATCH_MAX]
-        char *h_tab = nullptr, *h_tab_dev = nullptr;
-        float *d_frame = nullptr;            // hpe_locate_depth's staging buffer, one frame
+        DevBuf<hpe_locate> d_res;          // [HPE_BATCH_MAX + 1]
+        DevBuf<int> d_act;                 // [HPE_BATCH_MAX + 1]
+        DevBuf<unsigned long long> d_seq;  // [HPE_BATCH_MAX]
+        HostBuf<char> h_tab;
+        DevBuf<float> d_frame;             // hpe_locate_depth's staging buffer, one frame
         int B = 0;
         unsigned long long enq[HPE_BATCH_MAX] = {};
     } loc;
@@ -416,14 +419,14 @@ struct hpe_ctx {
         int mode = HPE_WINDOW_OFF, B = 0;
         double margin_xy = 0, margin_z = 0;
         std::vector<DevWindow> init;
-        DevWindow *d_tab = nullptr;  // [2][HPE_BATCH_MAX]
-        WinPar *d_par = nullptr;
+        DevBuf<DevWindow> d_tab;  // [2][HPE_BATCH_MAX]
+        DevBuf<WinPar> d_par;
         // hpe_window_from_pose's own pose, parameters and result
-        double *d_one_state = nullptr;
-        WinPar *d_one_par = nullptr;
-        DevWindow *d_one = nullptr;
+        DevBuf<double> d_one_state;
+        DevBuf<WinPar> d_one_par;
+        DevBuf<DevWindow> d_one;
     } win;
-    hipEvent_t seq_done = nullptr;  // recorded after a sequence: its slots' last reader
+    Event seq_done;  // recorded after a sequence: its slots' last reader
     bool seq_done_valid = false;
     unsigned epoch = 1;  // bumped whenever a buffer a captured graph uses is reallocated
     int batch_form = HPE_BATCH_FORM_AUTO;  // the batch calls' pso_evolve form (hpe_set_batch_form)
@@ -437,22 +440,22 @@ struct hpe_ctx {
     // resident raw sequences split each frame's distance transform over two refine launches
     // (HPE_PREP_SPLIT=0: the whole transform in one, as the pipelined loop has it)
     bool prep_split = true;
-    double *h_pinned = nullptr; // 256 doubles: [0,64) results, [64,128) inputs
-    int *d_evals = nullptr;
+    HostBuf<double> h_pinned;  // 256 doubles: [0,64) results, [64,128) inputs
+    DevBuf<int> d_evals;
     // multi-workgroup refine (clouds > RF_STAGE_MAX); HPE_REFINE_MW=0 keeps one workgroup
-    MwJob *d_mw_job = nullptr;
-    double *d_mw_part = nullptr;
-    unsigned *d_mw_ctr = nullptr;
-    int *d_mw_err = nullptr;
-    int *h_mw_err = nullptr, *h_mw_err_dev = nullptr;  // pinned copy of the flag (mapped)
+    DevBuf<MwJob> d_mw_job;
+    DevBuf<double> d_mw_part;
+    DevBuf<unsigned> d_mw_ctr;
+    DevBuf<int> d_mw_err;
+    HostBuf<int> h_mw_err;  // pinned copy of the flag (mapped)
     int mw_spin = MW_SPIN_MAX;  // HPE_MW_SPIN: polls per wait (a test forces timeouts with 0)
     int mw_fits = -1;  // the multi-workgroup launch fits co-resident (occupancy), -1 unknown
     bool refine_mw = true;
     bool refine_exact = false;  // refine spheres by the reference's chain (else hand frame)
     // speculated translation block (hpe_set_refine_spec): the staged refine's second workgroup
     bool refine_spec = true;
-    unsigned long long *d_spec_g = nullptr;  // DevSpec::g
-    unsigned *d_spec_ep = nullptr;           // DevSpec::epoch
+    DevBuf<unsigned long long> d_spec_g;  // DevSpec::g
+    DevBuf<unsigned> d_spec_ep;           // DevSpec::epoch
     int spec_spin = SPEC_SPIN_MAX;  // HPE_SPEC_SPIN: the leader's polls for a result (tests: 0)
     int spec_fits = -1;  // both refine workgroups and the preparation fit co-resident, -1 unknown
     unsigned long long captures = 0;  // graphs captured so far (hpe_graph_captures)
@@ -468,19 +471,19 @@ struct hpe_ctx {
         ncclComm_t comm = nullptr;
         // the scripted transport (hpe_subswarm_init_scripted) in the communicator's place:
         // peer rows [script_frames][nranks][27] and the device exchange counter
-        double *d_script = nullptr;
-        int *d_script_k = nullptr;
+        DevBuf<double> d_script;
+        DevBuf<int> d_script_k;
         int script_frames = 0;
         bool transport() const { return comm || d_script; }
         int nranks = 0, rank = 0;
         bool on = false;
-        double *d_gath = nullptr;  // [nranks][27]: row `rank` is this rank's frame result
+        DevBuf<double> d_gath;  // [nranks][27]: row `rank` is this rank's frame result
         // the exchange inside captured graphs (1), or direct launches while it is on (0): set
         // by hpe_subswarm_enable(ctx, 2), or when a capture holding the collective fails
         bool graphs = true;
         char note[256] = {0};
     } ss;
-    float *d_render = nullptr;
+    DevBuf<float> d_render;
     // PSO parameters
     double lb[26], ub[26], sd[26];
     double omega = 0.7298, phip = 1.49618, phig = 1.49618, minstep = 1e-6, minfunc = 1e-6;
@@ -495,7 +498,7 @@ struct hpe_ctx {
     // the same interval rocprofv3 --kernel-trace reports), one pool per kernel
     bool prof = false;
     struct Pool {
-        std::vector<hipEvent_t> ev;  // pairs
+        std::vector<Event> ev;  // pairs
         size_t used = 0;
     } pools[HPE_PROF_KERNELS];
 };
@@ -530,16 +533,6 @@ static int fail(hpe_ctx *c, int code, const char *fmt, ...) {
             return fail((c), HPE_E_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
                         __FILE__, __LINE__);                                              \
     } while (0)
-
-template <typename T>
-static hipError_t dalloc(T **p, size_t n) {
-    return hipMalloc((void **)p, sizeof(T) * (n ? n : 1));
-}
-template <typename T>
-static void dfree(T *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
 
 static DevObs make_obs(const Slot &s) {
     DevObs o;
@@ -581,16 +574,9 @@ static int need_frame(hpe_ctx *c, DevObs *o) {
 static int ensure_theta(hpe_ctx *c, int P) {
     if (P <= c->theta_cap) return HPE_OK;
     ++c->epoch;
-    dfree(c->d_theta);
-    dfree(c->d_cost);
-    dfree(c->d_terms);
-    dfree(c->d_S);
-    dfree(c->d_J);
-    HIPCHK(c, dalloc(&c->d_theta, (size_t)P * HPE_DOF));
-    HIPCHK(c, dalloc(&c->d_cost, (size_t)P));
-    HIPCHK(c, dalloc(&c->d_terms, (size_t)P * 3));
-    HIPCHK(c, dalloc(&c->d_S, (size_t)P * 3 * HPE_NS));
-    HIPCHK(c, dalloc(&c->d_J, (size_t)P * 63));
+    c->theta_cap = 0;
+    HIPCHK(c, alloc_all(c->d_theta, (size_t)P * HPE_DOF, c->d_cost, (size_t)P, c->d_terms, (size_t)P * 3,
+                        c->d_S, (size_t)P * 3 * HPE_NS, c->d_J, (size_t)P * 63));
     c->theta_cap = P;
     return HPE_OK;
 }
@@ -598,58 +584,22 @@ static int ensure_theta(hpe_ctx *c, int P) {
 static int ensure_match(hpe_ctx *c, size_t n) {
     if (n <= c->match_cap) return HPE_OK;
     ++c->epoch;
-    dfree(c->d_match);
-    HIPCHK(c, dalloc(&c->d_match, n));
+    c->match_cap = 0;
+    HIPCHK(c, c->d_match.alloc(n));
     c->match_cap = n;
     return HPE_OK;
 }
 
-static void free_swarm(Swarm &s) {
-    dfree(s.xh);
-    dfree(s.pch);
-    dfree(s.pb);
-    dfree(s.inbox);
-    dfree(s.v);
-    dfree(s.gpos);
-    dfree(s.normals);
-    dfree(s.bounds);
-    dfree(s.gmin);
-    dfree(s.trace_g);
-    dfree(s.trace_count);
-    dfree(s.trace_topo);
-    dfree(s.sig);
-    dfree(s.outl);
-    dfree(s.ibtc);
-    dfree(s.arena);
-    s.lanes = 0;
-    s.P = 0;
-    s.G = -1;
-}
-
-static void free_opt(OptState &s) {
-    dfree(s.x);
-    dfree(s.v);
-    dfree(s.pb);
-    dfree(s.pc);
-    dfree(s.gbest);
-    dfree(s.trace);
-    dfree(s.normals);
-    dfree(s.bounds);
-    dfree(s.match);
-    dfree(s.ctr);
-    s.P = 0;
-    s.G = -1;
-    s.n_cap = 0;
-}
-
-static void free_opt_lanes(OptLanes &s) {
-    dfree(s.arena);
-    dfree(s.normals);
-    dfree(s.bounds);
-    s.P = 0;
-    s.G = -1;
-    s.lanes = 0;
-    s.bounds_set = false;
+// A frame buffer's depth and DT images once, and its cloud grown to `need` points: each group
+// all or nothing, and a slot whose cloud could not be grown is invalid, with capacity 0.
+static hipError_t slot_buffers(Slot &s, int need) {
+    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W, n = (size_t)need;
+    hipError_t e = s.depth ? hipSuccess : alloc_all(s.depth, npix, s.dt, npix);
+    if (e != hipSuccess || need <= s.cap) return e;
+    s.cap = 0;
+    s.valid = false;
+    if ((e = alloc_all(s.cx, n, s.cy, n, s.cz, n)) == hipSuccess) s.cap = need;
+    return e;
 }
 
 // The lane arenas of a batch call (Swarm::arena): grown, never shrunk, with the epoch bumped
@@ -658,7 +608,7 @@ static int ensure_lanes(hpe_ctx *c, int lanes) {
     Swarm &s = c->sw;
     if (lanes <= s.lanes) return HPE_OK;
     ++c->epoch;
-    dfree(s.arena);
+    s.arena.reset();
     s.lanes = 0;
     const size_t n = (size_t)s.P * HPE_DOF, G1 = (size_t)s.G + 1;
     const size_t bytes[9] = {sizeof(double) * G1 * n,                                      // xh
@@ -676,7 +626,7 @@ static int ensure_lanes(hpe_ctx *c, int lanes) {
         at += (bytes[k] + 255) & ~(size_t)255;
     }
     s.stride = at;
-    HIPCHK(c, dalloc(&s.arena, s.stride * lanes));
+    HIPCHK(c, s.arena.alloc(s.stride * lanes));
     // empty inbox and ibtc slots (tag -1) and unwritten gmin cells are all-ones; the rest is
     // written before it is read
     HIPCHK(c, hipMemset(s.arena, 0xFF, s.stride * lanes));
@@ -687,10 +637,10 @@ static int ensure_lanes(hpe_ctx *c, int lanes) {
 // Swarm buffers + draw tables for (P, G, seed); rebuilt only when one changes.  lanes > 0
 // (hpe_track_batch_dev): also that many lane arenas.
 static int ensure_swarm(hpe_ctx *c, int P, int G, int lanes = 0) {
-    Swarm &s = c->sw;
-    if (s.P == P && s.G == G && s.seed == c->seed) return ensure_lanes(c, lanes);
+    if (c->sw.P == P && c->sw.G == G && c->sw.seed == c->seed) return ensure_lanes(c, lanes);
     ++c->epoch;
-    free_swarm(s);
+    c->sw = Swarm{};
+    Swarm s;  // built here and moved in whole: a failure leaves the context's swarm empty
     if (G > 32767) return fail(c, HPE_E_ARG, "maxiter %d too large", G + 1);
     std::vector<int> outl, indeg;
     const int K = hpe::make_links(c->seed, P, G, outl, &indeg);
@@ -708,34 +658,35 @@ static int ensure_swarm(hpe_ctx *c, int P, int G, int lanes = 0) {
         }
     }
     const size_t n = (size_t)P * HPE_DOF;
-    HIPCHK(c, dalloc(&s.xh, (size_t)(G + 1) * n));
-    HIPCHK(c, dalloc(&s.pch, (size_t)(G + 1) * P));
-    HIPCHK(c, dalloc(&s.pb, n));
+    HIPCHK(c, s.xh.alloc((size_t)(G + 1) * n));
+    HIPCHK(c, s.pch.alloc((size_t)(G + 1) * P));
+    HIPCHK(c, s.pb.alloc(n));
     const size_t ibn = (size_t)4 * P * K * IB_STRIDE;
-    HIPCHK(c, dalloc(&s.inbox, ibn));
+    HIPCHK(c, s.inbox.alloc(ibn));
     HIPCHK(c, hipMemset(s.inbox, 0xFF, sizeof(double) * ibn));  // tag -1: empty slot
-    HIPCHK(c, dalloc(&s.ibtc, (size_t)8 * P * K));
+    HIPCHK(c, s.ibtc.alloc((size_t)8 * P * K));
     HIPCHK(c, hipMemset(s.ibtc, 0xFF, sizeof(double) * 8 * P * K));
-    HIPCHK(c, dalloc(&s.v, n));
-    HIPCHK(c, dalloc(&s.gpos, (size_t)HPE_DOF));
-    HIPCHK(c, dalloc(&s.normals, n));
-    HIPCHK(c, dalloc(&s.bounds, (size_t)4 * HPE_DOF));
+    HIPCHK(c, s.v.alloc(n));
+    HIPCHK(c, s.gpos.alloc((size_t)HPE_DOF));
+    HIPCHK(c, s.normals.alloc(n));
+    HIPCHK(c, s.bounds.alloc((size_t)4 * HPE_DOF));
     const size_t ng = (size_t)(G + 1) * GMIN_SHARDS * GMIN_STRIDE;
-    HIPCHK(c, dalloc(&s.gmin, ng));
+    HIPCHK(c, s.gmin.alloc(ng));
     HIPCHK(c, hipMemset(s.gmin, 0xFF, sizeof(unsigned long long) * ng));
-    HIPCHK(c, dalloc(&s.trace_g, (size_t)(G > 0 ? G : 1)));
-    HIPCHK(c, dalloc(&s.trace_count, (size_t)(G > 0 ? G : 1)));
-    HIPCHK(c, dalloc(&s.trace_topo, (size_t)(G > 0 ? G : 1)));
-    HIPCHK(c, dalloc(&s.sig, (size_t)G + 1));
+    HIPCHK(c, s.trace_g.alloc((size_t)(G > 0 ? G : 1)));
+    HIPCHK(c, s.trace_count.alloc((size_t)(G > 0 ? G : 1)));
+    HIPCHK(c, s.trace_topo.alloc((size_t)(G > 0 ? G : 1)));
+    HIPCHK(c, s.sig.alloc((size_t)G + 1));
     std::vector<double> nrm(n);
     hpe::make_normals(c->seed, P, nrm.data());
     HIPCHK(c, hipMemcpy(s.normals, nrm.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    HIPCHK(c, dalloc(&s.outl, outl.size()));
+    HIPCHK(c, s.outl.alloc(outl.size()));
     HIPCHK(c, hipMemcpy(s.outl, outl.data(), sizeof(int) * outl.size(), hipMemcpyHostToDevice));
     s.P = P;
     s.G = G;
     s.K = K;
     s.seed = c->seed;
+    c->sw = std::move(s);
     c->bounds_dirty = true;
     return ensure_lanes(c, lanes);
 }
@@ -838,11 +789,12 @@ static int upload_bounds(hpe_ctx *c) {
 // The lanes' descriptors, cursors and refine evaluation counters (every batch call counts in
 // d_bevals).
 static int ensure_batch_lanes(hpe_ctx *c) {
-    if (!c->d_bobs) {
-        HIPCHK(c, dalloc(&c->d_bobs, HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&c->d_bcur, 2 * HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&c->d_bevals, HPE_BATCH_MAX * HPE_EVALS_N));
-        HIPCHK(c, hipMemset(c->d_bevals, 0, sizeof(int) * HPE_BATCH_MAX * HPE_EVALS_N));
+    if (!c->d_bevals) {  // assigned last, zeroed: a block that failed part way runs again in full
+        HIPCHK(c, alloc_all(c->d_bobs, HPE_BATCH_MAX, c->d_bcur, 2 * HPE_BATCH_MAX));
+        DevBuf<int> evals;
+        HIPCHK(c, evals.alloc(HPE_BATCH_MAX * HPE_EVALS_N));
+        HIPCHK(c, hipMemset(evals, 0, sizeof(int) * HPE_BATCH_MAX * HPE_EVALS_N));
+        c->d_bevals = std::move(evals);
     }
     return HPE_OK;
 }
@@ -1067,12 +1019,12 @@ static int launch_pso(hpe_ctx *c, int P, const FrameIo &io, bool tail, DevPick *
 // Scratch shared with hpe_prepare_frame (tmp cloud, scale terms, DT rows, counter).
 static int ensure_prep_scratch(hpe_ctx *c) {
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
-    if (!c->d_tmp) {
-        HIPCHK(c, dalloc(&c->d_tmp, 3 * npix));
-        HIPCHK(c, dalloc(&c->d_ctb, npix));
-        HIPCHK(c, dalloc(&c->d_dtf, npix));
-        HIPCHK(c, dalloc(&c->d_prep_ctr, 3));
-        HIPCHK(c, hipMemset(c->d_prep_ctr, 0, 3 * sizeof(unsigned)));
+    if (!c->d_prep_ctr) {  // assigned last, zeroed (as ensure_batch_lanes)
+        HIPCHK(c, alloc_all(c->d_tmp, 3 * npix, c->d_ctb, npix, c->d_dtf, npix));
+        DevBuf<unsigned> ctr;
+        HIPCHK(c, ctr.alloc(3));
+        HIPCHK(c, hipMemset(ctr, 0, 3 * sizeof(unsigned)));
+        c->d_prep_ctr = std::move(ctr);
     }
     return HPE_OK;
 }
@@ -1162,30 +1114,28 @@ int hpe_create(hpe_ctx **out, int device, const hpe_hand_params *hand) {
     hpe_ctx *c = new (std::nothrow) hpe_ctx();
     if (!c) return HPE_E_NOMEM;
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || c->stream.ensure(hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return HPE_E_HIP;
     }
     hpe::build_dev_hand(*hand, c->hand);
-    if (dalloc(&c->d_hand, 1) != hipSuccess ||
+    if (c->d_hand.alloc(1) != hipSuccess ||
         hipMemcpy(c->d_hand, &c->hand, sizeof(DevHand), hipMemcpyHostToDevice) != hipSuccess ||
-        dalloc(&c->d_lane_hands, HPE_BATCH_MAX) != hipSuccess || reset_lane_hands(c) != hipSuccess ||
-        dalloc(&c->d_state, 32) != hipSuccess || dalloc(&c->d_evals, 4) != hipSuccess ||
+        c->d_lane_hands.alloc(HPE_BATCH_MAX) != hipSuccess || reset_lane_hands(c) != hipSuccess ||
+        c->d_state.alloc(32) != hipSuccess || c->d_evals.alloc(4) != hipSuccess ||
         hipMemset(c->d_evals, 0, 4 * sizeof(int)) != hipSuccess ||
-        dalloc(&c->d_obs, HPE_MAX_SLOTS) != hipSuccess || dalloc(&c->d_obs_active, 1) != hipSuccess ||
-        dalloc(&c->d_seq_obs, 1) != hipSuccess || dalloc(&c->d_seq_cur, 2) != hipSuccess ||
-        dalloc(&c->d_mw_job, 1) != hipSuccess ||
-        dalloc(&c->d_mw_part, (size_t)MW_MAX_Q * MW_MAX_NODES) != hipSuccess ||
-        dalloc(&c->d_mw_ctr, MW_CTR_WORDS) != hipSuccess ||
+        c->d_obs.alloc(HPE_MAX_SLOTS) != hipSuccess || c->d_obs_active.alloc(1) != hipSuccess ||
+        c->d_seq_obs.alloc(1) != hipSuccess || c->d_seq_cur.alloc(2) != hipSuccess ||
+        c->d_mw_job.alloc(1) != hipSuccess ||
+        c->d_mw_part.alloc((size_t)MW_MAX_Q * MW_MAX_NODES) != hipSuccess ||
+        c->d_mw_ctr.alloc(MW_CTR_WORDS) != hipSuccess ||
         hipMemset(c->d_mw_ctr, 0, MW_CTR_WORDS * sizeof(unsigned)) != hipSuccess ||
-        dalloc(&c->d_mw_err, 1) != hipSuccess || hipMemset(c->d_mw_err, 0, sizeof(int)) != hipSuccess ||
-        dalloc(&c->d_spec_g, SPEC_GRAN) != hipSuccess ||
+        c->d_mw_err.alloc(1) != hipSuccess || hipMemset(c->d_mw_err, 0, sizeof(int)) != hipSuccess ||
+        c->d_spec_g.alloc(SPEC_GRAN) != hipSuccess ||
         hipMemset(c->d_spec_g, 0, SPEC_GRAN * sizeof(unsigned long long)) != hipSuccess ||
-        dalloc(&c->d_spec_ep, 64) != hipSuccess ||
+        c->d_spec_ep.alloc(64) != hipSuccess ||
         hipMemset(c->d_spec_ep, 0, 64 * sizeof(unsigned)) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_pinned, sizeof(double) * 256, 0) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_mw_err, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&c->h_mw_err_dev, c->h_mw_err, 0) != hipSuccess) {
+        c->h_pinned.alloc(256, 0) != hipSuccess || c->h_mw_err.alloc(1, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
         hpe_destroy(c);
         return HPE_E_HIP;
     }
@@ -1220,125 +1170,21 @@ static void drop_graphs(hpe_ctx *c) {
     }
 }
 
+// What has an order the owners cannot express: the streams drained, then the graphs before the
+// communicator their exchange nodes use, then the context -- whose members release themselves,
+// the streams last (hpe_ctx::stream).
 int hpe_destroy(hpe_ctx *c) {
     if (!c) return HPE_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->prep) (void)hipStreamSynchronize(c->prep);
-    for (auto &s : c->slots) {
-        if (s.ready) (void)hipEventDestroy(s.ready);
-        if (s.done) (void)hipEventDestroy(s.done);
-        dfree(s.cx);
-        dfree(s.cy);
-        dfree(s.cz);
-        dfree(s.depth);
-        dfree(s.dt);
-    }
-    drop_graphs(c);  // before the communicator their exchange nodes use
+    drop_graphs(c);
     if (c->ss.comm) (void)rccl_api().comm_destroy(c->ss.comm);
-    dfree(c->ss.d_gath);
-    dfree(c->ss.d_script);
-    dfree(c->ss.d_script_k);
-    free_swarm(c->sw);
-    free_opt(c->opt);
-    free_opt_lanes(c->optl);
-    dfree(c->optl.d_obs);
-    dfree(c->d_hand);
-    dfree(c->d_lane_hands);
-    dfree(c->d_theta);
-    dfree(c->d_cost);
-    dfree(c->d_terms);
-    dfree(c->d_S);
-    dfree(c->d_J);
-    dfree(c->d_match);
-    dfree(c->d_state);
-    dfree(c->d_evals);
-    dfree(c->d_mw_job);
-    dfree(c->d_mw_part);
-    dfree(c->d_mw_ctr);
-    dfree(c->d_mw_err);
-    dfree(c->d_spec_g);
-    dfree(c->d_spec_ep);
-    dfree(c->d_render);
-    dfree(c->d_obs);
-    dfree(c->d_obs_active);
-    dfree(c->d_seq_obs);
-    dfree(c->d_seq_cur);
-    dfree(c->d_bobs);
-    dfree(c->d_bcur);
-    dfree(c->d_bevals);
-    for (auto &a : c->rb.arena) dfree(a);
-    dfree(c->rb.d_obs);
-    dfree(c->rb.d_info);
-    dfree(c->rb.d_tab);
-    dfree(c->rb.d_ctr);
-    dfree(c->rb.d_raw);
-    dfree(c->rb.d_cur);
-    dfree(c->win.d_tab);
-    dfree(c->win.d_par);
-    dfree(c->win.d_one_state);
-    dfree(c->win.d_one_par);
-    dfree(c->win.d_one);
-    for (auto &par : c->live.h_raw)
-        for (float *h : par)
-            if (h) (void)hipHostFree(h);
-    dfree(c->live.d_tab);
-    dfree(c->live.d_seq);
-    dfree(c->live.d_act);
-    dfree(c->live.d_unit);
-    if (c->live.h_done) (void)hipHostFree(c->live.h_done);
-    if (c->rep.h_ring) (void)hipHostFree(c->rep.h_ring);
-    dfree(c->rep.d_lane_seq);
-    dfree(c->rep.d_streak);
-    dfree(c->rep.d_par);
-    if (c->loc.h_tab) (void)hipHostFree(c->loc.h_tab);
-    dfree(c->loc.d_res);
-    dfree(c->loc.d_act);
-    dfree(c->loc.d_seq);
-    dfree(c->loc.d_frame);
-    dfree(c->d_raw);
-    dfree(c->d_tmp);
-    dfree(c->d_ctb);
-    dfree(c->d_prep_ctr);
-    dfree(c->d_dtf);
-    dfree(c->d_info);
-    for (int k = 0; k < HPE_RAW_RING; ++k) {
-        if (c->h_raw[k]) (void)hipHostFree(c->h_raw[k]);
-        if (c->raw_ev[k]) (void)hipEventDestroy(c->raw_ev[k]);
-    }
-    if (c->main_mark) (void)hipEventDestroy(c->main_mark);
-    if (c->prep) (void)hipStreamDestroy(c->prep);
-    if (c->seq_done) (void)hipEventDestroy(c->seq_done);
-    for (int k = 0; k < 2; ++k) {
-        Slot &f = c->pipe.fr[k];
-        dfree(f.cx);
-        dfree(f.cy);
-        dfree(f.cz);
-        dfree(f.depth);
-        dfree(f.dt);
-        if (c->pipe.h_raw[k]) (void)hipHostFree(c->pipe.h_raw[k]);
-        if (c->pipe.used[k]) (void)hipEventDestroy(c->pipe.used[k]);
-    }
-    dfree(c->pipe.d_obs);
-    dfree(c->pipe.d_info);
-    dfree(c->pipe.d_raw);
-    dfree(c->pipe.d_seq);
-    dfree(c->pipe.d_dtf2);
-    dfree(c->pipe.d_split);
-    if (c->pipe.h_done) (void)hipHostFree(c->pipe.h_done);
-    if (c->h_mw_err) (void)hipHostFree(c->h_mw_err);
-    for (int k = 0; k < 2; ++k)
-        if (c->pipe.raw_ready[k]) (void)hipEventDestroy(c->pipe.raw_ready[k]);
-    if (c->pipe.copy) (void)hipStreamDestroy(c->pipe.copy);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    for (auto &pl : c->pools)
-        for (auto &e : pl.ev) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return HPE_OK;
 }
 
-void *hpe_stream(hpe_ctx *c) { return c ? (void *)c->stream : nullptr; }
+void *hpe_stream(hpe_ctx *c) { return c ? (void *)c->stream.get() : nullptr; }
 
 static int mw_check(hpe_ctx *c);
 
@@ -1362,19 +1208,7 @@ int hpe_store_frame(hpe_ctx *c, int slot, const hpe_frame *f) {
     if (c->prep) HIPCHK(c, hipStreamSynchronize(c->prep));
     if ((int)c->slots.size() <= slot) c->slots.resize(slot + 1);
     Slot &s = c->slots[slot];
-    if (!s.depth) {
-        HIPCHK(c, dalloc(&s.depth, (size_t)HPE_IMG_H * HPE_IMG_W));
-        HIPCHK(c, dalloc(&s.dt, (size_t)HPE_IMG_H * HPE_IMG_W));
-    }
-    if (f->n > s.cap) {
-        dfree(s.cx);
-        dfree(s.cy);
-        dfree(s.cz);
-        HIPCHK(c, dalloc(&s.cx, (size_t)f->n));
-        HIPCHK(c, dalloc(&s.cy, (size_t)f->n));
-        HIPCHK(c, dalloc(&s.cz, (size_t)f->n));
-        s.cap = f->n;
-    }
+    HIPCHK(c, slot_buffers(s, f->n));
     std::vector<double> soa(3 * (size_t)f->n);  // AoS (N x 3) -> SoA for coalesced loads
     for (int p = 0; p < f->n; ++p)
         for (int q = 0; q < 3; ++q) soa[(size_t)q * f->n + p] = f->cloud[3 * (size_t)p + q];
@@ -1410,7 +1244,7 @@ int hpe_select_frame(hpe_ctx *c, int slot) {
     if (slot != c->cur || s.dev) {  // stream-ordered: work already queued keeps its frame
         if (c->cur >= 0 && c->cur != slot) {  // everything queued so far used the old frame
             Slot &o = c->slots[c->cur];
-            if (!o.done) HIPCHK(c, hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
+            HIPCHK(c, o.done.ensure(hipEventDisableTiming));
             HIPCHK(c, hipEventRecord(o.done, c->stream));
             o.done_valid = true;
         }
@@ -1429,15 +1263,15 @@ int hpe_prepare_frame(hpe_ctx *c, int slot, const float *depth_mm, int to_cm, in
         return fail(c, HPE_E_ARG, "bad arguments (slot %d)", slot);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
-    if (!c->prep) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->prep, hipStreamNonBlocking));
-        HIPCHK(c, dalloc(&c->d_raw, npix));
+    HIPCHK(c, c->prep.ensure(hipStreamNonBlocking));
+    if (!c->raw_ev[HPE_RAW_RING - 1]) {  // created last: a block that failed part way runs again
+        HIPCHK(c, c->d_raw.alloc(npix));
         int rc0 = ensure_prep_scratch(c);
         if (rc0) return rc0;
-        HIPCHK(c, dalloc(&c->d_info, (size_t)HPE_MAX_SLOTS));
+        HIPCHK(c, c->d_info.alloc((size_t)HPE_MAX_SLOTS));
         for (int k = 0; k < HPE_RAW_RING; ++k) {
-            HIPCHK(c, hipHostMalloc((void **)&c->h_raw[k], sizeof(float) * npix, 0));
-            HIPCHK(c, hipEventCreateWithFlags(&c->raw_ev[k], hipEventDisableTiming));
+            HIPCHK(c, c->h_raw[k].alloc(npix, 0));
+            HIPCHK(c, c->raw_ev[k].ensure(hipEventDisableTiming));
         }
     }
     if ((int)c->slots.size() <= slot) c->slots.resize(slot + 1);
@@ -1446,25 +1280,13 @@ int hpe_prepare_frame(hpe_ctx *c, int slot, const float *depth_mm, int to_cm, in
     if (!s.depth || s.cap < need) {  // (re)allocation: nothing may still use the slot
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipStreamSynchronize(c->prep));
-        if (!s.depth) {
-            HIPCHK(c, dalloc(&s.depth, npix));
-            HIPCHK(c, dalloc(&s.dt, npix));
-        }
-        if (s.cap < need) {
-            dfree(s.cx);
-            dfree(s.cy);
-            dfree(s.cz);
-            HIPCHK(c, dalloc(&s.cx, (size_t)need));
-            HIPCHK(c, dalloc(&s.cy, (size_t)need));
-            HIPCHK(c, dalloc(&s.cz, (size_t)need));
-            s.cap = need;
-            ++c->epoch;
-        }
+        if (s.cap < need) ++c->epoch;
+        HIPCHK(c, slot_buffers(s, need));
     }
-    if (!s.ready) HIPCHK(c, hipEventCreateWithFlags(&s.ready, hipEventDisableTiming));
+    HIPCHK(c, s.ready.ensure(hipEventDisableTiming));
     // the frame's previous contents may still be read by queued tracking work
     if (slot == c->cur) {
-        if (!s.done) HIPCHK(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+        HIPCHK(c, s.done.ensure(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(s.done, c->stream));
         s.done_valid = true;
     }
@@ -1474,7 +1296,7 @@ int hpe_prepare_frame(hpe_ctx *c, int slot, const float *depth_mm, int to_cm, in
     // prepared just before the current one is tracked then runs beside that frame's
     // single-workgroup refine rather than beside the full-chip PSO generations
     {
-        if (!c->main_mark) HIPCHK(c, hipEventCreateWithFlags(&c->main_mark, hipEventDisableTiming));
+        HIPCHK(c, c->main_mark.ensure(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->main_mark, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->prep, c->main_mark, 0));
     }
@@ -1719,26 +1541,21 @@ static int ensure_opt(hpe_ctx *c, int P, int G, int n) {
     OptState &s = c->opt;
     const int need_n = n > RF_STAGE_MAX ? n : 0;
     if (s.P == P && s.G >= G && s.seed == c->seed && s.n_cap >= need_n) return HPE_OK;
-    free_opt(s);
+    s = OptState{};
+    OptState o;  // built here and moved in whole
     const size_t e = (size_t)P * HPE_DOF;
-    HIPCHK(c, dalloc(&s.x, e));
-    HIPCHK(c, dalloc(&s.v, e));
-    HIPCHK(c, dalloc(&s.pb, e));
-    HIPCHK(c, dalloc(&s.pc, (size_t)P));
-    HIPCHK(c, dalloc(&s.gbest, (size_t)28));
-    HIPCHK(c, dalloc(&s.trace, (size_t)(G > 0 ? G : 1)));
-    HIPCHK(c, dalloc(&s.normals, e));
-    HIPCHK(c, dalloc(&s.bounds, (size_t)3 * HPE_DOF));
-    HIPCHK(c, dalloc(&s.match, (size_t)P * (need_n > 0 ? need_n : 1)));
-    HIPCHK(c, dalloc(&s.ctr, (size_t)ARRIVE_SHARDS * 32 + 1));
-    HIPCHK(c, hipMemset(s.ctr, 0, sizeof(unsigned) * (ARRIVE_SHARDS * 32 + 1)));
+    HIPCHK(c, alloc_all(o.x, e, o.v, e, o.pb, e, o.pc, (size_t)P, o.gbest, (size_t)28,
+                        o.trace, (size_t)(G > 0 ? G : 1), o.normals, e, o.bounds, (size_t)3 * HPE_DOF,
+                        o.match, (size_t)P * (need_n > 0 ? need_n : 1), o.ctr, (size_t)ARRIVE_SHARDS * 32 + 1));
+    HIPCHK(c, hipMemset(o.ctr, 0, sizeof(unsigned) * (ARRIVE_SHARDS * 32 + 1)));
     std::vector<double> nrm(e);
     hpe::make_normals(c->seed, P, nrm.data(), ST_OPT_NORMAL);
-    HIPCHK(c, hipMemcpy(s.normals, nrm.data(), sizeof(double) * e, hipMemcpyHostToDevice));
-    s.P = P;
-    s.G = G;
-    s.n_cap = need_n;
-    s.seed = c->seed;
+    HIPCHK(c, hipMemcpy(o.normals, nrm.data(), sizeof(double) * e, hipMemcpyHostToDevice));
+    o.P = P;
+    o.G = G;
+    o.n_cap = need_n;
+    o.seed = c->seed;
+    s = std::move(o);
     return HPE_OK;
 }
 
@@ -1785,15 +1602,15 @@ int hpe_pso_optimise(hpe_ctx *c, const double x0[26], int P, double bestp[26],
     const bool staged = o.n <= RF_STAGE_MAX;
     const unsigned lds = staged ? (unsigned)((size_t)o.n * (3 * sizeof(double) + sizeof(int32_t))) : 0u;
     launch(c, HPE_PROF_PSO_INIT, k_opt_init, dim3(P), dim3(HPE_NT), 0, d, (const double *)c->d_state,
-           c->d_obs_active, (const DevHand *)c->d_hand);
+           c->d_obs_active.get(), (const DevHand *)c->d_hand);
     for (int g = 1; g <= G; ++g) {
         if (staged)
             launch(c, HPE_PROF_OPT_DESCENT, k_opt_descent<true>, dim3(P), dim3(RF_NT), lds, d,
-                   c->d_obs_active, (const DevHand *)c->d_hand, g);
+                   c->d_obs_active.get(), (const DevHand *)c->d_hand, g);
         else
             launch(c, HPE_PROF_OPT_DESCENT, k_opt_descent<false>, dim3(P), dim3(RF_NT), lds, d,
-                   c->d_obs_active, (const DevHand *)c->d_hand, g);
-        launch(c, HPE_PROF_OPT_MOVE, k_opt_move, dim3(P), dim3(HPE_NT), 0, d, c->d_obs_active,
+                   c->d_obs_active.get(), (const DevHand *)c->d_hand, g);
+        launch(c, HPE_PROF_OPT_MOVE, k_opt_move, dim3(P), dim3(HPE_NT), 0, d, c->d_obs_active.get(),
                (const DevHand *)c->d_hand, g);
     }
     HIPCHK(c, hipGetLastError());
@@ -1865,7 +1682,7 @@ static int refine_launch(hpe_ctx *c, const FrameIo &io, int do_refine, const Pre
         launch(c, HPE_PROF_REFINE,
                c->refine_exact ? k_refine<true, false, false, true> : k_refine<true, false, true, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0, io.obs, (const DevHand *)c->d_hand,
-               c->d_match, c->d_evals, do_refine, a, mw, pk, ps, sp);
+               c->d_match.get(), c->d_evals.get(), do_refine, a, mw, pk, ps, sp);
     } else if (io.n_max <= RF_STAGE_MAX) {
         // The dynamic LDS is padded to (almost) the whole CU: no other workgroup can share
         // the CU of this single-workgroup, latency-bound kernel.  Fixed size: the launch is
@@ -1873,25 +1690,25 @@ static int refine_launch(hpe_ctx *c, const FrameIo &io, int do_refine, const Pre
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<true> : k_refine<true, false, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0, io.obs, (const DevHand *)c->d_hand,
-               c->d_match, c->d_evals, do_refine, a, mw, pk, ps, nosp);
+               c->d_match.get(), c->d_evals.get(), do_refine, a, mw, pk, ps, nosp);
     } else if (c->refine_mw && mw_fits(c)) {  // multi-workgroup form: MW_MAX_Q helpers own cloud slices
         mw.job = c->d_mw_job;
         mw.part = c->d_mw_part;
         mw.ctr = c->d_mw_ctr;
         mw.err = c->d_mw_err;
-        mw.err_host = c->h_mw_err_dev;
+        mw.err_host = c->h_mw_err.dev();
         mw.Q = MW_MAX_Q;
         mw.spin = c->mw_spin;
         const dim3 grid(1 + MW_MAX_Q + (pa ? PREP_WG : 0));
         launch(c, HPE_PROF_REFINE,
                c->refine_exact ? k_refine<false, true> : k_refine<false, true, true>, grid,
                dim3(RF_NT), (unsigned)prep_lds_bytes(), d_x0, io.obs, (const DevHand *)c->d_hand,
-               c->d_match, c->d_evals, do_refine, a, mw, pk, ps, nosp);
+               c->d_match.get(), c->d_evals.get(), do_refine, a, mw, pk, ps, nosp);
     } else {
         const dim3 grid(pa ? 1 + PREP_WG : 1);
         launch(c, HPE_PROF_REFINE, c->refine_exact ? k_refine<false> : k_refine<false, false, true>,
                grid, dim3(RF_NT), RF_DYN_LDS, d_x0,
-               io.obs, (const DevHand *)c->d_hand, c->d_match, c->d_evals, do_refine, a,
+               io.obs, (const DevHand *)c->d_hand, c->d_match.get(), c->d_evals.get(), do_refine, a,
                mw, pk, ps, nosp);
     }
     HIPCHK(c, hipGetLastError());
@@ -1963,7 +1780,7 @@ static int check_batch_call(hpe_ctx *c, int P, int B) {
 // The chunked calls' trailer: the call is its frames' last reader, and hpe_prepare_frame waits
 // for this event before it writes a slot.
 static int mark_seq_done(hpe_ctx *c) {
-    if (!c->seq_done) HIPCHK(c, hipEventCreateWithFlags(&c->seq_done, hipEventDisableTiming));
+    HIPCHK(c, c->seq_done.ensure(hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->seq_done, c->stream));
     c->seq_done_valid = true;
     return HPE_OK;
@@ -2008,12 +1825,12 @@ int hpe_subswarm_fini(hpe_ctx *c) {
     drop_graphs(c);  // graphs holding the exchange go before the communicator / the script
     const ncclResult_t r = c->ss.comm ? rccl_api().comm_destroy(c->ss.comm) : ncclSuccess;
     c->ss.comm = nullptr;
-    dfree(c->ss.d_script);
-    dfree(c->ss.d_script_k);
+    c->ss.d_script.reset();
+    c->ss.d_script_k.reset();
     c->ss.script_frames = 0;
     c->ss.on = false;
     c->ss.nranks = 0;
-    dfree(c->ss.d_gath);
+    c->ss.d_gath.reset();
     ++c->epoch;  // the captured tracking graphs hold the exchange
     if (r != ncclSuccess) return fail(c, HPE_E_HIP, "ncclCommDestroy: %s", rccl_api().error_string(r));
     return HPE_OK;
@@ -2035,19 +1852,10 @@ int hpe_subswarm_init_scripted(hpe_ctx *c, int nranks, int rank, const double *s
     } else {
         int rc = hpe_subswarm_fini(c);
         if (rc) return rc;
-        double *gath = nullptr, *scr = nullptr;
-        int *k = nullptr;
-        if (dalloc(&gath, rows) != hipSuccess || dalloc(&scr, n) != hipSuccess ||
-            dalloc(&k, (size_t)1) != hipSuccess) {
-            dfree(gath);
-            dfree(scr);
-            dfree(k);
+        if (alloc_all(c->ss.d_gath, rows, c->ss.d_script, n, c->ss.d_script_k, 1) != hipSuccess) {
             (void)hipGetLastError();
             return fail(c, HPE_E_HIP, "subswarm_init_scripted: no device memory for %d frames", frames);
         }
-        c->ss.d_gath = gath;
-        c->ss.d_script = scr;
-        c->ss.d_script_k = k;
         c->ss.script_frames = frames;
         c->ss.nranks = nranks;
         c->ss.rank = rank;
@@ -2073,14 +1881,14 @@ int hpe_subswarm_init(hpe_ctx *c, const unsigned char id[HPE_SUBSWARM_ID_BYTES],
     int rc = hpe_subswarm_fini(c);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, dalloc(&c->ss.d_gath, (size_t)nranks * (HPE_DOF + 1)));
+    HIPCHK(c, c->ss.d_gath.alloc((size_t)nranks * (HPE_DOF + 1)));
     HIPCHK(c, hipMemset(c->ss.d_gath, 0xFF, sizeof(double) * nranks * (HPE_DOF + 1)));  // NaN
     ncclUniqueId uid;
     std::memcpy(&uid, id, sizeof(uid));
     ncclComm_t comm = nullptr;
     const ncclResult_t r = api.comm_init_rank(&comm, nranks, uid, rank);
     if (r != ncclSuccess) {
-        dfree(c->ss.d_gath);
+        c->ss.d_gath.reset();
         return fail(c, HPE_E_HIP, "ncclCommInitRank(%d of %d): %s", rank, nranks, api.error_string(r));
     }
     c->ss.comm = comm;
@@ -2100,7 +1908,7 @@ int hpe_subswarm_init(hpe_ctx *c, const unsigned char id[HPE_SUBSWARM_ID_BYTES],
         c->ss.comm = nullptr;
         c->ss.on = false;
         c->ss.nranks = 0;
-        dfree(c->ss.d_gath);
+        c->ss.d_gath.reset();
         return fail(c, HPE_E_HIP, "subswarm warm-up all-gather: %s", api.error_string(r1));
     }
     HIPCHK(c, hipMemsetAsync(c->ss.d_gath, 0xFF, sizeof(double) * nranks * (HPE_DOF + 1), c->stream));
@@ -2239,42 +2047,31 @@ static int ensure_pipe(hpe_ctx *c, int need) {
     hpe_ctx::Pipe &pp = c->pipe;
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
     if (!pp.d_obs) {
-        HIPCHK(c, dalloc(&pp.d_obs, 2));
-        HIPCHK(c, dalloc(&pp.d_info, 2));
-        HIPCHK(c, dalloc(&pp.d_raw, 2 * npix));
-        HIPCHK(c, hipStreamCreateWithFlags(&pp.copy, hipStreamNonBlocking));
+        DevBuf<DevObs> obs;  // moved in last: a block that failed part way runs again in full
+        HIPCHK(c, obs.alloc(2));
+        HIPCHK(c, pp.d_info.alloc(2));
+        HIPCHK(c, pp.d_raw.alloc(2 * npix));
+        HIPCHK(c, c->pipe_copy.ensure(hipStreamNonBlocking));
         if (const char *u = std::getenv("HPE_PIPE_UPLOAD")) pp.zero_copy = u[0] != '1';
-        HIPCHK(c, dalloc(&pp.d_seq, 1));
-        HIPCHK(c, dalloc(&pp.d_dtf2, 2 * npix));
-        HIPCHK(c, dalloc(&pp.d_split, 4));
+        HIPCHK(c, pp.d_seq.alloc(1));
+        HIPCHK(c, pp.d_dtf2.alloc(2 * npix));
+        HIPCHK(c, pp.d_split.alloc(4));
         HIPCHK(c, hipMemset(pp.d_split, 0, 4 * sizeof(int)));
-        HIPCHK(c, hipHostMalloc((void **)&pp.h_done, sizeof(unsigned long long),
-                                hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(c, hipHostGetDevicePointer((void **)&pp.h_done_dev, pp.h_done, 0));
+        HIPCHK(c, pp.h_done.alloc(1, hipHostMallocMapped | hipHostMallocCoherent));
         for (int k = 0; k < 2; ++k) {
-            HIPCHK(c, hipHostMalloc((void **)&pp.h_raw[k], sizeof(float) * npix,
-                                    hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(c, hipHostGetDevicePointer((void **)&pp.h_raw_dev[k], pp.h_raw[k], 0));
-            HIPCHK(c, hipEventCreateWithFlags(&pp.used[k], hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&pp.raw_ready[k], hipEventDisableTiming));
+            HIPCHK(c, pp.h_raw[k].alloc(npix, hipHostMallocMapped | hipHostMallocCoherent));
+            HIPCHK(c, pp.used[k].ensure(hipEventDisableTiming));
+            HIPCHK(c, pp.raw_ready[k].ensure(hipEventDisableTiming));
         }
+        pp.d_obs = std::move(obs);
     }
     for (int k = 0; k < 2; ++k) {
         Slot &f = pp.fr[k];
-        if (!f.depth) {
-            HIPCHK(c, dalloc(&f.depth, npix));
-            HIPCHK(c, dalloc(&f.dt, npix));
-        }
-        if (f.cap < need) {
-            dfree(f.cx);
-            dfree(f.cy);
-            dfree(f.cz);
-            HIPCHK(c, dalloc(&f.cx, (size_t)need));
-            HIPCHK(c, dalloc(&f.cy, (size_t)need));
-            HIPCHK(c, dalloc(&f.cz, (size_t)need));
-            f.cap = need;
+        if (f.cap < need) {  // a buffer about to go is no sequence's current frame
             ++c->epoch;
+            pp.cur = -1;
         }
+        HIPCHK(c, slot_buffers(f, need));
         f.valid = true;
         f.n_max = need;
         pp.used_valid[k] = false;
@@ -2296,7 +2093,7 @@ int hpe_pipeline_begin(hpe_ctx *c, const float *depth_mm, int to_cm, int downsam
     pp.downsample = downsample ? 1 : 0;
     pp.focal = focal;
     HIPCHK(c, hipMemsetAsync(pp.d_seq, 0, sizeof(unsigned long long), c->stream));
-    __atomic_store_n(pp.h_done, 0ull, __ATOMIC_RELEASE);
+    __atomic_store_n(pp.h_done.get(), 0ull, __ATOMIC_RELEASE);
     pp.enq = 0;
     pp.used_seq[0] = pp.used_seq[1] = 0;
     // the first frame: prepared on the tracking stream
@@ -2565,7 +2362,7 @@ static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_stat
                            (const double *)d_states, hand, (const WinPar *)c->win.d_par, io.win, act);
     if (prep || refine)
         launch(c, HPE_PROF_REFINE, kr, dim3(prep ? 1 + PREP_WG : 1, B), dim3(RF_NT), RF_DYN_LDS,
-               d_states, obs, hand, c->d_bevals, refine ? 1 : 0, io.prep, (const DevWindow *)io.win,
+               d_states, obs, hand, c->d_bevals.get(), refine ? 1 : 0, io.prep, (const DevWindow *)io.win,
                act, io.unit, io.raw, (const int *)io.cur);
     const size_t stride = c->sw.stride;
     const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
@@ -2691,11 +2488,7 @@ static int window_from_pose(hpe_ctx *c, const DevHand *hand, const double *theta
         return fail(c, HPE_E_ARG, "margins %g, %g: negative or not finite", margin_xy, margin_z);
     HIPCHK(c, hipSetDevice(c->device));
     hpe_ctx::LaneWin &w = c->win;
-    if (!w.d_one) {
-        HIPCHK(c, dalloc(&w.d_one_state, (size_t)HPE_STATE_N));
-        HIPCHK(c, dalloc(&w.d_one_par, 1));
-        HIPCHK(c, dalloc(&w.d_one, 1));
-    }
+    if (!w.d_one) HIPCHK(c, alloc_all(w.d_one_state, (size_t)HPE_STATE_N, w.d_one_par, 1, w.d_one, 1));
     const WinPar par{margin_xy, margin_z, focal, 1, 0};
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(w.d_one_state, theta, sizeof(double) * HPE_DOF, hipMemcpyHostToDevice));
@@ -2766,7 +2559,7 @@ int hpe_batch_windows_readback(hpe_ctx *c, int parity, int B, hpe_window *out) {
     if (B < 1 || B > HPE_BATCH_MAX)
         return fail(c, HPE_E_ARG, "windows of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
     if (!out) return fail(c, HPE_E_ARG, "null windows");
-    if (!c->win.d_tab)
+    if (!c->rb.d_obs)  // (the table is allocated with the raw batch's)
         return fail(c, HPE_E_STATE, "no window table: no raw or live batch has run yet");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2890,8 +2683,8 @@ int hpe_track_pipelined(hpe_ctx *c, int P, int refine, double *d_state, const fl
         std::memcpy(pp.h_raw[nxt], next_depth_mm, sizeof(float) * npix);
         if (!pp.zero_copy) {  // SDMA upload, overlapping the frame still running
             HIPCHK(c, hipMemcpyAsync(pp.d_raw + nxt * npix, pp.h_raw[nxt], sizeof(float) * npix,
-                                     hipMemcpyHostToDevice, pp.copy));
-            HIPCHK(c, hipEventRecord(pp.raw_ready[nxt], pp.copy));
+                                     hipMemcpyHostToDevice, c->pipe_copy));
+            HIPCHK(c, hipEventRecord(pp.raw_ready[nxt], c->pipe_copy));
             HIPCHK(c, hipStreamWaitEvent(c->stream, pp.raw_ready[nxt], 0));
         }
     }
@@ -2904,10 +2697,10 @@ int hpe_track_pipelined(hpe_ctx *c, int P, int refine, double *d_state, const fl
     FrameIo io = pipe_frame_io(c, cur, d_state);
     if (pp.zero_copy) {  // the final kernel publishes the frame's number
         io.seq = pp.d_seq;
-        io.done_host = pp.h_done_dev;
+        io.done_host = pp.h_done.dev();
     }
     // the next raw frame: in its pinned host buffer (zero copy) or uploaded to d_raw[nxt]
-    const float *raw = pp.zero_copy ? pp.h_raw_dev[nxt] : pp.d_raw + nxt * npix;
+    const float *raw = pp.zero_copy ? pp.h_raw[nxt].dev() : pp.d_raw + nxt * npix;
     const PrepArgs pa = prep_args(c, pp.fr[nxt], raw, pp.to_cm, pp.downsample, pp.focal,
                                   pp.d_obs + nxt, pp.d_info + nxt);
     rc = run_graphed(c, c->graphs[hpe_ctx::GC_PIPE], key,
@@ -3062,22 +2855,24 @@ static int ensure_raw_batch(hpe_ctx *c, int B, int to_cm, double focal) {
     hpe_ctx::RawBatch &rb = c->rb;
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W, M = HPE_BATCH_MAX;
     if (!rb.d_obs) {
-        HIPCHK(c, dalloc(&rb.d_obs, 2 * M));
-        HIPCHK(c, dalloc(&rb.d_info, 2 * M));
-        HIPCHK(c, dalloc(&rb.d_tab, 2 * M));
-        HIPCHK(c, dalloc(&rb.d_ctr, 32 * M));
+        DevBuf<DevObs> obs;  // moved in last: a block that failed part way runs again in full
+        HIPCHK(c, obs.alloc(2 * M));
+        HIPCHK(c, rb.d_info.alloc(2 * M));
+        HIPCHK(c, rb.d_tab.alloc(2 * M));
+        HIPCHK(c, rb.d_ctr.alloc(32 * M));
         HIPCHK(c, hipMemset(rb.d_ctr, 0, sizeof(unsigned) * 32 * M));
-        HIPCHK(c, dalloc(&rb.d_raw, M));
-        HIPCHK(c, dalloc(&rb.d_cur, 2 * M));
+        HIPCHK(c, rb.d_raw.alloc(M));
+        HIPCHK(c, rb.d_cur.alloc(2 * M));
         // the lane windows' table, by [parity][lane] like d_tab, and their parameters; until a
         // windowed call writes them, whole-frame windows
-        HIPCHK(c, dalloc(&c->win.d_tab, 2 * M));
-        HIPCHK(c, dalloc(&c->win.d_par, 1));
+        HIPCHK(c, c->win.d_tab.alloc(2 * M));
+        HIPCHK(c, c->win.d_par.alloc(1));
         std::vector<DevWindow> whole(2 * M, DevWindow{0, HPE_IMG_H - 1, 0, HPE_IMG_W - 1, -HUGE_VAL,
                                                       HUGE_VAL, -HUGE_VALF, HUGE_VALF, {0, 0}});
         HIPCHK(c, hipMemcpy(c->win.d_tab, whole.data(), sizeof(DevWindow) * whole.size(),
                             hipMemcpyHostToDevice));
         HIPCHK(c, hipMemset(c->win.d_par, 0, sizeof(WinPar)));
+        rb.d_obs = std::move(obs);
     }
     if (B <= rb.lanes && to_cm == rb.to_cm && focal == rb.focal) return HPE_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3090,7 +2885,7 @@ static int ensure_raw_batch(hpe_ctx *c, int B, int to_cm, double focal) {
     const size_t o_tmp = 2 * frame, o_ctb = o_tmp + sizeof(double) * 3 * npix,
                  o_dtf = o_ctb + sizeof(double) * npix, bytes = o_dtf + sizeof(int) * npix;
     while (rb.lanes < B) {
-        HIPCHK(c, dalloc(&rb.arena[rb.lanes], bytes));
+        HIPCHK(c, rb.arena[rb.lanes].alloc(bytes));
         ++rb.lanes;
     }
     std::vector<PrepArgs> &tab = rb.tab;
@@ -3208,28 +3003,23 @@ static int ensure_live_batch(hpe_ctx *c, int B) {
     hpe_ctx::LiveBatch &lv = c->live;
     const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W, M = HPE_BATCH_MAX;
     if (!lv.d_tab) {
-        HIPCHK(c, dalloc(&lv.d_tab, 2 * M));
-        HIPCHK(c, dalloc(&lv.d_seq, 1));
-        HIPCHK(c, dalloc(&lv.d_act, HPE_BATCH_MAX));  // the lanes' activity words (lane pacing)
+        DevBuf<PrepArgs> tab;  // moved in last: a block that failed part way runs again in full
+        HIPCHK(c, tab.alloc(2 * M));
+        HIPCHK(c, lv.d_seq.alloc(1));
+        HIPCHK(c, lv.d_act.alloc(HPE_BATCH_MAX));  // the lanes' activity words (lane pacing)
         HIPCHK(c, hipMemset(lv.d_act, 0, sizeof(int) * HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&lv.d_unit, 1));  // a u16 batch's depth unit (lane input)
-        HIPCHK(c, hipHostMalloc((void **)&lv.h_done, sizeof(unsigned long long),
-                                hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(c, hipHostGetDevicePointer((void **)&lv.h_done_dev, lv.h_done, 0));
+        HIPCHK(c, lv.d_unit.alloc(1));  // a u16 batch's depth unit (lane input)
+        HIPCHK(c, lv.h_done.alloc(1, hipHostMallocMapped | hipHostMallocCoherent));
+        lv.d_tab = std::move(tab);
     }
-    for (; lv.lanes < B; ++lv.lanes)
-        for (int p = 0; p < 2; ++p) {
-            float *&h = lv.h_raw[p][lv.lanes];
-            if (!h)
-                HIPCHK(c, hipHostMalloc((void **)&h, sizeof(float) * npix,
-                                        hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(c, hipHostGetDevicePointer((void **)&lv.h_raw_dev[p][lv.lanes], h, 0));
-        }
+    for (; lv.lanes < B; ++lv.lanes)  // (a lane counts once both its buffers are there)
+        for (int p = 0; p < 2; ++p)
+            if (!lv.h_raw[p][lv.lanes]) HIPCHK(c, lv.h_raw[p][lv.lanes].alloc(npix, hipHostMallocMapped | hipHostMallocCoherent));
     if (lv.tab_gen == c->rb.tab_gen && lv.tab_lanes == lv.lanes) return HPE_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<PrepArgs> tab = c->rb.tab;
     for (int p = 0; p < 2; ++p)
-        for (int b = 0; b < lv.lanes; ++b) tab[p * M + b].raw = lv.h_raw_dev[p][b];
+        for (int b = 0; b < lv.lanes; ++b) tab[p * M + b].raw = lv.h_raw[p][b].dev();
     HIPCHK(c, hipMemcpy(lv.d_tab, tab.data(), sizeof(PrepArgs) * tab.size(), hipMemcpyHostToDevice));
     lv.tab_gen = c->rb.tab_gen;
     lv.tab_lanes = lv.lanes;
@@ -3289,15 +3079,10 @@ int hpe_set_batch_report(hpe_ctx *c, int depth, const hpe_report_watch *watch) {
                     "with (end it first)");
     if (depth && !r.d_par) {  // once, at full size: never inside a capture, never moved
         HIPCHK(c, hipSetDevice(c->device));
-        if (!r.h_ring) {
-            HIPCHK(c, hipHostMalloc((void **)&r.h_ring, REP_LANE_BYTES * HPE_BATCH_MAX,
-                                    hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(c, hipHostGetDevicePointer((void **)&r.h_ring_dev, r.h_ring, 0));
-            std::memset(r.h_ring, 0, REP_LANE_BYTES * HPE_BATCH_MAX);
-        }
-        if (!r.d_lane_seq) HIPCHK(c, dalloc(&r.d_lane_seq, HPE_BATCH_MAX));
-        if (!r.d_streak) HIPCHK(c, dalloc(&r.d_streak, HPE_BATCH_MAX));
-        HIPCHK(c, dalloc(&r.d_par, 1));  // the last: a set that failed half way is made up for
+        HIPCHK(c, r.h_ring.alloc(REP_LANE_BYTES * HPE_BATCH_MAX, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(r.h_ring, 0, REP_LANE_BYTES * HPE_BATCH_MAX);
+        // d_par, the guard, last: a set that failed part way runs again in full
+        HIPCHK(c, alloc_all(r.d_lane_seq, HPE_BATCH_MAX, r.d_streak, HPE_BATCH_MAX, r.d_par, 1));
     }
     r.depth = depth;  // no epoch bump: the live graphs are keyed by it (GraphKey::report)
     r.watch = w;
@@ -3330,7 +3115,7 @@ static int begin_reports(hpe_ctx *c, int B, double focal) {
 static int enqueue_report(hpe_ctx *c, int B, const double *d_states, int parity, const int *act,
                           unsigned sel, int kind) {
     const hpe_ctx::Report &r = c->rep;
-    const RepDev rd{(unsigned long long *)r.h_ring_dev, r.d_par, r.d_lane_seq, r.d_streak};
+    const RepDev rd{(unsigned long long *)r.h_ring.dev(), r.d_par, r.d_lane_seq, r.d_streak};
     hipLaunchKernelGGL(k_report_b, dim3(B), dim3(64), 0, c->stream, d_states,
                        (const DevHand *)c->d_lane_hands,
                        (const PrepInfo *)c->rb.d_info + parity * HPE_BATCH_MAX,
@@ -3427,23 +3212,15 @@ static int ensure_locate(hpe_ctx *c) {
     hpe_ctx::Locate &lo = c->loc;
     if (lo.d_frame) return HPE_OK;
     const size_t M = HPE_BATCH_MAX;
-    if (!lo.h_tab) {
-        HIPCHK(c, hipHostMalloc((void **)&lo.h_tab, (size_t)LOC_SLOT * M,
-                                hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(c, hipHostGetDevicePointer((void **)&lo.h_tab_dev, lo.h_tab, 0));
-        std::memset(lo.h_tab, 0, (size_t)LOC_SLOT * M);
-    }
-    if (!lo.d_res) HIPCHK(c, dalloc(&lo.d_res, M + 1));
+    HIPCHK(c, lo.h_tab.alloc((size_t)LOC_SLOT * M, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(lo.h_tab, 0, (size_t)LOC_SLOT * M);
+    HIPCHK(c, lo.d_res.alloc(M + 1));
     // (zeroed on the stream: the launches that read them follow it there)
-    if (!lo.d_act) {
-        HIPCHK(c, dalloc(&lo.d_act, M + 1));
-        HIPCHK(c, hipMemsetAsync(lo.d_act, 0, sizeof(int) * (M + 1), c->stream));
-    }
-    if (!lo.d_seq) {
-        HIPCHK(c, dalloc(&lo.d_seq, M));
-        HIPCHK(c, hipMemsetAsync(lo.d_seq, 0, sizeof(unsigned long long) * M, c->stream));
-    }
-    HIPCHK(c, dalloc(&lo.d_frame, (size_t)HPE_IMG_H * HPE_IMG_W));  // the last: see hpe_set_batch_report
+    HIPCHK(c, lo.d_act.alloc(M + 1));
+    HIPCHK(c, hipMemsetAsync(lo.d_act, 0, sizeof(int) * (M + 1), c->stream));
+    HIPCHK(c, lo.d_seq.alloc(M));
+    HIPCHK(c, hipMemsetAsync(lo.d_seq, 0, sizeof(unsigned long long) * M, c->stream));
+    HIPCHK(c, lo.d_frame.alloc((size_t)HPE_IMG_H * HPE_IMG_W));  // the guard, last (as hpe_set_batch_report)
     return HPE_OK;
 }
 
@@ -3503,7 +3280,7 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
     if (u16) HIPCHK(c, hipMemcpy(lv.d_unit, &unit_mm, sizeof(float), hipMemcpyHostToDevice));
     lv.unit_mm = u16 ? unit_mm : 1.f;
     HIPCHK(c, hipMemsetAsync(lv.d_seq, 0, sizeof(unsigned long long), c->stream));
-    __atomic_store_n(lv.h_done, 0ull, __ATOMIC_RELEASE);
+    __atomic_store_n(lv.h_done.get(), 0ull, __ATOMIC_RELEASE);
     lv.enq = 0;
     lv.used_seq[0] = lv.used_seq[1] = 0;
     // lane location's buffers, while nothing is in flight: a locate call of this batch (it needs
@@ -3632,7 +3409,7 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
     if (c->win.mode != HPE_WINDOW_OFF) io.win = c->win.d_tab + nxt * HPE_BATCH_MAX;
     io.follow = c->win.mode == HPE_WINDOW_FOLLOW;
     io.seq = lv.d_seq;
-    io.done_host = lv.h_done_dev;
+    io.done_host = lv.h_done.dev();
     if (lv.u16) io.unit = lv.d_unit;
     if (paced) {
         write_lane_act(c, B, lv.pending, given);
@@ -3673,12 +3450,12 @@ int hpe_track_batch_pipelined_u16(hpe_ctx *c, int P, int refine, int B, double *
 // bounds the context holds now.  Nothing a captured graph uses: no epoch bump.
 static int ensure_opt_lanes(hpe_ctx *c, int P, int G, int lanes) {
     OptLanes &s = c->optl;
-    if (!s.d_obs) HIPCHK(c, dalloc(&s.d_obs, HPE_BATCH_MAX));
+    if (!s.d_obs) HIPCHK(c, s.d_obs.alloc(HPE_BATCH_MAX));
     if (!(s.P == P && s.G >= G && s.seed == c->seed && s.lanes >= lanes)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight use the arenas
         if (lanes < s.lanes) lanes = s.lanes;        // grown, never shrunk
         if (G < s.G) G = s.G;
-        free_opt_lanes(s);
+        s.reset();
         const size_t e = sizeof(double) * (size_t)P * HPE_DOF;
         const size_t bytes[7] = {e, e, e, sizeof(double) * (size_t)P, sizeof(double) * 28,
                                  sizeof(double) * (size_t)(G > 0 ? G : 1),
@@ -3689,11 +3466,10 @@ static int ensure_opt_lanes(hpe_ctx *c, int P, int G, int lanes) {
             at += (bytes[k] + 127) & ~(size_t)127;
         }
         s.stride = at;
-        HIPCHK(c, dalloc(&s.arena, s.stride * (size_t)lanes));
+        HIPCHK(c, alloc_all(s.arena, s.stride * (size_t)lanes, s.normals, (size_t)P * HPE_DOF,
+                            s.bounds, (size_t)3 * HPE_DOF));
         // the counters start at 0 (on the stream: the launches that count follow it there)
         HIPCHK(c, hipMemsetAsync(s.arena, 0, s.stride * (size_t)lanes, c->stream));
-        HIPCHK(c, dalloc(&s.normals, (size_t)P * HPE_DOF));
-        HIPCHK(c, dalloc(&s.bounds, (size_t)3 * HPE_DOF));
         std::vector<double> nrm((size_t)P * HPE_DOF);
         hpe::make_normals(c->seed, P, nrm.data(), ST_OPT_NORMAL);
         HIPCHK(c, hipMemcpy(s.normals, nrm.data(), e, hipMemcpyHostToDevice));
@@ -3924,13 +3700,13 @@ int hpe_batch_pipeline_locate(hpe_ctx *c, int B, double *d_states, uint32_t lane
     const int cur = lv.cur, M = HPE_BATCH_MAX;
     // the lanes' current raw frames: the pinned buffers of the parity the next track call tracks
     for (int b = 0; b < B; ++b)
-        if (lanes >> b & 1) ln.raw[b] = lv.h_raw_dev[cur][b];
+        if (lanes >> b & 1) ln.raw[b] = lv.h_raw[cur][b].dev();
     DevWindow *const wcur = c->win.d_tab + cur * M;
     DevWindow *const woth = c->win.mode == HPE_WINDOW_FIXED ? c->win.d_tab + (cur ^ 1) * M : nullptr;
     const auto k_locate = lv.u16 ? k_locate_b<true> : k_locate_b<false>;
     hipLaunchKernelGGL(k_locate, dim3(B), dim3(LOC_NT), 0, c->stream, ln, (unsigned)lanes,
                        lv.unit_mm, lv.to_cm, lv.focal, wcur, woth,
-                       lo.d_act, lo.d_res, lo.d_seq, (unsigned long long *)lo.h_tab_dev);
+                       lo.d_act, lo.d_res, lo.d_seq, (unsigned long long *)lo.h_tab.dev());
     HIPCHK(c, hipGetLastError());
     // the locate kernel is enqueued: it advances the selected lanes' device counters, and it and
     // the preparation below read the pinned buffers of parity cur in place, behind everything
@@ -3997,8 +3773,9 @@ int hpe_profile_enable(hpe_ctx *c, int on) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (auto &pl : c->pools) {
         if (on && pl.ev.empty()) {
-            pl.ev.resize(2 * 8192);
-            for (auto &e : pl.ev) HIPCHK(c, hipEventCreate(&e));
+            std::vector<Event> ev(2 * 8192);  // published whole
+            for (auto &e : ev) HIPCHK(c, e.ensure(hipEventDefault));
+            pl.ev = std::move(ev);
         }
         pl.used = 0;
     }
@@ -4061,7 +3838,7 @@ int hpe_render_depth(hpe_ctx *c, const double theta[26], double focal, float *ou
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_theta(c, 1);
     if (rc) return rc;
-    if (!c->d_render) HIPCHK(c, dalloc(&c->d_render, (size_t)HPE_IMG_H * HPE_IMG_W));
+    if (!c->d_render) HIPCHK(c, c->d_render.alloc((size_t)HPE_IMG_H * HPE_IMG_W));
     HIPCHK(c, hipMemcpyAsync(c->d_theta, theta, sizeof(double) * HPE_DOF, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_build, dim3(1), dim3(HPE_NT), 0, c->stream, c->d_theta, 1, c->d_hand,
                        c->d_S, (double *)nullptr);
