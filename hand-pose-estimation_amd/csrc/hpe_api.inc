@@ -139,6 +139,8 @@ struct GraphKey {
     int report; // lane reports are on (hpe_set_batch_report): one more launch, k_report_b; else 0
     int u16;    // a live batch of 16-bit frames (hpe_batch_pipeline_begin_u16): the u16 ring
                 // kernels; never its depth unit, which device memory holds
+    int view;   // ... read through lane views (hpe_batch_pipeline_begin_view): the view kernels;
+                // never a view, which device memory holds too
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
@@ -147,7 +149,7 @@ struct GraphKey {
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
                next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
                hands == o.hands && pacing == o.pacing && report == o.report && u16 == o.u16 &&
-               to_cm == o.to_cm &&
+               view == o.view && to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -224,6 +226,8 @@ struct LaneFrameIo {
     // lane input: the pinned ring holds 16-bit pixels, in this depth unit (device memory; null:
     // float frames)
     const float *unit = nullptr;
+    // ... camera frames read through the lanes' views: unit then names the batch's ViewTab
+    bool view = false;
 };
 
 }  // namespace
@@ -374,9 +378,25 @@ struct hpe_ctx {
         bool u16 = false;
         float unit_mm = 1.f;  // the host's copy of *d_unit (the locate kernel takes it by value)
         DevBuf<float> d_unit;
-        size_t frame_bytes() const {
+        // lane views (hpe_batch_pipeline_begin_view): a u16 batch whose lane b delivers camera
+        // frames of views[b]; d_view holds the unit and the views (ViewTab), written at the begin,
+        // and stands where d_unit stands for a plain u16 batch.  views_B: the lanes of the last
+        // view begin (hpe_batch_views_readback), 0: none yet
+        bool view = false;
+        hpe_view views[HPE_BATCH_MAX] = {};
+        int views_B = 0;
+        DevBuf<ViewTab> d_view;
+        // what every pinned buffer holds, in floats: one 240x320 float frame, or more once a view
+        // batch needed it (grown for all lanes at once, never shrunk)
+        size_t raw_floats = (size_t)HPE_IMG_H * HPE_IMG_W;
+        size_t frame_bytes(int lane) const {
+            if (view) return sizeof(uint16_t) * (size_t)views[lane].pitch * (size_t)views[lane].height;
             return (u16 ? sizeof(uint16_t) : sizeof(float)) * (size_t)HPE_IMG_H * HPE_IMG_W;
         }
+        const float *unit_arg() const {  // the lane kernels' `unit` argument
+            return view ? (const float *)d_view.get() : u16 ? d_unit.get() : nullptr;
+        }
+        LaneSrc src() const { return view ? LANE_SRC_VIEW : u16 ? LANE_SRC_U16 : LANE_SRC_RING; }
     } live;
     // lane reports (hpe_set_batch_report): the setting the next begin reads (depth 0: off), and
     // what the rings hold -- the depth and lane count of the last batch begun with reports on
@@ -2205,7 +2225,7 @@ static LaneForm lane_form(hpe_ctx *c, int P, int B, const DevSwarm &d, const Lan
     LaneForm f{};
     f.paced = io.act != nullptr;
     f.hands = f.paced || lane_hands_set(c);
-    f.src = !io.prep ? LANE_SRC_NONE : io.unit ? LANE_SRC_U16 : io.raw ? LANE_SRC_RAW : LANE_SRC_RING;
+    f.src = !io.prep ? LANE_SRC_NONE : io.unit ? (io.view ? LANE_SRC_VIEW : LANE_SRC_U16) : io.raw ? LANE_SRC_RAW : LANE_SRC_RING;
     f.win = io.prep && io.win;
     f.live = io.seq != nullptr;
     f.rigid = !c->refine_exact;
@@ -2217,7 +2237,8 @@ static LaneForm lane_form(hpe_ctx *c, int P, int B, const DevSwarm &d, const Lan
 }
 
 // One selector per role: the instantiations the host can reach and no others (WIN needs a source;
-// PACED is the live batch's -- the ring, 16-bit or not -- in the HANDS shape and never FILT).
+// PACED is the live batch's -- the ring, 16-bit or not, or through views -- in the HANDS shape and
+// never FILT).
 extern "C++" {
 typedef void (*LaneRefineFn)(double *, const DevObs *, const DevHand *, int *, int, const PrepArgs *,
                              const DevWindow *, const int *, const float *, const float *const *,
@@ -2233,6 +2254,9 @@ static LaneRefineFn lane_refine_kernel_t(LaneSrc src, bool win) {
     case LANE_SRC_U16:
         return win ? k_refine_lane<RIGID, HANDS, LANE_SRC_U16, true, PACED>
                    : k_refine_lane<RIGID, HANDS, LANE_SRC_U16, false, PACED>;
+    case LANE_SRC_VIEW:
+        return win ? k_refine_lane<RIGID, HANDS, LANE_SRC_VIEW, true, PACED>
+                   : k_refine_lane<RIGID, HANDS, LANE_SRC_VIEW, false, PACED>;
     case LANE_SRC_RAW:
         if constexpr (!PACED)
             return win ? k_refine_lane<RIGID, HANDS, LANE_SRC_RAW, true, false>
@@ -2262,6 +2286,7 @@ static LanePrepareFn lane_prepare_kernel_t(bool win, bool paced) {
 }
 static LanePrepareFn lane_prepare_kernel(LaneSrc src, bool win, bool paced) {
     if (src == LANE_SRC_RAW) return lane_prepare_kernel_t<LANE_SRC_RAW>(win, false);
+    if (src == LANE_SRC_VIEW) return lane_prepare_kernel_t<LANE_SRC_VIEW>(win, paced);
     return src == LANE_SRC_U16 ? lane_prepare_kernel_t<LANE_SRC_U16>(win, paced)
                                : lane_prepare_kernel_t<LANE_SRC_RING>(win, paced);
 }
@@ -2999,9 +3024,11 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
 // pinned ring of every new lane, the frame counter, and the ring form of the PrepArgs table --
 // rb's entries with raw = the lane's pinned buffer of that parity -- rewritten whenever rb's
 // table was or a lane got its ring (the stream drained first: launches in flight read it).
-static int ensure_live_batch(hpe_ctx *c, int B) {
+// need_floats: what a pinned buffer must hold, in floats -- one 240x320 float frame, or a view
+// batch's largest camera frame; buffers that are too small are replaced for every lane at once.
+static int ensure_live_batch(hpe_ctx *c, int B, size_t need_floats) {
     hpe_ctx::LiveBatch &lv = c->live;
-    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W, M = HPE_BATCH_MAX;
+    const size_t M = HPE_BATCH_MAX;
     if (!lv.d_tab) {
         DevBuf<PrepArgs> tab;  // moved in last: a block that failed part way runs again in full
         HIPCHK(c, tab.alloc(2 * M));
@@ -3009,12 +3036,26 @@ static int ensure_live_batch(hpe_ctx *c, int B) {
         HIPCHK(c, lv.d_act.alloc(HPE_BATCH_MAX));  // the lanes' activity words (lane pacing)
         HIPCHK(c, hipMemset(lv.d_act, 0, sizeof(int) * HPE_BATCH_MAX));
         HIPCHK(c, lv.d_unit.alloc(1));  // a u16 batch's depth unit (lane input)
+        HIPCHK(c, lv.d_view.alloc(1));  // a view batch's unit and views
         HIPCHK(c, lv.h_done.alloc(1, hipHostMallocMapped | hipHostMallocCoherent));
         lv.d_tab = std::move(tab);
     }
+    const unsigned pin = hipHostMallocMapped | hipHostMallocCoherent;
+    if (need_floats > lv.raw_floats) {
+        // a view batch whose largest camera frame does not fit: every lane's ring again at that
+        // size (the stream has drained: nothing reads the old buffers), all lanes or none -- the
+        // new buffers are built aside and moved in together, and the table is rewritten below
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::vector<HostBuf<float>> fresh(2 * (size_t)lv.lanes);
+        for (auto &h : fresh) HIPCHK(c, h.alloc(need_floats, pin));
+        for (int p = 0; p < 2; ++p)
+            for (int b = 0; b < lv.lanes; ++b) lv.h_raw[p][b] = std::move(fresh[p * (size_t)lv.lanes + b]);
+        lv.raw_floats = need_floats;
+        lv.tab_lanes = -1;
+    }
     for (; lv.lanes < B; ++lv.lanes)  // (a lane counts once both its buffers are there)
         for (int p = 0; p < 2; ++p)
-            if (!lv.h_raw[p][lv.lanes]) HIPCHK(c, lv.h_raw[p][lv.lanes].alloc(npix, hipHostMallocMapped | hipHostMallocCoherent));
+            if (!lv.h_raw[p][lv.lanes]) HIPCHK(c, lv.h_raw[p][lv.lanes].alloc(lv.raw_floats, pin));
     if (lv.tab_gen == c->rb.tab_gen && lv.tab_lanes == lv.lanes) return HPE_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<PrepArgs> tab = c->rb.tab;
@@ -3236,12 +3277,21 @@ static int begin_locates(hpe_ctx *c, int B) {
     return HPE_OK;
 }
 
+static int check_view(hpe_ctx *c, const hpe_view &v, int lane);
+
 // The begin of a live batch in either frame format: u16 false, float mm frames; true, 16-bit
-// frames of unit_mm each.
+// frames of unit_mm each -- 240x320, or with `views` lane b's camera frame of views[b].
 static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool u16, float unit_mm,
-                            int to_cm, int downsample, double focal) {
+                            int to_cm, int downsample, double focal,
+                            const hpe_view *views = nullptr) {
     if (B < 1 || B > HPE_BATCH_MAX)
         return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    size_t need_floats = (size_t)HPE_IMG_H * HPE_IMG_W;
+    for (int b = 0; views && b < B; ++b) {
+        if (int vrc = check_view(c, views[b], b)) return vrc;
+        const size_t fl = ((size_t)views[b].pitch * (size_t)views[b].height + 1) / 2;
+        if (fl > need_floats) need_floats = fl;
+    }
     const bool paced = c->batch_pacing == HPE_PACING_FREE;
     if (!depth_mm || (!paced && lane_frames(depth_mm, B) != 1))
         return fail(c, HPE_E_ARG, "null frame array or lane frame");
@@ -3272,9 +3322,18 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
     lv.cur = -1;
     to_cm = to_cm ? 1 : 0;
     int rc = ensure_batch_lanes(c);
-    if (rc || (rc = ensure_raw_batch(c, B, to_cm, focal)) || (rc = ensure_live_batch(c, B))) return rc;
+    if (rc || (rc = ensure_raw_batch(c, B, to_cm, focal)) || (rc = ensure_live_batch(c, B, need_floats))) return rc;
     if ((rc = write_windows(c, focal, to_cm))) return rc;
     lv.u16 = u16;
+    lv.view = views != nullptr;
+    if (views) {  // the unit and the views, one block (the stream has drained)
+        ViewTab vt{};
+        vt.unit = unit_mm;
+        std::memcpy(vt.view, views, sizeof(hpe_view) * (size_t)B);
+        HIPCHK(c, hipMemcpy(lv.d_view, &vt, sizeof(vt), hipMemcpyHostToDevice));
+        std::memcpy(lv.views, views, sizeof(hpe_view) * (size_t)B);
+        lv.views_B = B;
+    }
     // the depth unit, as the windows' parameters: device memory, not the graphs, holds it (the
     // stream has drained)
     if (u16) HIPCHK(c, hipMemcpy(lv.d_unit, &unit_mm, sizeof(float), hipMemcpyHostToDevice));
@@ -3290,15 +3349,15 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
     // frame 0 of every lane: into its pinned buffer of parity 0, prepared from there
     for (int b = 0; b < B; ++b)
         if ((given >> b & 1) && depth_mm[b] != lv.h_raw[0][b])
-            std::memcpy(lv.h_raw[0][b], depth_mm[b], lv.frame_bytes());
+            std::memcpy(lv.h_raw[0][b], depth_mm[b], lv.frame_bytes(b));
     const bool win = c->win.mode != HPE_WINDOW_OFF;
     // paced: only the lanes given a frame prepare one; the others start empty
     if (paced) write_lane_act(c, B, 0, given);
-    hipLaunchKernelGGL(lane_prepare_kernel(u16 ? LANE_SRC_U16 : LANE_SRC_RING, win, paced),
+    hipLaunchKernelGGL(lane_prepare_kernel(lv.src(), win, paced),
                        dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream, (const PrepArgs *)lv.d_tab,
                        (const DevWindow *)(win ? c->win.d_tab : nullptr),
                        (const int *)(paced ? lv.d_act : nullptr),
-                       (const float *)(u16 ? lv.d_unit : nullptr), (const float *const *)nullptr,
+                       lv.unit_arg(), (const float *const *)nullptr,
                        (const int *)nullptr);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3323,6 +3382,66 @@ int hpe_batch_pipeline_begin_u16(hpe_ctx *c, int B, const uint16_t *const *depth
     return live_batch_begin(c, B, (const void *const *)depth, true, unit_mm, to_cm, downsample, focal);
 }
 
+// One lane's view against the refusals of include/hpe.h "Lane views".
+static int check_view(hpe_ctx *c, const hpe_view &v, int lane) {
+    if (v.step < 1 || v.step > 8)
+        return fail(c, HPE_E_ARG, "lane %d: view step %d outside 1..8", lane, v.step);
+    if (v.width < 1 || v.height < 1 || v.pitch < v.width)
+        return fail(c, HPE_E_ARG, "lane %d: view of a %d x %d camera image with pitch %d", lane,
+                    v.width, v.height, v.pitch);
+    if (v.pitch > HPE_VIEW_DIM_MAX || v.height > HPE_VIEW_DIM_MAX ||
+        (long long)v.pitch * v.height > HPE_VIEW_PIXELS_MAX)
+        return fail(c, HPE_E_ARG, "lane %d: view pitch %d or height %d above %d, or more than %d "
+                    "pixels per frame", lane, v.pitch, v.height, HPE_VIEW_DIM_MAX, HPE_VIEW_PIXELS_MAX);
+    if ((v.flags & ~HPE_VIEW_FLIP_COLS) || v.pad)
+        return fail(c, HPE_E_ARG, "lane %d: unknown view flags 0x%x or non-zero pad %d", lane,
+                    v.flags, v.pad);
+    return HPE_OK;
+}
+
+int hpe_batch_pipeline_begin_view(hpe_ctx *c, int B, const uint16_t *const *frames,
+                                  const hpe_view *views, float unit_mm, int to_cm,
+                                  int downsample, double focal) {
+    if (!c) return HPE_E_ARG;
+    if (!views) return fail(c, HPE_E_ARG, "null views");
+    return live_batch_begin(c, B, (const void *const *)frames, true, unit_mm, to_cm, downsample,
+                            focal, views);
+}
+
+int hpe_view_fit(int width, int height, int pitch, double fx, double cx, double cy, int step,
+                 uint32_t flags, hpe_view *out, double *focal_out, double residual_px[2]) {
+    if (!out || !std::isfinite(fx) || !(fx > 0) || !std::isfinite(cx) || !std::isfinite(cy))
+        return HPE_E_ARG;
+    const bool flip = (flags & HPE_VIEW_FLIP_COLS) != 0;
+    const double r0 = cy - 120.0 * step, c0 = cx - (flip ? 159.0 : 160.0) * step;
+    if (!(std::fabs(r0) < 1e9) || !(std::fabs(c0) < 1e9)) return HPE_E_ARG;
+    const hpe_view v = {width, height, pitch, (int32_t)std::lrint(r0), (int32_t)std::lrint(c0),
+                        step, flags, 0};
+    if (check_view(nullptr, v, 0)) return HPE_E_ARG;
+    *out = v;
+    if (focal_out) *focal_out = fx / step;
+    if (residual_px) {  // the principal point in model pixels, less (160, 120)
+        const double mc = (cx - v.col0) / step;
+        residual_px[0] = (flip ? 319.0 - mc : mc) - 160.0;
+        residual_px[1] = (cy - v.row0) / step - 120.0;
+    }
+    return HPE_OK;
+}
+
+int hpe_batch_views_readback(hpe_ctx *c, int B, hpe_view *out) {
+    if (!c) return HPE_E_ARG;
+    if (!out) return fail(c, HPE_E_ARG, "null views");
+    hpe_ctx::LiveBatch &lv = c->live;
+    if (!lv.views_B) return fail(c, HPE_E_STATE, "no view batch has begun (hpe_batch_pipeline_begin_view)");
+    if (B < 1 || B > lv.views_B)
+        return fail(c, HPE_E_ARG, "%d lanes, the last view batch began with %d", B, lv.views_B);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, (const char *)lv.d_view.get() + offsetof(ViewTab, view),
+                        sizeof(hpe_view) * (size_t)B, hipMemcpyDeviceToHost));
+    return HPE_OK;
+}
+
 // Lane `lane`'s pinned buffer of the parity the next track call reads, once the device has read
 // the frame it last held (the track call's own wait, before its copy).
 int hpe_batch_frame_buffer(hpe_ctx *c, int lane, void **buf_out, size_t *bytes_out) {
@@ -3339,7 +3458,7 @@ int hpe_batch_frame_buffer(hpe_ctx *c, int lane, void **buf_out, size_t *bytes_o
         return fail(c, HPE_E_HIP, "live batch frame %llu did not complete",
                     (unsigned long long)lv.used_seq[nxt]);
     *buf_out = lv.h_raw[nxt][lane];
-    if (bytes_out) *bytes_out = lv.frame_bytes();
+    if (bytes_out) *bytes_out = lv.frame_bytes(lane);
     return HPE_OK;
 }
 
@@ -3384,7 +3503,7 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
                         (unsigned long long)lv.used_seq[nxt]);
         for (int b = 0; b < B; ++b)  // only the lanes given a frame, and not one filled in place
             if ((given >> b & 1) && next_depth_mm[b] != lv.h_raw[nxt][b])
-                std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], lv.frame_bytes());
+                std::memcpy(lv.h_raw[nxt][b], next_depth_mm[b], lv.frame_bytes(b));
     }
     const int G = ensure_tracking(c, P, B);  // (the lanes' tables are the begin's)
     if (G < 0) return G;
@@ -3401,6 +3520,7 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
     key.downsample = 1;
     key.focal = lv.focal;
     key.u16 = lv.u16 ? 1 : 0;  // ... nor the frame format (never the unit)
+    key.view = lv.view ? 1 : 0;  // ... nor whether it is read through views (never a view)
     // a frame of a raw batch's on the descriptors of parity cur, with the ring's preparation (the
     // next frames read from the pinned buffers of parity nxt), no history or cursor, and the final
     // launch that publishes the batch's frame number
@@ -3410,7 +3530,8 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
     io.follow = c->win.mode == HPE_WINDOW_FOLLOW;
     io.seq = lv.d_seq;
     io.done_host = lv.h_done.dev();
-    if (lv.u16) io.unit = lv.d_unit;
+    io.unit = lv.unit_arg();
+    io.view = lv.view;
     if (paced) {
         write_lane_act(c, B, lv.pending, given);
         io.act = lv.d_act;
@@ -3679,7 +3800,7 @@ int hpe_batch_pipeline_locate(hpe_ctx *c, int B, double *d_states, uint32_t lane
     if (!d_states || !tmpl) return fail(c, HPE_E_ARG, "null device states or pose templates");
     if (!lanes || (B < 32 && lanes >> B))
         return fail(c, HPE_E_ARG, "lane mask 0x%x: empty, or a bit at or above B = %d", lanes, B);
-    LocLanes ln{};
+    LocLanesView ln{};
     for (int b = 0; b < B; ++b)  // the selected lanes' entries alone are read
         if (lanes >> b & 1)
             if (int rc = locate_par(c, params ? params[b] : LOC_DEFAULTS, b, &ln.par[b])) return rc;
@@ -3703,10 +3824,17 @@ int hpe_batch_pipeline_locate(hpe_ctx *c, int B, double *d_states, uint32_t lane
         if (lanes >> b & 1) ln.raw[b] = lv.h_raw[cur][b].dev();
     DevWindow *const wcur = c->win.d_tab + cur * M;
     DevWindow *const woth = c->win.mode == HPE_WINDOW_FIXED ? c->win.d_tab + (cur ^ 1) * M : nullptr;
-    const auto k_locate = lv.u16 ? k_locate_b<true> : k_locate_b<false>;
-    hipLaunchKernelGGL(k_locate, dim3(B), dim3(LOC_NT), 0, c->stream, ln, (unsigned)lanes,
-                       lv.unit_mm, lv.to_cm, lv.focal, wcur, woth,
-                       lo.d_act, lo.d_res, lo.d_seq, (unsigned long long *)lo.h_tab.dev());
+    if (lv.view) {  // the lanes' camera frames, read through their views
+        std::memcpy(ln.view, lv.views, sizeof(ln.view));
+        hipLaunchKernelGGL((k_locate_b<true, true>), dim3(B), dim3(LOC_NT), 0, c->stream, ln,
+                           (unsigned)lanes, lv.unit_mm, lv.to_cm, lv.focal, wcur, woth, lo.d_act.get(),
+                           lo.d_res.get(), lo.d_seq.get(), (unsigned long long *)lo.h_tab.dev());
+    } else {
+        const auto k_locate = lv.u16 ? k_locate_b<true> : k_locate_b<false>;
+        hipLaunchKernelGGL(k_locate, dim3(B), dim3(LOC_NT), 0, c->stream, (const LocLanes &)ln,
+                           (unsigned)lanes, lv.unit_mm, lv.to_cm, lv.focal, wcur, woth, lo.d_act.get(),
+                           lo.d_res.get(), lo.d_seq.get(), (unsigned long long *)lo.h_tab.dev());
+    }
     HIPCHK(c, hipGetLastError());
     // the locate kernel is enqueued: it advances the selected lanes' device counters, and it and
     // the preparation below read the pinned buffers of parity cur in place, behind everything
@@ -3717,10 +3845,10 @@ int hpe_batch_pipeline_locate(hpe_ctx *c, int B, double *d_states, uint32_t lane
     lv.used_seq[cur] = lv.enq + 1;
     // the found lanes' current frames prepared again through their new windows: the begin's
     // kernel in its windowed, idle-aware form, gated by the table the locate kernel filled
-    hipLaunchKernelGGL(lane_prepare_kernel(lv.u16 ? LANE_SRC_U16 : LANE_SRC_RING, true, true),
+    hipLaunchKernelGGL(lane_prepare_kernel(lv.src(), true, true),
                        dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
                        (const PrepArgs *)lv.d_tab + cur * M, (const DevWindow *)wcur,
-                       (const int *)lo.d_act, (const float *)(lv.u16 ? lv.d_unit : nullptr),
+                       (const int *)lo.d_act, lv.unit_arg(),
                        (const float *const *)nullptr, (const int *)nullptr);
     LocTmpl tp{};
     std::memcpy(tp.th, tmpl, sizeof(double) * HPE_DOF * (size_t)B);

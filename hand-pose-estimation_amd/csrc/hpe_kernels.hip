@@ -1375,6 +1375,10 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
 //       U16   hpe_batch_pipeline_begin_u16: the ring holding unsigned 16-bit pixels, read in place
 //             and multiplied by the batch's depth unit *unit -- device memory written at the
 //             begin, never a captured argument (PrepArgsU16, hpe_prep.hpp)
+//       VIEW  hpe_batch_pipeline_begin_view: the ring holding the lane's camera frame, 16-bit
+//             pixels at the camera's resolution, read in place through the lane's view -- `unit`
+//             names a ViewTab, the depth unit and the lanes' views behind it, device memory
+//             written at the begin like the unit (PrepArgsView, hpe_prep.hpp)
 //   WIN: hpe_set_batch_window.  The frame is read through the lane's window wtab[b] (the
 //     DevWindow table next to the PrepArgs table, same parity offset), in the band workgroups and
 //     the distance transform's mask alike (prep_workgroup<true>): the preparation of the frame
@@ -1390,10 +1394,10 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
 //     publishes the call's frame number whether or not lane 0 tracks.
 //   HANDS: hpe_set_batch_hands.  The hand is entry blockIdx.y of the flat table (lane_hand).
 // The host names these combinations and no others (hpe_api.inc, the lane_*_kernel selectors):
-// WIN needs a source; PACED is the live batch's, so RING or U16 (or NONE, its ending frame), and
+// WIN needs a source; PACED is the live batch's, so RING, U16 or VIEW (or NONE, its ending frame), and
 // is built in the HANDS shape alone -- the table holds the context's hand in every entry while
 // no lane hands are set, which is pinned bit-identical to the !HANDS forms.
-enum LaneSrc { LANE_SRC_NONE, LANE_SRC_RAW, LANE_SRC_RING, LANE_SRC_U16 };
+enum LaneSrc { LANE_SRC_NONE, LANE_SRC_RAW, LANE_SRC_RING, LANE_SRC_U16, LANE_SRC_VIEW };
 #define HPE_ACT_TRACK 1
 #define HPE_ACT_PREP 2
 __device__ __forceinline__ DevSwarm lane_swarm(DevSwarm sw, size_t stride) {
@@ -1525,8 +1529,8 @@ __global__ void k_raw_begin_b(BatchRaw first, int n, const float **__restrict__ 
 }
 
 // The preparation of lane blockIdx.y from source SRC: its table entry, and with it RAW: on raw
-// frame cur + next (three independent loads); RING: nothing else; U16: the depth unit.  Only the
-// preparation workgroups call it.
+// frame cur + next (three independent loads); RING: nothing else; U16: the depth unit; VIEW: the
+// unit and the lane's view, two more independent loads.  Only the preparation workgroups call it.
 template <LaneSrc SRC>
 __device__ __forceinline__ auto lane_prep(const PrepArgs *__restrict__ tab,
                                           const float *__restrict__ unit,
@@ -1544,6 +1548,13 @@ __device__ __forceinline__ auto lane_prep(const PrepArgs *__restrict__ tab,
         PrepArgsU16 a;
         static_cast<PrepArgs &>(a) = tab[blockIdx.y];
         a.unit = *unit;
+        return a;
+    } else if constexpr (SRC == LANE_SRC_VIEW) {
+        const ViewTab *__restrict__ const vt = (const ViewTab *)unit;
+        PrepArgsView a;
+        static_cast<PrepArgs &>(a) = tab[blockIdx.y];
+        a.unit = vt->unit;
+        a.view = vt->view[blockIdx.y];
         return a;
     } else {
         return tab[blockIdx.y];

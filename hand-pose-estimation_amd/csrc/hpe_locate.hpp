@@ -46,7 +46,11 @@ struct LocLanes {
 struct LocTmpl {
     double th[HPE_BATCH_MAX][HPE_DOF];
 };
-static_assert(sizeof(LocLanes) <= 2048 && sizeof(LocTmpl) <= 3584, "kernel arguments");
+// The same with the lanes' views (a view batch's locate)
+struct LocLanesView : LocLanes {
+    hpe_view view[HPE_BATCH_MAX];
+};
+static_assert(sizeof(LocLanesView) <= 2048 && sizeof(LocTmpl) <= 3584, "kernel arguments");
 
 struct LocBox {
     int row_lo, row_hi, col_lo, col_hi;
@@ -79,11 +83,21 @@ struct LocPix {
     double Z;
     bool valid;
 };
-template <bool U16>
+// VIEW: raw is the lane's camera frame, and pixel `pix` of the model image is picked through the
+// lane's view *vw (view_pick, hpe_prep.hpp: the preparation's own index arithmetic and select).
+template <bool U16, bool VIEW = false>
 __device__ __forceinline__ LocPix loc_pixel(const void *__restrict__ raw, int pix, float unit,
-                                            int to_cm, const LocPar &p) {
-    const float rv = U16 ? (float)((const unsigned short *)raw)[pix] * unit
-                         : ((const float *)raw)[pix];
+                                            int to_cm, const LocPar &p,
+                                            const hpe_view *vw = nullptr) {
+    static_assert(U16 || !VIEW, "a view reads 16-bit pixels");
+    float rv;
+    if constexpr (VIEW) {
+        bool inside;
+        const unsigned short u = ((const unsigned short *)raw)[view_pick(*vw, pix, &inside)];
+        rv = (float)(inside ? u : (unsigned short)0) * unit;
+    } else {
+        rv = U16 ? (float)((const unsigned short *)raw)[pix] * unit : ((const float *)raw)[pix];
+    }
     LocPix q;
     q.r = pix / HPE_IMG_W;
     q.c = pix - HPE_IMG_W * q.r;
@@ -135,8 +149,11 @@ __device__ __forceinline__ LocSums loc_block_sums(LocSums s, unsigned long long 
 // the record is also published to the lane's slot of the pinned host table with the report
 // ring's begin / end words (hpe_report.hpp), seq = ++lane_seq[b] -- one thread stores the
 // whole slot, every word a system-scope store, the end word a release.
-template <bool U16>
-__global__ __launch_bounds__(LOC_NT) void k_locate_b(LocLanes ln, unsigned sel, float unit, int to_cm,
+// VIEW (hpe_batch_pipeline_begin_view): ln is a LocLanesView, the lanes' views behind the frames
+// and parameters, and all three sweeps read the lane's camera frame through its view.
+template <bool U16, bool VIEW = false>
+__global__ __launch_bounds__(LOC_NT) void k_locate_b(std::conditional_t<VIEW, LocLanesView, LocLanes> ln,
+                                                     unsigned sel, float unit, int to_cm,
                                                      double focal, DevWindow *__restrict__ wcur,
                                                      DevWindow *__restrict__ woth,
                                                      int *__restrict__ act,
@@ -156,13 +173,15 @@ __global__ __launch_bounds__(LOC_NT) void k_locate_b(LocLanes ln, unsigned sel, 
     __shared__ LocBox sbox;
     const void *__restrict__ const raw = ln.raw[b];
     const LocPar p = ln.par[b];
+    hpe_view vw{};
+    if constexpr (VIEW) vw = ln.view[b];
 
     // 1. the histogram of the valid pixels' bins, and the nearest bin past `skip` pixels
     hist[2 * t] = 0u;
     hist[2 * t + 1] = 0u;
     __syncthreads();
     for (int i = t; i < NPIX; i += LOC_NT) {
-        const LocPix q = loc_pixel<U16>(raw, i, unit, to_cm, p);
+        const LocPix q = loc_pixel<U16, VIEW>(raw, i, unit, to_cm, p, &vw);
         if (q.valid) atomicAdd(&hist[q.k], 1u);
     }
     __syncthreads();
@@ -193,7 +212,7 @@ __global__ __launch_bounds__(LOC_NT) void k_locate_b(LocLanes ln, unsigned sel, 
         const int k_hi = k_near + p.sb;  // sb <= LOC_K (the host clamps)
         LocSums s{0, 0, 0, 0};
         for (int i = t; i < NPIX; i += LOC_NT) {
-            const LocPix q = loc_pixel<U16>(raw, i, unit, to_cm, p);
+            const LocPix q = loc_pixel<U16, VIEW>(raw, i, unit, to_cm, p, &vw);
             if (q.valid && q.k >= k_near && q.k <= k_hi) {
                 s.m += 1;
                 s.r += (unsigned)q.r;
@@ -214,7 +233,7 @@ __global__ __launch_bounds__(LOC_NT) void k_locate_b(LocLanes ln, unsigned sel, 
         // 4. pass 2: the valid pixels inside the box
         s = LocSums{0, 0, 0, 0};
         for (int i = t; i < NPIX; i += LOC_NT) {
-            const LocPix q = loc_pixel<U16>(raw, i, unit, to_cm, p);
+            const LocPix q = loc_pixel<U16, VIEW>(raw, i, unit, to_cm, p, &vw);
             if (q.valid && q.r >= bx.row_lo && q.r <= bx.row_hi && q.c >= bx.col_lo &&
                 q.c <= bx.col_hi && q.Z >= bx.z_lo && q.Z <= bx.z_hi) {
                 s.m += 1;

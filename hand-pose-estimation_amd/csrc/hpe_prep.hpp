@@ -21,6 +21,7 @@
 // stores, workgroup barrier, agent release, arrival counter; the last arriver acquires.
 #pragma once
 #include "hpe_device.hpp"
+#include "../../include/hpe.h"
 
 #define PREP_NT 512
 #define PREP_BANDS 8
@@ -73,6 +74,59 @@ __device__ __forceinline__ unsigned short raw_load(const PrepArgsU16 &a, int i) 
 }
 __device__ __forceinline__ float raw_value(const PrepArgsU16 &a, unsigned short u) {
     return (float)u * a.unit;
+}
+
+// The same through a lane view (hpe_view, include/hpe.h "Lane views"): raw names a camera frame
+// of pitch x height 16-bit pixels, and model pixel i = 320 r + c stands for camera pixel
+// (row0 + step r, col0 + step (FLIP ? 319 - c : c)), or for 0 when that lies outside the camera
+// image.  view_pick is the rule's index arithmetic, shared with the locate kernel: the index is
+// clamped into the image, so the load is unconditional, and a select zeroes what lay outside --
+// no load becomes conditional, and all of prep_band's passes stay in flight at once.  The value
+// that is left then takes the u16 rule, (float)u * unit.
+struct PrepArgsView : PrepArgsU16 {
+    hpe_view view;  // the lane's entry of the device table the begin wrote
+};
+// What a view batch's kernels receive where a u16 batch's receive the address of its depth unit:
+// the unit, and behind it the lanes' views -- one block of device memory the begin writes, so the
+// lane kernels keep one argument list and no graph holds a view.
+struct ViewTab {
+    float unit;
+    int pad[7];
+    hpe_view view[HPE_BATCH_MAX];
+};
+static_assert(sizeof(hpe_view) == 32 && offsetof(ViewTab, view) == 32, "hpe_view is 32 bytes");
+__device__ __forceinline__ int view_pick(const hpe_view &v, int i, bool *inside) {
+    const int r = i / HPE_IMG_W, c = i - HPE_IMG_W * r;
+    // (unsigned adds: an origin near INT_MAX wraps to a negative coordinate, outside like the sum)
+    const int cc = (v.flags & HPE_VIEW_FLIP_COLS) ? HPE_IMG_W - 1 - c : c;
+    const int sr = (int)((unsigned)v.row0 + (unsigned)(v.step * r));
+    const int sc = (int)((unsigned)v.col0 + (unsigned)(v.step * cc));
+    *inside = (unsigned)sr < (unsigned)v.height && (unsigned)sc < (unsigned)v.width;
+    return min(max(sr, 0), v.height - 1) * v.pitch + min(max(sc, 0), v.width - 1);
+}
+// A loaded view pixel: the 16 bits the clamped load brought, and the model pixel they were
+// picked for -- a compile-time expression of the thread index once the passes are unrolled, so
+// it takes no register.  raw_value selects: whether the pick lay inside the camera image is
+// computed again where the value is used, beside the window's own row and column arithmetic,
+// and nothing but the 16 bits is carried across the load's latency.  (The pick at the load is
+// made on an opaque copy of i: merged with the one at the use by the compiler, its row, column
+// and flag would stay live in registers for every load in flight, and the forms spill.)
+struct ViewPix {
+    unsigned short u;
+    int i;
+};
+__device__ __forceinline__ ViewPix raw_load(const PrepArgsView &a, int i) {
+    int j = i;
+    asm("" : "+v"(j));
+    bool inside;
+    // an unsigned 32-bit byte offset on the lane's uniform base: one address register per load
+    const unsigned off = 2u * (unsigned)view_pick(a.view, j, &inside);
+    return ViewPix{*(const HPE_GAS unsigned short *)((const HPE_GAS char *)a.raw + off), i};
+}
+__device__ __forceinline__ float raw_value(const PrepArgsView &a, ViewPix p) {
+    bool inside;
+    (void)view_pick(a.view, p.i, &inside);
+    return (float)(inside ? p.u : (unsigned short)0) * a.unit;
 }
 
 // The distance transform split over two launches (resident raw sequences; prep_dt_split).
@@ -516,12 +570,12 @@ __device__ __forceinline__ void prep_write_descriptor(const PrepArgs &a) {
 // WIN: the bands and the transform's mask both read the frame through the window *wn (the
 // split transform has no windowed form: the batch calls, which alone have windows, never split).
 // A = PrepArgsU16: a frame of 16-bit pixels in a live batch's pinned ring, which has neither a
-// raw row cursor nor a split.
+// raw row cursor nor a split; A = PrepArgsView: the same, a camera frame read through a view.
 template <bool WIN = false, class A = PrepArgs>
 __device__ __forceinline__ void prep_workgroup(const A &a0, int g, unsigned char *lds,
                                                const PrepSplit *ps = nullptr,
                                                const DevWindow *wn = nullptr) {
-    constexpr bool U16 = std::is_same_v<A, PrepArgsU16>;
+    constexpr bool U16 = std::is_base_of_v<PrepArgsU16, A>;
     int *flag = (int *)(lds + PREP_CH * 8 + 8);
     A a = a0;
     if (!U16 && a0.raw_row) a.raw = a0.raw + (size_t)(*a0.raw_row + 1) * a0.raw_stride;

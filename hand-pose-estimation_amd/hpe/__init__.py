@@ -14,7 +14,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _lib, locate, report, window
+from . import _lib, locate, report, view, window
 from ._lib import HpeError, ptr
 
 __all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "scaled_hand",
@@ -43,7 +43,8 @@ def reference_bounds():
     return ub, lb, sd
 
 
-BATCH_INPUTS = {"f32": np.float32, "u16": np.uint16}  # a live batch's frame formats
+# a live batch's frame formats ("view": uint16 camera frames read through lane views)
+BATCH_INPUTS = {"f32": np.float32, "u16": np.uint16, "view": np.uint16}
 
 
 def depth_u16_to_mm(frame_u16, unit_mm=1.0):
@@ -213,8 +214,9 @@ class Context:
             int(to_cm), int(downsample), float(focal), int(frames_per_graph),
             C.c_void_p(d_hist_ptr) if d_hist_ptr else None))
 
-    def _host_frames(self, what, depths, dtype=np.float32):
-        """The lanes' host frames as 240x320 arrays of `dtype` and the array of their addresses
+    def _host_frames(self, what, depths, dtype=np.float32, views=None):
+        """The lanes' host frames as 240x320 arrays of `dtype` (views: lane b's as a
+        (height, pitch) camera frame of views[b]) and the array of their addresses
         (the arrays must outlive the call that takes the addresses).  Under the "free" pacing
         (set_batch_pacing) an entry may be None: a null address, no frame for that lane.
         float32 frames are converted from whatever is given; uint16 frames must be uint16
@@ -235,22 +237,43 @@ class Context:
         elif any(d is not None and np.asarray(d).dtype == np.uint16 for d in ds):
             raise TypeError(f"{what}: a float batch was given uint16 frames (begin the batch "
                             "with input=\"u16\", or convert with depth_u16_to_mm)")
+        if views is not None and len(views) != len(ds):
+            raise ValueError(f"{what}: {len(ds)} lane frames for {len(views)} views")
+        shapes = ([(IMG_H, IMG_W)] * len(ds) if views is None
+                  else [(v.height, v.pitch) for v in views])
+        for d, sh in zip(ds, shapes):
+            if d is not None and np.asarray(d).size != sh[0] * sh[1]:
+                raise ValueError(f"{what}: a frame of {np.asarray(d).size} pixels, the lane's is "
+                                 f"{sh[0]} x {sh[1]}")
         fr = [None if d is None else
-              np.ascontiguousarray(d, dtype=dtype).reshape(IMG_H, IMG_W) for d in ds]
+              np.ascontiguousarray(d, dtype=dtype).reshape(sh) for d, sh in zip(ds, shapes)]
         return fr, (C.c_void_p * len(fr))(*[None if f is None else f.ctypes.data for f in fr])
 
     def batch_pipeline_begin(self, depths, to_cm=True, downsample=True, focal=241.42,
-                             input="f32", unit_mm=1.0):
+                             input="f32", unit_mm=1.0, views=None):
         """Begin a live batch of B = len(depths) lanes: lane b's first raw frame (host, float
         mm 240x320) is copied and prepared.  Ends a live batch in progress.
         input="u16": the batch's frames are uint16 arrays of unit_mm millimetres per count
         (hpe_batch_pipeline_begin_u16), read as such by the device; lane b then equals the
         float batch on depth_u16_to_mm(frame, unit_mm) bit for bit.  The batch keeps its format:
-        track_batch_pipelined follows it."""
+        track_batch_pipelined follows it.
+        input="view": uint16 frames at the camera's own resolution (hpe_batch_pipeline_begin_view),
+        lane b's a (height, pitch) frame of views[b] (hpe.view.View or anything as_view takes);
+        focal is the model image's, fx / step.  Lane b then equals the float batch on
+        depth_u16_to_mm(views[b].reduce(frame), unit_mm) bit for bit."""
         if input not in BATCH_INPUTS:
             raise ValueError(f"batch input {input!r} is not one of {sorted(BATCH_INPUTS)}")
-        fr, arr = self._host_frames("batch_pipeline_begin", depths, BATCH_INPUTS[input])
-        if input == "u16":
+        if (input == "view") != (views is not None):
+            raise ValueError("views go with input=\"view\", and input=\"view\" needs views")
+        vs = None if views is None else [view.as_view(v).check() for v in views]
+        fr, arr = self._host_frames("batch_pipeline_begin", depths, BATCH_INPUTS[input], vs)
+        if input == "view":
+            tab = (_lib.View * len(vs))(*[_lib.View(*[getattr(v, f) for f in view.FIELDS])
+                                          for v in vs])
+            self.check(self.lib.hpe_batch_pipeline_begin_view(
+                self._h, len(fr), arr, tab, float(unit_mm), int(to_cm), int(downsample),
+                float(focal)))
+        elif input == "u16":
             self.check(self.lib.hpe_batch_pipeline_begin_u16(
                 self._h, len(fr), arr, float(unit_mm), int(to_cm), int(downsample), float(focal)))
         else:
@@ -258,10 +281,12 @@ class Context:
                                                          int(downsample), float(focal)))
         self._live_lanes = len(fr)
         self._live_input = input
+        self._live_views = vs
 
     def batch_frame_buffer(self, lane):
         """Lane `lane`'s pinned buffer that the next track_batch_pipelined reads, as a 240x320
-        numpy view (float32 or uint16, the batch's format) over the library's memory
+        numpy view (float32 or uint16, the batch's format; for a view batch the lane's
+        (height, pitch) uint16 camera frame) over the library's memory
         (hpe_batch_frame_buffer: it first waits until the device has read the frame the buffer
         last held).  Write the lane's next frame into it and pass the view back as that lane's
         entry of next_depths: nothing is copied for the lane.  Ask again after every call: the
@@ -270,6 +295,9 @@ class Context:
         self.check(self.lib.hpe_batch_frame_buffer(self._h, int(lane), C.byref(buf), C.byref(n)))
         dt = BATCH_INPUTS[getattr(self, "_live_input", "f32")]
         raw = (C.c_char * n.value).from_address(buf.value)
+        vs = getattr(self, "_live_views", None)
+        if vs is not None and 0 <= int(lane) < len(vs):
+            return np.frombuffer(raw, dtype=dt).reshape(vs[int(lane)].height, vs[int(lane)].pitch)
         return np.frombuffer(raw, dtype=dt).reshape(IMG_H, IMG_W)
 
     def track_batch_pipelined(self, num_p, refine, d_states_ptr, next_depths=None):
@@ -286,9 +314,10 @@ class Context:
             # the lane count of the begin (1 without one: the library then reports the state)
             B, arr = getattr(self, "_live_lanes", 0) or 1, None
         else:
-            fr, arr = self._host_frames("track_batch_pipelined", next_depths, BATCH_INPUTS[inp])
+            fr, arr = self._host_frames("track_batch_pipelined", next_depths, BATCH_INPUTS[inp],
+                                        getattr(self, "_live_views", None))
             B = len(fr)
-        track = (self.lib.hpe_track_batch_pipelined_u16 if inp == "u16"
+        track = (self.lib.hpe_track_batch_pipelined_u16 if inp in ("u16", "view")
                  else self.lib.hpe_track_batch_pipelined)
         self.check(track(self._h, int(num_p), int(refine), B, C.c_void_p(d_states_ptr), arr))
 
@@ -534,6 +563,13 @@ class Context:
         arr = (_lib.Window * max(int(B), 1))()
         self.check(self.lib.hpe_batch_windows_readback(self._h, int(parity), int(B), arr))
         return [window.as_window(arr[b]) for b in range(int(B))]
+
+    def batch_views_readback(self, B):
+        """The lane views the device table holds (hpe_batch_views_readback; synchronises): B
+        hpe.view.View of the last view batch begun."""
+        out = (_lib.View * int(B))()
+        self.check(self.lib.hpe_batch_views_readback(self._h, int(B), out))
+        return [view.as_view(v) for v in out]
 
     def batch_wave_wpp(self, num_p, B) -> int:
         """Waves per particle (1 or 2) of a wave-form batch of B lanes of num_p particles: the

@@ -45,6 +45,16 @@ class Window(C.Structure):
                 ("col_hi", C.c_int32), ("z_lo", C.c_double), ("z_hi", C.c_double)]
 
 
+VIEW_FLIP_COLS = 1  # HPE_VIEW_FLIP_COLS
+
+
+class View(C.Structure):
+    """hpe_view: 32 bytes (hpe/view.py is the rule in numpy)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32),
+                ("row0", C.c_int32), ("col0", C.c_int32), ("step", C.c_int32),
+                ("flags", C.c_uint32), ("pad", C.c_int32)]
+
+
 REPORT_TRACK, REPORT_INIT = 1, 2  # HPE_REPORT_* kinds
 REPORT_F_NAN, REPORT_F_EMPTY, REPORT_F_SUSPECT, REPORT_F_LOST = 1, 2, 4, 8  # HPE_REPORT_F_*
 
@@ -111,6 +121,12 @@ SIGNATURES = {
                                                 C.c_void_p, C.POINTER(C.c_void_p)]),
     "hpe_batch_frame_buffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_size_t)]),
+    "hpe_batch_pipeline_begin_view": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
+                                                C.POINTER(View), C.c_float, C.c_int, C.c_int,
+                                                C.c_double]),
+    "hpe_view_fit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                               C.c_int, C.c_uint32, C.POINTER(View), dp, dp]),
+    "hpe_batch_views_readback": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(View)]),
     "hpe_set_batch_form": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_batch_wave_wpp": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hpe_set_batch_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Window),

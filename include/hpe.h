@@ -438,6 +438,78 @@ int hpe_track_batch_pipelined_u16(hpe_ctx *ctx, int num_p, int refine, int B, do
                                   const uint16_t *const *next_depth);
 int hpe_batch_frame_buffer(hpe_ctx *ctx, int lane, void **buf_out, size_t *bytes_out);
 
+/* Lane views: a live batch on 16-bit frames at the camera's own resolution.  No depth camera
+ * delivers 240x320 frames with the principal point at (160, 120): a view tells the library how
+ * the model image lies in a lane's camera image, and the preparation's load does the crop and
+ * the decimation.  Model pixel (r, c), 0 <= r < 240, 0 <= c < 320, reads camera pixel (sr, sc):
+ *   sr = row0 + step * r
+ *   sc = col0 + step * (flags & HPE_VIEW_FLIP_COLS ? 319 - c : c)
+ * and its 16-bit value is cam[sr * pitch + sc] if 0 <= sr < height && 0 <= sc < width, else 0
+ * ("no depth", like any other hole).  This is a pick (nearest-neighbour decimation), the usual
+ * reduction for depth: averaging would invent surfaces across depth edges.  A hole at the picked
+ * pixel stays a hole, whatever its camera neighbours hold; block rules (min-non-zero, median) are
+ * not offered.  The flip tracks a left hand, or a camera that faces the user, with the right-hand
+ * model.  The picked value follows the u16 batch's rule unchanged: rv = (float)u * unit_mm.
+ *
+ * hpe_batch_pipeline_begin_view is hpe_batch_pipeline_begin_u16 with views[b] (host, B entries,
+ * read before return) the view of lane b -- cameras of one model still differ in principal point,
+ * so the origins differ per lane -- and frames[b] a camera frame of pitch * height pixels.  focal
+ * is the MODEL image's focal length, the camera's fx divided by step; one focal serves the batch,
+ * as in every other batch call: lanes whose fx / step differ are the caller's to reconcile (the
+ * library cannot know, and does not check).  Tracking is hpe_track_batch_pipelined_u16: on a view
+ * batch next_depth[b] is a camera frame of lane b's view.  hpe_batch_frame_buffer returns a
+ * buffer of pitch * height * 2 bytes for the lane and reports that size, so a camera SDK delivers
+ * its native frame there and the track call copies nothing.  Lane b equals, bit for bit after
+ * every frame, hpe_pipeline_begin + hpe_track_pipelined on that stream reduced on the host by the
+ * rule above and converted by the u16 rule (hpe/view.py: View.reduce, then depth_u16_to_mm) --
+ * with windows, lane hands, either pacing, either batch form, reports,
+ * hpe_batch_pipeline_optimise and hpe_batch_pipeline_locate, which reads the lane's camera frame
+ * through its view in all three passes.  The views live in a device table written at the begin,
+ * never a captured argument: two view batches of one shape with different views replay the same
+ * graphs.  The pinned buffers grow at the begin to the largest lane frame (the stream drained,
+ * all lanes or none) and never shrink: a context runs float, u16 and view batches in turn, and
+ * reallocates only when a frame does not fit.
+ *
+ * Coordinates.  Window bounds, report pixels, locate search bounds and results all stay in
+ * MODEL-image coordinates.  Model pixel (r, c) -- fractional for a report's px or a located centre
+ * -- is camera pixel
+ *   row = row0 + step * r,   col = col0 + step * (FLIP ? 319 - c : c)
+ * and a model window [lo, hi] covers camera rows row0 + step * lo .. row0 + step * hi (columns
+ * likewise; under the flip the two column ends swap).
+ *
+ * hpe_view_fit (host only, no context) fits a view of the given step to a camera's intrinsics:
+ *   row0 = lrint(cy - 120.0 * step),  col0 = lrint(cx - 160.0 * step)
+ *   (under the flip col0 = lrint(cx - 159.0 * step): model column 160 reads camera column cx)
+ *   *focal_out = fx / step
+ * residual_px (optional) receives what the rounding left: the principal point's offset from model
+ * pixel (160, 120) in model pixels, {column, row}.  hpe_batch_views_readback synchronises and
+ * copies the table's first B entries (the last view begin's), like hpe_batch_windows_readback.
+ *
+ * Refused with HPE_E_ARG, nothing changed: null views (or out), step outside 1..8, width or
+ * height < 1, pitch < width, pitch or height > HPE_VIEW_DIM_MAX, pitch * height >
+ * HPE_VIEW_PIXELS_MAX (4 MiB per frame; 1920x1080 fits), an unknown flag bit, non-zero pad; for
+ * hpe_view_fit also fx, cx or cy not finite, fx <= 0, or an origin beyond +-1e9 pixels.  A view lying wholly outside its camera
+ * image is legal: it reads empty frames.  hpe_track_batch_pipelined (float) on a view batch is
+ * HPE_E_STATE, as on a u16 batch; hpe_batch_views_readback without a view batch begun on the
+ * context is HPE_E_STATE.  Every other refusal is the u16 begin's. */
+#define HPE_VIEW_FLIP_COLS 1u
+#define HPE_VIEW_DIM_MAX 2048
+#define HPE_VIEW_PIXELS_MAX 2097152
+typedef struct hpe_view {    /* 32 bytes */
+    int32_t width, height;   /* camera image, pixels */
+    int32_t pitch;           /* pixels from one camera row to the next, >= width */
+    int32_t row0, col0;      /* camera pixel of model pixel (0, 0); may be negative */
+    int32_t step;            /* 1..8: camera pixels per model pixel, both axes */
+    uint32_t flags;          /* HPE_VIEW_FLIP_COLS or 0 */
+    int32_t pad;             /* 0 */
+} hpe_view;
+int hpe_batch_pipeline_begin_view(hpe_ctx *ctx, int B, const uint16_t *const *frames,
+                                  const hpe_view *views, float unit_mm, int to_cm,
+                                  int downsample, double focal);
+int hpe_view_fit(int width, int height, int pitch, double fx, double cx, double cy, int step,
+                 uint32_t flags, hpe_view *out, double *focal_out, double residual_px[2]);
+int hpe_batch_views_readback(hpe_ctx *ctx, int B, hpe_view *out);
+
 /* The form of pso_evolve in the three batch calls above (hpe_track_batch_dev,
  * hpe_track_raw_batch_dev, hpe_batch_pipeline_begin / hpe_track_batch_pipelined).
  * HPE_BATCH_FORM_AUTO (default): as described there -- a workgroup per particle, and num_p in the

@@ -53,11 +53,22 @@ work and print the same results_sha1.  Without either option the rendered floats
 (hpe_batch_frame_buffer) and that buffer passed back, so the library copies nothing; the write is
 the tool's, standing in for the camera's.  Every --live line names its "input" and "in_place",
 and "host_bytes_copied_per_call", the bytes the library copies into the ring per call.
+--input view --cam WxH --step K (with --live): the lanes deliver 16-bit frames at the camera's own
+resolution, read through a lane view (hpe_batch_pipeline_begin_view) -- the centred view of that
+step, hpe.view.View(W, H, W, (H - 240 K) // 2, (W - 320 K) // 2, K).  A camera frame is the
+quantised rendered frame enlarged K times (every camera pixel of a model pixel's block holds its
+value) on an empty canvas; the check asserts that the mirror (View.reduce) gives the quantised
+frame back, and runs the lanes alone on its float conversion.  --host-reduce (with --input u16 and
+--cam): the same camera frames, reduced by the tool inside the timed loop with the strided copy an
+application makes without views, cam[r0:r0+240K:K, c0:c0+320K:K], and fed to the plain u16 batch
+(with --in-place that copy goes straight into the lane's pinned buffer): the baseline a view batch
+is measured against.  All three runs track identical trajectories and print the same results_sha1.
 Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
                                              [--window off|fixed|follow] [--hands shared|distinct]
                                              [--pacing lockstep|free] [--drop K]
                                              [--report DEPTH] [--consume sync|report]
-                                             [--input f32|u16] [--unit MM] [--in-place]
+                                             [--input f32|u16|view] [--unit MM] [--in-place]
+                                             [--cam WxH] [--step K] [--host-reduce]
                                              [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
@@ -181,33 +192,44 @@ def make_host_lanes(ctx, B, n):
              for th in synth.trajectory(n, b, revert=0.02)] for b in range(B)]
 
 
-def next_in_place(ctx, host, f):
+def next_in_place(ctx, host, f, reduce=None):
     """Frame f of every lane written into the lane's pinned buffer of the next call: the buffers,
-    to be passed back as the call's next frames."""
+    to be passed back as the call's next frames.  reduce: the strided view of a camera frame that
+    is written instead (--host-reduce: the copy into the buffer is the reduction)."""
     out = []
     for b, fr in enumerate(host):
         buf = ctx.batch_frame_buffer(b)
-        buf[:] = fr[f]
+        buf[:] = fr[f] if reduce is None else reduce(fr[f])
         out.append(buf)
     return out
 
 
-def run_live(ctx, st, host, n, consume=None, begin_kw=None, in_place=False):
+def lanes_kw(begin_kw, B):
+    """The begin's keywords for B lanes: one view for every lane becomes B views."""
+    kw = dict(begin_kw or {})
+    if "views" in kw:
+        kw["views"] = [kw["views"]] * B
+    return kw
+
+
+def run_live(ctx, st, host, n, consume=None, begin_kw=None, in_place=False, reduce=None):
     """n frames of every lane of host through the live batch, a frame per lane and call
-    (begin_kw: the begin's input format; in_place: next_in_place instead of arrays to copy).
+    (begin_kw: the begin's input format; in_place: next_in_place instead of arrays to copy;
+    reduce: --host-reduce, every camera frame reduced by the tool before it is given).
     consume "sync": after every call hpe_sync and a device-to-host copy of the B x 27 states (what
     an application does without reports); "report": after every call each lane's newest report is
     read, one call behind and without any synchronisation (--report), and the last ones at the
     end.  Returns the results consumed: the number of state rows or complete reports read."""
     B, got = len(host), 0
-    ctx.batch_pipeline_begin([fr[0] for fr in host], **(begin_kw or {}))
+    give = (lambda x: x) if reduce is None else (lambda x: np.ascontiguousarray(reduce(x)))
+    ctx.batch_pipeline_begin([give(fr[0]) for fr in host], **lanes_kw(begin_kw, B))
     for f in range(n):
         if f + 1 >= n:
             nxt = None
         elif in_place:
-            nxt = next_in_place(ctx, host, f + 1)
+            nxt = next_in_place(ctx, host, f + 1, reduce)
         else:
-            nxt = [fr[f + 1] for fr in host]
+            nxt = [give(fr[f + 1]) for fr in host]
         ctx.track_batch_pipelined(P, 1, st.data_ptr(), nxt)
         if consume == "sync":
             ctx.check(ctx.lib.hpe_sync(ctx.h))
@@ -276,21 +298,23 @@ def run_live_rebegin(ctx, torch, st, subs, host, n, K):
 
 
 def check_live_against_alone(ctx, torch, x0, host, n=6, alone=None, feed=None, begin_kw=None,
-                             in_place=False):
+                             in_place=False, reduce=None):
     """host: the lanes' float frames, which the lanes alone track; feed: what the batch is given
-    (default: host; the u16 frames that host converts, for a u16 batch)."""
+    (default: host; the u16 frames that host converts, for a u16 batch; camera frames for a view
+    batch, or with reduce, the tool's own reduction, for --host-reduce)."""
     B = len(host)
     feed = host if feed is None else feed
     st = start_states(torch, x0, B)
     hist = []
-    ctx.batch_pipeline_begin([fr[0] for fr in feed], **(begin_kw or {}))
+    give = (lambda x: x) if reduce is None else (lambda x: np.ascontiguousarray(reduce(x)))
+    ctx.batch_pipeline_begin([give(fr[0]) for fr in feed], **lanes_kw(begin_kw, B))
     for f in range(n):
         if f + 1 >= n:
             nxt = None
         elif in_place:
-            nxt = next_in_place(ctx, feed, f + 1)
+            nxt = next_in_place(ctx, feed, f + 1, reduce)
         else:
-            nxt = [fr[f + 1] for fr in feed]
+            nxt = [give(fr[f + 1]) for fr in feed]
         ctx.track_batch_pipelined(P, 1, st.data_ptr(), nxt)
         ctx.check(ctx.lib.hpe_sync(ctx.h))
         hist.append(st.cpu().numpy().copy())
@@ -339,11 +363,21 @@ def main():
     ap.add_argument("--drop", type=int, default=0)
     ap.add_argument("--report", type=int, default=0, metavar="DEPTH")
     ap.add_argument("--consume", choices=("sync", "report"), default=None)
-    ap.add_argument("--input", choices=("f32", "u16"), default="f32")
+    ap.add_argument("--input", choices=("f32", "u16", "view"), default="f32")
+    ap.add_argument("--cam", default=None, metavar="WxH")
+    ap.add_argument("--step", type=int, default=2, metavar="K")
+    ap.add_argument("--host-reduce", action="store_true")
     ap.add_argument("--unit", type=float, default=None, metavar="MM")
     ap.add_argument("--in-place", action="store_true")
     a = ap.parse_args()
-    quantised = a.input == "u16" or a.unit is not None
+    quantised = a.input in ("u16", "view") or a.unit is not None
+    cam_mode = a.input == "view" or a.host_reduce
+    if a.host_reduce and a.input != "u16":
+        ap.error("--host-reduce reduces camera frames for the plain u16 batch: --input u16")
+    if (a.cam is not None) != cam_mode and not (a.input == "view" and a.cam is None):
+        ap.error("--cam goes with --input view or --host-reduce")
+    if cam_mode and a.hands != "shared":
+        ap.error("camera frames need --hands shared")
     if (quantised or a.in_place) and (not a.live or a.drop):
         ap.error("--input, --unit and --in-place need --live without --drop")
     if a.in_place and a.hands != "shared":
@@ -353,6 +387,19 @@ def main():
     unit = np.float32(1.0 if a.unit is None else a.unit)
     # (no keyword to the begin unless asked for: an older build under A/B lacks them)
     begin_kw = {"input": "u16", "unit_mm": float(unit)} if a.input == "u16" else None
+    view = reduce = None
+    if cam_mode:
+        from hpe.view import View
+        W, H = (int(x) for x in (a.cam or "640x480").lower().split("x"))
+        K = a.step
+        if not 1 <= K <= 8 or 320 * K > W or 240 * K > H:
+            ap.error("--cam WxH --step K: the model image enlarged K times must fit the camera's")
+        view = View(W, H, W, (H - 240 * K) // 2, (W - 320 * K) // 2, K).check()
+        if a.input == "view":
+            begin_kw = {"input": "view", "views": view, "unit_mm": float(unit)}
+        else:  # the copy an application makes today
+            def reduce(cam):
+                return cam[view.row0:view.row0 + 240 * K:K, view.col0:view.col0 + 320 * K:K]
     if (a.report or a.consume) and (not a.live or a.drop):
         ap.error("--report and --consume need --live without --drop: reports are the live batch's")
     if a.consume == "report" and not a.report:
@@ -393,8 +440,19 @@ def main():
                     for f in fr] for fr in host]
             host = [[hpe.depth_u16_to_mm(q, unit) for q in fr] for fr in q16]
             feed = q16 if a.input == "u16" else host
+        if cam_mode:  # the camera frames: every model pixel's K x K block holds its value
+            def camera(q):
+                cam = np.zeros((view.height, view.pitch), np.uint16)
+                cam[view.row0:view.row0 + 240 * K, view.col0:view.col0 + 320 * K] = \
+                    np.repeat(np.repeat(q, K, axis=0), K, axis=1)
+                return cam
+            feed = [[camera(q) for q in fr] for fr in q16]
+            for b in range(nb):  # the mirror gives the quantised frames back
+                for f in range(6):
+                    if not np.array_equal(view.reduce(feed[b][f]), q16[b][f]):
+                        raise AssertionError("View.reduce of a camera frame is not the frame it was made of")
         check_live_against_alone(ctx, torch, hpe.X0, host[:nb], alone=alone, feed=feed[:nb],
-                                 begin_kw=begin_kw, in_place=a.in_place)
+                                 begin_kw=begin_kw, in_place=a.in_place, reduce=reduce)
     elif a.raw:
         raws = make_raw_lanes(ctx, torch, max(counts), n)
         check_raw_against_alone(ctx, torch, hpe.X0, raws[:nb], alone=alone)
@@ -462,7 +520,7 @@ def main():
             elif a.live and a.drop:
                 tracked[0] = run_live_rebegin(ctx, torch, st, subs, host[:B], n, a.drop)
             elif a.live:
-                consumed[0] = run_live(ctx, st, feed[:B], n, a.consume, begin_kw, a.in_place)
+                consumed[0] = run_live(ctx, st, feed[:B], n, a.consume, begin_kw, a.in_place, reduce)
             elif a.raw:
                 ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG,
                                     d_hist_ptr=hist.data_ptr())
@@ -511,7 +569,12 @@ def main():
                 line["unit_mm"] = float(unit)
             line["in_place"] = a.in_place
             line["host_bytes_copied_per_call"] = 0 if a.in_place else \
-                B * 240 * 320 * (2 if a.input == "u16" else 4)
+                B * (view.pitch * view.height * 2 if a.input == "view" else
+                     240 * 320 * (2 if a.input == "u16" else 4))
+            if cam_mode:
+                line["cam"] = "%dx%d" % (view.width, view.height)
+                line["step"] = view.step
+                line["host_reduce"] = a.host_reduce
         if a.report:
             line["report_depth"] = a.report
         if a.consume:
