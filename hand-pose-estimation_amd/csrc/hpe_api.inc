@@ -56,6 +56,17 @@ struct Swarm {
     DevBuf<char> arena;
     size_t stride = 0, off[9] = {0};
     int lanes = 0;
+    // hpe_set_batch_seeds: the lanes' own draw tables for (P, G, tab_seeds) -- a copy of normals
+    // and of outl per lane, back to back, the inbox counts [lane][g] and the LaneSeeds entry that
+    // names them -- and what the arenas were last used under: arena_seeds (empty: the context's
+    // seed) and laneK, the K that sizes their inboxes (the largest over arena_seeds; K itself
+    // while no seeds are set).  ensure_lane_seeds keeps all of it.
+    DevBuf<double> lane_normals;
+    DevBuf<int> lane_outl;
+    DevBuf<InboxCounts> lane_kin;
+    DevBuf<LaneSeeds> lane_ls;
+    std::vector<uint64_t> tab_seeds, arena_seeds;
+    int tab_lanes = 0, tab_K = 0, laneK = 0;  // (tab_K: the largest K over tab_seeds)
 };
 
 // RCCL entry points of the library's own subswarm exchange (hpe_subswarm_init), opened at
@@ -141,6 +152,10 @@ struct GraphKey {
                 // kernels; never its depth unit, which device memory holds
     int view;   // ... read through lane views (hpe_batch_pipeline_begin_view): the view kernels;
                 // never a view, which device memory holds too
+    int seeds;  // lane seeds are set (hpe_set_batch_seeds): the SEEDS kernels; never a seed, which
+                // device memory holds
+    int groups; // lane groups are set (hpe_set_batch_groups): one more launch, k_group_pick; never
+                // a group, which device memory holds
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
@@ -149,7 +164,7 @@ struct GraphKey {
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
                next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
                hands == o.hands && pacing == o.pacing && report == o.report && u16 == o.u16 &&
-               view == o.view && to_cm == o.to_cm &&
+               view == o.view && seeds == o.seeds && groups == o.groups && to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -250,6 +265,18 @@ struct hpe_ctx {
     // stream drained) captures nothing.
     DevBuf<DevHand> d_lane_hands;     // [HPE_BATCH_MAX]
     int lane_hands_B = 0;             // the B the lane hands were set for, 0: none
+    // the batch lanes' seeds (hpe_set_batch_seeds): entry b lane b's, empty: the context's seed
+    // for every lane.  The swarm holds the tables built from them (Swarm::lane_*).
+    std::vector<uint64_t> lane_seeds;
+    // the batch lanes' groups (hpe_set_batch_groups): the device table k_group_pick reads (the
+    // graphs hold its address alone and key whether groups are set, GraphKey::groups), its host
+    // copy, and the own-rows table [HPE_BATCH_MAX][27] -- every lane's own {bestp, cost} of the
+    // last grouped frame it tracked (group_rows: one has been enqueued since the groups were set)
+    DevBuf<LaneGroups> d_lane_groups;
+    LaneGroups lane_groups{};
+    int lane_groups_B = 0;            // the B the groups were set for, 0: none
+    DevBuf<double> d_group_own;
+    bool group_rows = false;
     std::vector<Slot> slots;
     int cur = -1;
     // scratch
@@ -635,11 +662,11 @@ static int ensure_lanes(hpe_ctx *c, int lanes) {
                              sizeof(double) * G1 * s.P,                                    // pch
                              sizeof(double) * n,                                           // pb
                              sizeof(double) * n,                                           // v
-                             sizeof(double) * 4 * s.P * s.K * IB_STRIDE,                   // inbox
+                             sizeof(double) * 4 * s.P * s.laneK * IB_STRIDE,               // inbox
                              sizeof(unsigned long long) * G1 * GMIN_SHARDS * GMIN_STRIDE,  // gmin
                              sizeof(Sig) * G1,                                             // sig
                              sizeof(double) * HPE_DOF,                                     // gpos
-                             sizeof(double) * 8 * s.P * s.K};                              // ibtc
+                             sizeof(double) * 8 * s.P * s.laneK};                          // ibtc
     size_t at = 0;
     for (int k = 0; k < 9; ++k) {  // every array on a 256-byte boundary, as hipMalloc gives
         s.off[k] = at;
@@ -654,10 +681,104 @@ static int ensure_lanes(hpe_ctx *c, int lanes) {
     return HPE_OK;
 }
 
+// The inbox counts of one seed's topologies (InboxCounts, P <= KIN_MAX): kin[g] for g = 0..G from
+// make_links' in-degrees.
+static void inbox_counts(int P, int G, const std::vector<int> &indeg, InboxCounts *kin) {
+    std::vector<int> kept(P, 0);  // max in-degree over topologies 1..g-1
+    for (int g = 1; g <= G; ++g) {
+        for (int r = 0; r < P; ++r) {
+            kin[g].k0[r] = (uint8_t)kept[r];
+            kin[g].k1[r] = (uint8_t)indeg[(size_t)g * P + r];
+        }
+        for (int r = 0; r < P; ++r) kept[r] = std::max(kept[r], indeg[(size_t)g * P + r]);
+    }
+}
+
+// The lanes' own draw tables (hpe_set_batch_seeds) of the swarm as it stands, for c->lane_seeds,
+// and the arenas' K.  make_links and make_normals run once per distinct seed.  A seed set whose
+// largest K exceeds IB_KMAX is refused before anything changes.  The tables are grown, never
+// shrunk (the epoch bumped: the graphs hold their addresses), and rewritten in place once the
+// stream has drained when only the seeds change -- the graphs of that shape replay on the new
+// tables and nothing is captured.  Whenever the seeds the arenas were last used under change
+// (lane seeds set, changed or cleared), the arenas are emptied again: an inbox slot a new
+// topology never fills could still hold the old one's push of the same generation, whose tag
+// matches (the wave form and swarms above KIN_MAX read all K slots by tag).  A changed K drops
+// the arenas instead: ensure_lanes builds them at the new size.
+static int ensure_lane_seeds(hpe_ctx *c) {
+    Swarm &s = c->sw;
+    const std::vector<uint64_t> &want = c->lane_seeds;
+    const int B = (int)want.size(), P = s.P, G = s.G;
+    if (want == s.arena_seeds && (B || s.laneK == s.K)) return HPE_OK;
+    int K = s.K;
+    if (B && want != s.tab_seeds) {
+        const size_t n = (size_t)P * HPE_DOF, G1 = (size_t)G + 1, no = G1 * P * 6;
+        std::vector<double> nrm(n * B);
+        std::vector<int> outl(no * B), lk(B, 0);
+        std::vector<InboxCounts> kin(G1 * B, InboxCounts{});
+        LaneSeeds ls{};
+        for (int b = 0; b < B; ++b) {
+            ls.seed[b] = want[b];
+            int same = 0;
+            while (want[same] != want[b]) ++same;
+            if (same < b) {  // an earlier lane's seed: its tables again
+                std::copy_n(nrm.begin() + n * same, n, nrm.begin() + n * b);
+                std::copy_n(outl.begin() + no * same, no, outl.begin() + no * b);
+                std::copy_n(kin.begin() + G1 * same, G1, kin.begin() + G1 * b);
+                lk[b] = lk[same];
+                continue;
+            }
+            std::vector<int> o, indeg;
+            lk[b] = hpe::make_links(want[b], P, G, o, &indeg);
+            if (lk[b] > IB_KMAX)
+                return fail(c, HPE_E_ARG, "lane %d: informant in-degree %d > %d", b, lk[b], IB_KMAX);
+            std::copy(o.begin(), o.end(), outl.begin() + no * b);
+            if (P <= KIN_MAX) inbox_counts(P, G, indeg, kin.data() + G1 * b);
+            hpe::make_normals(want[b], P, nrm.data() + n * b);
+        }
+        K = *std::max_element(lk.begin(), lk.end());
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight read the tables
+        if (B > s.tab_lanes) {
+            ++c->epoch;
+            s.tab_lanes = 0;
+            s.tab_seeds.clear();
+            HIPCHK(c, s.lane_normals.alloc(n * B));
+            HIPCHK(c, s.lane_outl.alloc(no * B));
+            HIPCHK(c, s.lane_kin.alloc(G1 * B));
+            if (!s.lane_ls) HIPCHK(c, s.lane_ls.alloc(1));
+            s.tab_lanes = B;
+        }
+        s.tab_seeds.clear();  // (a copy that fails part way leaves tables of no seed set)
+        ls.kin = s.lane_kin;
+        HIPCHK(c, hipMemcpy(s.lane_normals, nrm.data(), sizeof(double) * nrm.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(s.lane_outl, outl.data(), sizeof(int) * outl.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(s.lane_kin, kin.data(), sizeof(InboxCounts) * kin.size(), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(s.lane_ls, &ls, sizeof(ls), hipMemcpyHostToDevice));
+        s.tab_seeds = want;
+        s.tab_K = K;
+    } else if (B) {
+        K = s.tab_K;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (K != s.laneK) {  // other inboxes: ensure_lanes builds the arenas again
+        s.laneK = K;
+        s.arena.reset();
+        s.lanes = 0;
+    } else if (s.lanes) {
+        HIPCHK(c, hipMemset(s.arena, 0xFF, s.stride * s.lanes));
+    }
+    s.arena_seeds = want;
+    return HPE_OK;
+}
+
 // Swarm buffers + draw tables for (P, G, seed); rebuilt only when one changes.  lanes > 0
-// (hpe_track_batch_dev): also that many lane arenas.
+// (hpe_track_batch_dev): also that many lane arenas, and the lanes' own draw tables when lane
+// seeds are set.
 static int ensure_swarm(hpe_ctx *c, int P, int G, int lanes = 0) {
-    if (c->sw.P == P && c->sw.G == G && c->sw.seed == c->seed) return ensure_lanes(c, lanes);
+    if (c->sw.P == P && c->sw.G == G && c->sw.seed == c->seed) {
+        if (lanes)
+            if (int rc = ensure_lane_seeds(c)) return rc;
+        return ensure_lanes(c, lanes);
+    }
     ++c->epoch;
     c->sw = Swarm{};
     Swarm s;  // built here and moved in whole: a failure leaves the context's swarm empty
@@ -668,14 +789,7 @@ static int ensure_swarm(hpe_ctx *c, int P, int G, int lanes = 0) {
     s.kin.clear();
     if (P <= KIN_MAX) {  // valid inbox slots per receiver and generation (InboxCounts)
         s.kin.assign((size_t)G + 1, InboxCounts{});
-        std::vector<int> kept(P, 0);  // max in-degree over topologies 1..g-1
-        for (int g = 1; g <= G; ++g) {
-            for (int r = 0; r < P; ++r) {
-                s.kin[g].k0[r] = (uint8_t)kept[r];
-                s.kin[g].k1[r] = (uint8_t)indeg[(size_t)g * P + r];
-            }
-            for (int r = 0; r < P; ++r) kept[r] = std::max(kept[r], indeg[(size_t)g * P + r]);
-        }
+        inbox_counts(P, G, indeg, s.kin.data());
     }
     const size_t n = (size_t)P * HPE_DOF;
     HIPCHK(c, s.xh.alloc((size_t)(G + 1) * n));
@@ -704,10 +818,12 @@ static int ensure_swarm(hpe_ctx *c, int P, int G, int lanes = 0) {
     HIPCHK(c, hipMemcpy(s.outl, outl.data(), sizeof(int) * outl.size(), hipMemcpyHostToDevice));
     s.P = P;
     s.G = G;
-    s.K = K;
+    s.K = s.laneK = K;
     s.seed = c->seed;
     c->sw = std::move(s);
     c->bounds_dirty = true;
+    if (lanes)
+        if (int rc = ensure_lane_seeds(c)) return rc;
     return ensure_lanes(c, lanes);
 }
 
@@ -738,10 +854,17 @@ static DevSwarm dev_swarm(hpe_ctx *c) {
 }
 
 // Lane 0 of the batch arenas (the kernels add blockIdx.y * stride); the tables every lane
-// shares come from the swarm.  No trace (hpe_pso_trace is not updated), no exchange.
+// shares come from the swarm -- with lane seeds set, lane 0's of the lanes' own tables (the SEEDS
+// kernels add their lane's offset, and read d.seed from the LaneSeeds entry).  K is the arenas'.
+// No trace (hpe_pso_trace is not updated), no exchange.
 static DevSwarm batch_swarm(hpe_ctx *c) {
     Swarm &s = c->sw;
     DevSwarm d = dev_swarm(c);
+    d.K = s.laneK;
+    if (!c->lane_seeds.empty()) {
+        d.normals = s.lane_normals;
+        d.outl = s.lane_outl;
+    }
     d.xh = (double *)(s.arena + s.off[0]);
     d.pch = (double *)(s.arena + s.off[1]);
     d.pb = (double *)(s.arena + s.off[2]);
@@ -2210,7 +2333,10 @@ int hpe_track_sequence_dev(hpe_ctx *c, int P, int refine, double *d_state, int f
 // The kernel forms of one frame of B lanes: the axes of hpe_kernels.hip's lane templates, derived
 // once from the frame's targets and the context.
 struct LaneForm {
-    bool hands;   // the HANDS forms: lane hands are set (the batch graphs' key field), or paced
+    bool hands;   // the HANDS forms: lane hands are set (the batch graphs' key field), or paced,
+                  // or seeded
+    bool seeds;   // hpe_set_batch_seeds: the SEEDS forms of the kernels that draw, in the HANDS
+                  // shape alone (as the paced ones)
     LaneSrc src;  // the refine launch prepares every lane's next frame from there (NONE: no next)
     bool win;     // ... through the lanes' windows
     bool paced;   // HPE_PACING_FREE: the idle-aware forms, in the HANDS shape alone (the table
@@ -2224,7 +2350,8 @@ static int lane_hands_set(const hpe_ctx *c) { return c->lane_hands_B ? 1 : 0; }
 static LaneForm lane_form(hpe_ctx *c, int P, int B, const DevSwarm &d, const LaneFrameIo &io) {
     LaneForm f{};
     f.paced = io.act != nullptr;
-    f.hands = f.paced || lane_hands_set(c);
+    f.seeds = !c->lane_seeds.empty();
+    f.hands = f.paced || f.seeds || lane_hands_set(c);
     f.src = !io.prep ? LANE_SRC_NONE : io.unit ? (io.view ? LANE_SRC_VIEW : LANE_SRC_U16) : io.raw ? LANE_SRC_RAW : LANE_SRC_RING;
     f.win = io.prep && io.win;
     f.live = io.seq != nullptr;
@@ -2298,50 +2425,54 @@ static LaneWindowFn lane_window_kernel(const LaneForm &f) {
 
 // init: both forms have one argument list
 typedef void (*LaneInitFn)(DevSwarm, size_t, const double *, const DevObs *, const DevHand *,
-                           const int *);
-template <bool HANDS, bool PACED>
+                           const int *, const LaneSeeds *);
+template <bool HANDS, bool PACED, bool SEEDS = false>
 static LaneInitFn lane_init_kernel_t(const LaneForm &f) {
     if (f.wpp == 2)
-        return f.coop ? k_pso_init_wb<2, true, HANDS, PACED> : k_pso_init_wb<2, false, HANDS, PACED>;
+        return f.coop ? k_pso_init_wb<2, true, HANDS, PACED, SEEDS> : k_pso_init_wb<2, false, HANDS, PACED, SEEDS>;
     if (f.wpp)
-        return f.coop ? k_pso_init_wb<1, true, HANDS, PACED> : k_pso_init_wb<1, false, HANDS, PACED>;
+        return f.coop ? k_pso_init_wb<1, true, HANDS, PACED, SEEDS> : k_pso_init_wb<1, false, HANDS, PACED, SEEDS>;
     if constexpr (!PACED)
-        if (f.filt) return k_pso_init_b<true, HANDS, false>;
-    return k_pso_init_b<false, HANDS, PACED>;
+        if (f.filt) return k_pso_init_b<true, HANDS, false, SEEDS>;
+    return k_pso_init_b<false, HANDS, PACED, SEEDS>;
 }
 static LaneInitFn lane_init_kernel(const LaneForm &f) {
+    if (f.seeds) return f.paced ? lane_init_kernel_t<true, true, true>(f) : lane_init_kernel_t<true, false, true>(f);
     return f.paced ? lane_init_kernel_t<true, true>(f)
                    : f.hands ? lane_init_kernel_t<true, false>(f) : lane_init_kernel_t<false, false>(f);
 }
 
 typedef void (*LaneGenFn)(DevSwarm, size_t, const DevObs *, const DevHand *, int, double, double,
-                          double, InboxCounts, const int *);
-template <bool HANDS, bool PACED>
+                          double, InboxCounts, const int *, const LaneSeeds *);
+template <bool HANDS, bool PACED, bool SEEDS = false>
 static LaneGenFn lane_gen_kernel_t(const LaneForm &f) {
     if constexpr (!PACED)
         if (f.filt)
-            return f.r16 ? k_pso_gen_b<true, true, HANDS, false> : k_pso_gen_b<false, true, HANDS, false>;
-    return f.r16 ? k_pso_gen_b<true, false, HANDS, PACED> : k_pso_gen_b<false, false, HANDS, PACED>;
+            return f.r16 ? k_pso_gen_b<true, true, HANDS, false, SEEDS> : k_pso_gen_b<false, true, HANDS, false, SEEDS>;
+    return f.r16 ? k_pso_gen_b<true, false, HANDS, PACED, SEEDS> : k_pso_gen_b<false, false, HANDS, PACED, SEEDS>;
 }
 static LaneGenFn lane_gen_kernel(const LaneForm &f) {
+    if (f.seeds) return f.paced ? lane_gen_kernel_t<true, true, true>(f) : lane_gen_kernel_t<true, false, true>(f);
     return f.paced ? lane_gen_kernel_t<true, true>(f)
                    : f.hands ? lane_gen_kernel_t<true, false>(f) : lane_gen_kernel_t<false, false>(f);
 }
 
 // the wave form's generation (no exchange, no inbox counts)
 typedef void (*LaneWaveGenFn)(DevSwarm, size_t, const DevObs *, const DevHand *, int, double, double,
-                              double, const int *);
-template <int WPP, bool HANDS, bool PACED>
+                              double, const int *, const LaneSeeds *);
+template <int WPP, bool HANDS, bool PACED, bool SEEDS>
 static LaneWaveGenFn lane_wave_gen_kernel_t(bool coop, bool r16) {
-    return coop ? (r16 ? k_pso_gen_wb<true, WPP, true, HANDS, PACED> : k_pso_gen_wb<false, WPP, true, HANDS, PACED>)
-                : (r16 ? k_pso_gen_wb<true, WPP, false, HANDS, PACED> : k_pso_gen_wb<false, WPP, false, HANDS, PACED>);
+    return coop ? (r16 ? k_pso_gen_wb<true, WPP, true, HANDS, PACED, SEEDS> : k_pso_gen_wb<false, WPP, true, HANDS, PACED, SEEDS>)
+                : (r16 ? k_pso_gen_wb<true, WPP, false, HANDS, PACED, SEEDS> : k_pso_gen_wb<false, WPP, false, HANDS, PACED, SEEDS>);
 }
-template <bool HANDS, bool PACED>
+template <bool HANDS, bool PACED, bool SEEDS = false>
 static LaneWaveGenFn lane_wave_gen_kernel_t(const LaneForm &f) {
-    return f.wpp == 2 ? lane_wave_gen_kernel_t<2, HANDS, PACED>(f.coop, f.r16)
-                      : lane_wave_gen_kernel_t<1, HANDS, PACED>(f.coop, f.r16);
+    return f.wpp == 2 ? lane_wave_gen_kernel_t<2, HANDS, PACED, SEEDS>(f.coop, f.r16)
+                      : lane_wave_gen_kernel_t<1, HANDS, PACED, SEEDS>(f.coop, f.r16);
 }
 static LaneWaveGenFn lane_wave_gen_kernel(const LaneForm &f) {
+    if (f.seeds)
+        return f.paced ? lane_wave_gen_kernel_t<true, true, true>(f) : lane_wave_gen_kernel_t<true, false, true>(f);
     return f.paced ? lane_wave_gen_kernel_t<true, true>(f)
                    : f.hands ? lane_wave_gen_kernel_t<true, false>(f)
                              : lane_wave_gen_kernel_t<false, false>(f);
@@ -2393,22 +2524,30 @@ static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_stat
     const double W1 = 1. / (2 * std::log(2.0)), C1 = 0.5 + std::log(2.0), C2 = C1;  // PSO.cpp:772-774
     const int per_wg = f.wpp ? PW_WPB / f.wpp : 1;  // one or two waves per particle, or a workgroup
     const dim3 grid((P + per_wg - 1) / per_wg, B), block(f.wpp ? PW_NT : HPE_NT);
+    // lane seeds: the lanes' table entry (null: every lane draws under the context's seed)
+    const LaneSeeds *ls = f.seeds ? c->sw.lane_ls.get() : nullptr;
     launch(c, HPE_PROF_PSO_INIT, lane_init_kernel(f), grid, block, 0, d, stride,
-           (const double *)d_states, obs, hand, act);
+           (const double *)d_states, obs, hand, act, ls);
     if (f.wpp) {
         const LaneWaveGenFn kw = lane_wave_gen_kernel(f);
         for (int g = 1; g <= d.G; ++g)
-            launch(c, HPE_PROF_PSO_GEN, kw, grid, block, 0, d, stride, obs, hand, g, W1, C1, C2, act);
+            launch(c, HPE_PROF_PSO_GEN, kw, grid, block, 0, d, stride, obs, hand, g, W1, C1, C2, act, ls);
     } else {
-        static const InboxCounts all_k{};  // P > KIN_MAX: the kernel reads K slots
+        // P > KIN_MAX: the kernel reads K slots; seeded: its lane's counts from the device table
+        static const InboxCounts all_k{};
         const LaneGenFn kg = lane_gen_kernel(f);
         for (int g = 1; g <= d.G; ++g)
             launch(c, HPE_PROF_PSO_GEN, kg, grid, block, 0, d, stride, obs, hand, g, W1, C1, C2,
-                   c->sw.kin.empty() ? all_k : c->sw.kin[g], act);
+                   c->sw.kin.empty() || f.seeds ? all_k : c->sw.kin[g], act, ls);
     }
     launch(c, HPE_PROF_PSO_FINAL, lane_final_kernel(f), dim3(1, B), dim3(HPE_NT), 0, d, stride, d_states,
            io.obs, hand, (DevObs *)nullptr, f.wpp ? 0 : 1, io.seq, io.done_host, io.hist,
            (const int *)nullptr, io.slots, io.cur, act);
+    // lane groups: every group's rows become its best own row, ahead of the reports and of the
+    // next frame's windows and refine, which read the rows
+    if (c->lane_groups_B)
+        hipLaunchKernelGGL(k_group_pick, dim3(B), dim3(64), 0, c->stream, d_states, c->d_group_own.get(),
+                           io.hist, (const int *)io.cur, (const LaneGroups *)c->d_lane_groups, act);
     HIPCHK(c, hipGetLastError());
     return HPE_OK;
 }
@@ -2578,6 +2717,114 @@ static int check_hand_lanes(hpe_ctx *c, int B) {
     return HPE_OK;
 }
 
+// ---------------------------------------------------------------- lane seeds and groups
+int hpe_set_batch_seeds(hpe_ctx *c, int B, const uint64_t *seeds) {
+    if (!c) return HPE_E_ARG;
+    if (seeds && (B < 1 || B > HPE_BATCH_MAX))
+        return fail(c, HPE_E_ARG, "seeds for %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (c->live.cur >= 0)
+        return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the seeds it began with "
+                    "(end it first)");
+    // the tables follow at the next batch call, for its (P, G): ensure_lane_seeds.  No epoch bump:
+    // the graphs hold the tables' addresses and key whether seeds are set (GraphKey::seeds)
+    if (seeds) c->lane_seeds.assign(seeds, seeds + B);
+    else c->lane_seeds.clear();
+    return HPE_OK;
+}
+
+int hpe_set_batch_groups(hpe_ctx *c, int B, int n_groups, const int32_t *sizes) {
+    if (!c) return HPE_E_ARG;
+    const bool on = n_groups != 0 && sizes;
+    LaneGroups g{};
+    if (on) {
+        if (B < 1 || B > HPE_BATCH_MAX)
+            return fail(c, HPE_E_ARG, "groups over %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+        if (n_groups < 0 || n_groups > B)
+            return fail(c, HPE_E_ARG, "%d groups over %d lanes", n_groups, B);
+        int at = 0;
+        for (int k = 0; k < n_groups; ++k) {
+            if (sizes[k] < 1 || sizes[k] > B - at)
+                return fail(c, HPE_E_ARG, "group %d: size %d is not positive, or the sizes pass %d "
+                            "lanes", k, (int)sizes[k], B);
+            for (int m = 0; m < sizes[k]; ++m) g.first[at + m] = at, g.size[at + m] = sizes[k];
+            at += sizes[k];
+        }
+        if (at != B) return fail(c, HPE_E_ARG, "the group sizes sum to %d, not to %d lanes", at, B);
+    }
+    if (c->live.cur >= 0)
+        return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps the groups it began "
+                    "with (end it first)");
+    if (on) {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (!c->d_group_own) {  // once, never reallocated: the graphs hold both addresses
+            DevBuf<LaneGroups> tab;
+            HIPCHK(c, tab.alloc(1));
+            HIPCHK(c, c->d_group_own.alloc((size_t)HPE_BATCH_MAX * HPE_STATE_N));
+            c->d_lane_groups = std::move(tab);
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // launches in flight read the table
+        HIPCHK(c, hipMemcpy(c->d_lane_groups, &g, sizeof(g), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemset(c->d_group_own, 0, sizeof(double) * HPE_BATCH_MAX * HPE_STATE_N));
+    }
+    c->lane_groups = g;
+    c->lane_groups_B = on ? B : 0;  // no epoch bump: GraphKey::groups
+    c->group_rows = false;
+    return HPE_OK;
+}
+
+// A batch call's or begin's lane count against the lane seeds' and groups' (none set: any).
+static int check_seed_group_lanes(hpe_ctx *c, int B) {
+    if (!c->lane_seeds.empty() && B != (int)c->lane_seeds.size())
+        return fail(c, HPE_E_ARG, "%d lanes, the seeds were set for %d (hpe_set_batch_seeds)", B,
+                    (int)c->lane_seeds.size());
+    if (c->lane_groups_B && B != c->lane_groups_B)
+        return fail(c, HPE_E_ARG, "%d lanes, the groups were set for %d (hpe_set_batch_groups)", B,
+                    c->lane_groups_B);
+    return HPE_OK;
+}
+
+// Free pacing: a group advances as one -- the entries of a group's lanes (bit b of `given`) are
+// all null or all non-null.
+static int check_group_frames(hpe_ctx *c, int B, uint32_t given) {
+    for (int b = 0; c->lane_groups_B && b < B; ++b)
+        if ((given >> b & 1) != (given >> c->lane_groups.first[b] & 1))
+            return fail(c, HPE_E_ARG, "lane %d: a frame for some lanes of its group only (a group "
+                        "advances as one)", b);
+    return HPE_OK;
+}
+
+int hpe_batch_group_pick(hpe_ctx *c, int B, double *d_states) {
+    if (!c) return HPE_E_ARG;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!d_states) return fail(c, HPE_E_ARG, "null device states");
+    if (!c->lane_groups_B) return fail(c, HPE_E_STATE, "no lane groups are set (hpe_set_batch_groups)");
+    if (int rc = check_seed_group_lanes(c, B)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_group_pick, dim3(B), dim3(64), 0, c->stream, d_states, (double *)nullptr,
+                       (double *)nullptr, (const int *)nullptr, (const LaneGroups *)c->d_lane_groups,
+                       (const int *)nullptr);
+    HIPCHK(c, hipGetLastError());
+    return HPE_OK;
+}
+
+int hpe_batch_group_rows(hpe_ctx *c, int B, double *rows_out) {
+    if (!c) return HPE_E_ARG;
+    if (B < 1 || B > HPE_BATCH_MAX)
+        return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+    if (!rows_out) return fail(c, HPE_E_ARG, "null rows");
+    if (!c->lane_groups_B || !c->group_rows)
+        return fail(c, HPE_E_STATE, "no grouped frame has been tracked (hpe_set_batch_groups)");
+    if (B != c->lane_groups_B)
+        return fail(c, HPE_E_ARG, "%d lanes, the groups were set for %d (hpe_set_batch_groups)", B,
+                    c->lane_groups_B);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(rows_out, c->d_group_own, sizeof(double) * (size_t)B * HPE_STATE_N,
+                        hipMemcpyDeviceToHost));
+    return HPE_OK;
+}
+
 int hpe_batch_windows_readback(hpe_ctx *c, int parity, int B, hpe_window *out) {
     if (!c) return HPE_E_ARG;
     if (parity < 0 || parity > 1) return fail(c, HPE_E_ARG, "buffer parity %d", parity);
@@ -2609,7 +2856,9 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
                         const int32_t *first_slots, int n, int frames_per_graph, double *d_hist) {
     if (!c) return HPE_E_ARG;
     int rc = check_chunked_call(c, P, frames_per_graph);
-    if (rc || (rc = check_batch_call(c, P, B)) || (rc = check_hand_lanes(c, B))) return rc;
+    if (rc || (rc = check_batch_call(c, P, B)) || (rc = check_hand_lanes(c, B)) ||
+        (rc = check_seed_group_lanes(c, B)))
+        return rc;
     if (!d_states || !first_slots) return fail(c, HPE_E_ARG, "null device states or first slots");
     if (n < 1) return fail(c, HPE_E_ARG, "n = %d frames", n);
     for (int b = 0; b < B; ++b) {
@@ -2652,6 +2901,8 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
         key.B = B;
         key.wave = batch_wave_wpp(c, P, B);
         key.hands = lane_hands_set(c);
+        key.seeds = !c->lane_seeds.empty();
+        key.groups = c->lane_groups_B ? 1 : 0;
         for (int i = 0; i < k; ++i)
             if (c->slots[first_slots[0] + f0 + i].n_max > HPE_NT / 2) key.filt |= 1u << i;
         // k frames of B lanes, one after the other on the tracking stream: each lane on its own
@@ -2666,6 +2917,7 @@ int hpe_track_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_states,
                  return erc;
              })))
             return rc;
+        if (c->lane_groups_B) c->group_rows = true;
     }
     return mark_seq_done(c);
 }
@@ -2977,7 +3229,9 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
     if (!downsample)
         return fail(c, HPE_E_ARG, "downsample = 0: full clouds hold up to %d points, a batch takes "
                     "the single-workgroup refine (<= %d)", HPE_IMG_H * HPE_IMG_W, RF_STAGE_MAX);
-    if ((rc = check_window_lanes(c, B)) || (rc = check_hand_lanes(c, B))) return rc;
+    if ((rc = check_window_lanes(c, B)) || (rc = check_hand_lanes(c, B)) ||
+        (rc = check_seed_group_lanes(c, B)))
+        return rc;
     HIPCHK(c, hipSetDevice(c->device));
     to_cm = to_cm ? 1 : 0;
     if ((rc = ensure_raw_batch(c, B, to_cm, focal))) return rc;
@@ -3007,6 +3261,8 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
         key.wave = batch_wave_wpp(c, P, B);
         key.win = c->win.mode;
         key.hands = lane_hands_set(c);
+        key.seeds = !c->lane_seeds.empty();
+        key.groups = c->lane_groups_B ? 1 : 0;
         key.to_cm = to_cm;
         key.downsample = 1;
         key.focal = focal;
@@ -3015,6 +3271,7 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
                                                 d_hist);
              })))
             return rc;
+        if (c->lane_groups_B) c->group_rows = true;
     }
     return mark_seq_done(c);
 }
@@ -3313,6 +3570,9 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
                         "(a live batch reads its pinned buffers in place)");
     if (int wrc = check_window_lanes(c, B)) return wrc;
     if (int hrc = check_hand_lanes(c, B)) return hrc;
+    if (int src = check_seed_group_lanes(c, B)) return src;
+    if (paced)
+        if (int grc = check_group_frames(c, B, given)) return grc;
     if (u16 && !(std::isfinite(unit_mm) && unit_mm > 0))
         return fail(c, HPE_E_ARG, "depth unit %g mm is not finite and positive", (double)unit_mm);
     HIPCHK(c, hipSetDevice(c->device));
@@ -3490,6 +3750,8 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
     const int cur = lv.cur, nxt = cur ^ 1;
     const uint32_t all = B < 32 ? (1u << B) - 1 : ~0u;
     const uint32_t given = !next ? 0 : paced ? lane_mask(next_depth_mm, B) : all;
+    if (paced)
+        if (int grc = check_group_frames(c, B, given)) return grc;
     // a lane's own pinned buffer as its next frame (hpe_batch_frame_buffer) was filled in place;
     // a buffer of the other parity holds a current frame: its pointer is from before an earlier call
     for (int b = 0; b < B; ++b)
@@ -3512,6 +3774,8 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
     key.wave = batch_wave_wpp(c, P, B);
     key.win = c->win.mode;  // the begin's: it cannot change while the batch lives
     key.hands = lane_hands_set(c);  // ... nor can the hands
+    key.seeds = !c->lane_seeds.empty();  // ... nor the seeds
+    key.groups = c->lane_groups_B ? 1 : 0;  // ... nor the groups
     key.pacing = lv.pacing;  // ... nor the pacing; FREE: next is "the array is non-null", and
                              // the lanes' masks are never part of the key
     key.cur = cur;
@@ -3545,6 +3809,7 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
                               : HPE_OK;
          })))
         return rc;
+    if (c->lane_groups_B) c->group_rows = true;
     if (lv.report)
         for (int b = 0; b < B; ++b) c->rep.enq[b] += (paced ? lv.pending : all) >> b & 1;
     ++lv.enq;  // this frame's number; lane 0's final workgroup publishes it to h_done

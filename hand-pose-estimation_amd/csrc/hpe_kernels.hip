@@ -1355,11 +1355,13 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
 // the mutable arrays of all lanes are B identical arenas `stride` bytes apart, the argument
 // holds lane 0's pointers, and a lane rebases them with scalar adds on the entry batch's
 // words (no table of per-lane structs to load first).  normals, outl, bounds and the inbox
-// counts are shared: every lane draws under the context's seed.  Lanes never communicate.
+// counts are shared: every lane draws under the context's seed -- unless lane seeds are set
+// (SEEDS below).  Lanes never communicate inside a frame; lane groups exchange rows after one
+// (k_group_pick).
 //
 // One template per role -- k_pso_init_b, k_pso_gen_b, k_pso_init_wb, k_pso_gen_wb (pso_evolve in
 // the workgroup and the wave form), k_pso_final_b, k_refine_lane, k_prepare_lane, k_window_b --
-// and four independent axes, each a template parameter.  Every form of a role has one argument
+// and five independent axes, each a template parameter.  Every form of a role has one argument
 // list; what a form does not read is passed null and never loaded.
 //   SRC (LaneSrc): where the preparation workgroups find the lane's next raw frame.  They ride in
 //     the refine launch, grid (1 + PREP_WG, B): workgroup (0, b) refines, (1.., b) run
@@ -1393,6 +1395,9 @@ __global__ __launch_bounds__(RF_NT) void k_refine(double *__restrict__ x0g, cons
 //     counter or hand-off, and stores nothing -- but for lane 0's final workgroup, which
 //     publishes the call's frame number whether or not lane 0 tracks.
 //   HANDS: hpe_set_batch_hands.  The hand is entry blockIdx.y of the flat table (lane_hand).
+//   SEEDS: hpe_set_batch_seeds, on the four roles that draw (k_pso_init_b, k_pso_gen_b,
+//     k_pso_init_wb, k_pso_gen_wb).  The lane's normals, links, inbox counts and Philox key come
+//     from per-lane device tables (lane_seeded); built in the HANDS shape alone, like PACED.
 // The host names these combinations and no others (hpe_api.inc, the lane_*_kernel selectors):
 // WIN needs a source; PACED is the live batch's, so RING, U16 or VIEW (or NONE, its ending frame), and
 // is built in the HANDS shape alone -- the table holds the context's hand in every entry while
@@ -1422,33 +1427,68 @@ template <bool HANDS>
 __device__ __forceinline__ const DevHand *lane_hand(const DevHand *__restrict__ tab) {
     return HANDS ? tab + blockIdx.y : tab;
 }
+// The lane's seed (hpe_set_batch_seeds).  SEEDS: what every lane shares under the context's seed
+// -- the normals, the link table, the Philox key, and in the workgroup form the inbox counts --
+// is the lane's own: the host lays B copies of normals and outl out back to back (lane 0's in the
+// argument, as the arenas), so a lane rebases them by scalar multiply-adds on P and G, and takes
+// its seed and its counts [lane][g] from the device table `ls`.  sw.K is the largest K over the
+// lanes' seeds: it sizes and addresses the inbox alone -- outl names (receiver, slot) -- so a
+// lane's values do not depend on it.  !SEEDS: the swarm as it came, `ls` never loaded, and the
+// kernel compiles as it did before there were lane seeds.  The SEEDS forms are built in the HANDS
+// shape alone, as the PACED ones are.
+struct LaneSeeds {
+    unsigned long long seed[16];
+    const InboxCounts *kin;  // [lane][g], g = 0..G
+};
+static_assert(HPE_BATCH_MAX == 16, "LaneSeeds holds one seed per lane");
+template <bool SEEDS>
+__device__ __forceinline__ DevSwarm lane_seeded(DevSwarm sw, const LaneSeeds *__restrict__ ls) {
+    if (SEEDS) {
+        sw.normals += (size_t)sw.P * HPE_DOF * blockIdx.y;
+        sw.outl += (size_t)(sw.G + 1) * sw.P * 6 * blockIdx.y;
+        sw.seed = ls->seed[blockIdx.y];
+    }
+    return sw;
+}
 #define HPE_STATE_N (HPE_DOF + 1)  // {x0 -> bestp, cost} of one lane
 #define HPE_EVALS_N 4              // a lane's refine evaluation counter {last, -, total (u64)}
 
 // states: B x 27; obs: B descriptors, lane b's current frame (k_seq_begin_b / k_pso_final_b)
-template <bool FILT, bool HANDS, bool PACED>
+template <bool FILT, bool HANDS, bool PACED, bool SEEDS = false>
 __global__ __launch_bounds__(HPE_NT) void k_pso_init_b(DevSwarm sw, size_t stride,
                                                        const double *__restrict__ states,
                                                        const DevObs *__restrict__ obs,
                                                        const DevHand *__restrict__ Hg,
-                                                       const int *__restrict__ act) {
+                                                       const int *__restrict__ act,
+                                                       const LaneSeeds *__restrict__ ls) {
     static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    static_assert(HANDS || !SEEDS, "the seeded forms index the hand table");
     if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
-    pso_init_body<HPE_NT, FILT>(lane_swarm(sw, stride), states + (size_t)HPE_STATE_N * blockIdx.y,
-                                obs + blockIdx.y, lane_hand<HANDS>(Hg));
+    pso_init_body<HPE_NT, FILT>(lane_swarm(lane_seeded<SEEDS>(sw, ls), stride),
+                                states + (size_t)HPE_STATE_N * blockIdx.y, obs + blockIdx.y,
+                                lane_hand<HANDS>(Hg));
 }
 
-template <bool ROW16, bool FILT, bool HANDS, bool PACED>
+// SEEDS: the inbox counts are the lane's, entry [lane][g] of the device table, not the by-value
+// argument (which the host then leaves zero and the kernel never reads).
+template <bool ROW16, bool FILT, bool HANDS, bool PACED, bool SEEDS = false>
 __global__ __launch_bounds__(HPE_NT) void k_pso_gen_b(DevSwarm sw, size_t stride,
                                                       const DevObs *__restrict__ obs,
                                                       const DevHand *__restrict__ Hg, int g,
                                                       double W1, double C1, double C2,
                                                       InboxCounts kin,
-                                                      const int *__restrict__ act) {
+                                                      const int *__restrict__ act,
+                                                      const LaneSeeds *__restrict__ ls) {
     static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    static_assert(HANDS || !SEEDS, "the seeded forms index the hand table");
     if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
-    pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, lane_hand<HANDS>(Hg),
-                                             g, W1, C1, C2, kin);
+    if constexpr (SEEDS)
+        pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(lane_seeded<true>(sw, ls), stride),
+                                                 obs + blockIdx.y, lane_hand<HANDS>(Hg), g, W1, C1, C2,
+                                                 ls->kin[(size_t)(sw.G + 1) * blockIdx.y + g]);
+    else
+        pso_gen_body<HPE_NT, false, ROW16, FILT>(lane_swarm(sw, stride), obs + blockIdx.y, lane_hand<HANDS>(Hg),
+                                                 g, W1, C1, C2, kin);
 }
 
 // k_pso_final's TAIL form on the lane's cursor cur[2 b] = {slot, row}: the row indexes hist
@@ -1703,32 +1743,36 @@ __device__ __forceinline__ DevSwarm lane_swarm_w(DevSwarm sw, size_t stride) {
     return sw;
 }
 
-template <int WPP, bool COOP, bool HANDS, bool PACED>
+template <int WPP, bool COOP, bool HANDS, bool PACED, bool SEEDS = false>
 __global__ __launch_bounds__(PW_NT) void k_pso_init_wb(DevSwarm sw, size_t stride,
                                                        const double *__restrict__ states,
                                                        const DevObs *__restrict__ obs,
                                                        const DevHand *__restrict__ hands,
-                                                       const int *__restrict__ act) {
+                                                       const int *__restrict__ act,
+                                                       const LaneSeeds *__restrict__ ls) {
     static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    static_assert(HANDS || !SEEDS, "the seeded forms index the hand table");
     if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
     const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
-    sw = lane_swarm_w(sw, stride);
+    sw = lane_swarm_w(lane_seeded<SEEDS>(sw, ls), stride);
     const double *__restrict__ const x0 = states + (size_t)HPE_STATE_N * blockIdx.y;
     const DevObs *__restrict__ const og = obs + blockIdx.y;
 #include "hpe_wave_init_body.inc"
 }
 
-template <bool ROW16, int WPP, bool COOP, bool HANDS, bool PACED>
+template <bool ROW16, int WPP, bool COOP, bool HANDS, bool PACED, bool SEEDS = false>
 __global__ __launch_bounds__(PW_NT, WPP == 2 ? 2 : 4) void k_pso_gen_wb(DevSwarm sw, size_t stride,
                                                       const DevObs *__restrict__ obs,
                                                       const DevHand *__restrict__ hands, int g,
                                                       double W1, double C1, double C2,
-                                                      const int *__restrict__ act) {
+                                                      const int *__restrict__ act,
+                                                      const LaneSeeds *__restrict__ ls) {
     static_assert(HANDS || !PACED, "the idle-aware forms index the hand table");
+    static_assert(HANDS || !SEEDS, "the seeded forms index the hand table");
     if (PACED && !(act[blockIdx.y] & HPE_ACT_TRACK)) return;
     const DevHand *__restrict__ const Hg = lane_hand<HANDS>(hands);
     constexpr bool XCH = false;  // no exchange inside a batch
-    sw = lane_swarm_w(sw, stride);
+    sw = lane_swarm_w(lane_seeded<SEEDS>(sw, ls), stride);
     const DevObs *__restrict__ const og = obs + blockIdx.y;
 #include "hpe_wave_gen_body.inc"
 }
@@ -1743,6 +1787,51 @@ static_assert(HPE_BATCH_MAX == 16, "LaneAct holds one word per lane");
 __global__ void k_lane_act(LaneAct a, int *__restrict__ act) {
     const int t = threadIdx.x;
     if (t < HPE_BATCH_MAX) act[t] = a.word[t];
+}
+
+// ------------------------------------------------------------------ lane groups
+// hpe_set_batch_groups: runs of consecutive lanes that track one stream as independent subswarms
+// and carry the best of their results to the next frame -- the subswarm exchange's per-frame pick
+// (k_pick_best, hpe/dist.py pick_best) between lanes, with no communicator.  One wave per lane
+// after the frame's final launch and ahead of k_report_b (the kernel boundary is the hand-off: no
+// counter, no spin); the wave of a group's first lane works, the others return at entry.  It
+//   copies each of the group's rows of `states` -- what k_pso_final_b just wrote, the lane's own
+//     {bestp, cost} -- into the own-rows table `own` (null: hpe_batch_group_pick, which picks
+//     among arbitrary rows and leaves the table alone),
+//   picks by pick_best_row: the smallest cost, NaN as +inf, ties to the lowest lane, an all-NaN
+//     group its lowest lane, and
+//   stores the picked row into every row of the group in `states` and, inside a resident call
+//     (hist, cur), into each lane's history row of this frame: row cur[2 b + 1] - 1 of the row
+//     cursor, which the final kernel has already advanced (as pick_apply).
+// The groups are device memory the host writes while the stream is drained (the graphs hold the
+// table's address, never a group).  act (a free-paced batch): a group idles as one -- the host
+// refuses a split group -- so its first lane's word decides, and an idle group loads and stores
+// nothing else.  Lane l < 27 of the wave carries column l of every row it loads before the first
+// store of that column; the picked row's load depends on every cost, so no store of the wave
+// precedes a load another lane still needs.  Plain vector stores.
+struct LaneGroups {
+    int first[16];  // lane b's group begins at lane first[b] ...
+    int size[16];   // ... and holds size[b] lanes
+};
+static_assert(HPE_BATCH_MAX == 16, "LaneGroups holds one entry per lane");
+__global__ __launch_bounds__(64) void k_group_pick(double *states, double *__restrict__ own,
+                                                   double *__restrict__ hist, const int *__restrict__ cur,
+                                                   const LaneGroups *__restrict__ grp,
+                                                   const int *__restrict__ act) {
+    const int b = blockIdx.x, l = threadIdx.x;
+    if (grp->first[b] != b) return;
+    if (act && !(act[b] & HPE_ACT_TRACK)) return;
+    const int n = grp->size[b];
+    double *const rows = states + (size_t)HPE_STATE_N * b;
+    const int w = pick_best_row(rows, n, l);
+    if (l > HPE_DOF) return;
+    const double x = rows[(size_t)HPE_STATE_N * w + l];
+    if (own)
+        for (int m = 0; m < n; ++m) own[(size_t)HPE_STATE_N * (b + m) + l] = rows[(size_t)HPE_STATE_N * m + l];
+    for (int m = 0; m < n; ++m) {
+        rows[(size_t)HPE_STATE_N * m + l] = x;
+        if (hist && cur) hist[(size_t)HPE_STATE_N * (cur[2 * (b + m) + 1] - 1) + l] = x;
+    }
 }
 
 // ------------------------------------------------------------------ lane reports

@@ -14,7 +14,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _lib, locate, report, view, window
+from . import _lib, group, locate, report, view, window
 from ._lib import HpeError, ptr
 
 __all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "scaled_hand",
@@ -546,6 +546,44 @@ class Context:
             raise TypeError("set_batch_hands takes handmodel or HandParams entries")
         arr = (_lib.HandParams * max(len(ps), 1))(*ps)
         self.check(self.lib.hpe_set_batch_hands(self._h, len(ps), arr))
+
+    def set_batch_seeds(self, seeds):
+        """A seed per lane (hpe_set_batch_seeds) in track_batch, track_raw_batch and the live
+        batch, from the next call or begin on: lane b's pso_evolve draws under seeds[b] -- it is
+        then the single-sequence call on a context after set_seed(seeds[b]), bit for bit -- and
+        the batch calls take exactly len(seeds) lanes; None (default): every lane draws under the
+        context's seed.  The batch optimiser keeps the context's seed.  A live batch in progress
+        keeps the seeds it began with: the call raises (HPE_E_STATE)."""
+        if seeds is None:
+            self.check(self.lib.hpe_set_batch_seeds(self._h, 0, None))
+            return
+        s = [int(v) for v in seeds]
+        arr = (C.c_uint64 * max(len(s), 1))(*s)
+        self.check(self.lib.hpe_set_batch_seeds(self._h, len(s), arr))
+
+    def set_batch_groups(self, sizes):
+        """Lane groups (hpe_set_batch_groups): sizes lists the groups' lane counts, consecutive
+        lanes, summing to the batch's B; after every tracked frame each group's rows of d_states
+        (and of d_hist) become the group's best own row by hpe.group.pick's rule, and the lanes'
+        own rows are kept for batch_group_rows.  None or an empty list (default): no groups."""
+        if sizes is None or len(sizes) == 0:
+            self.check(self.lib.hpe_set_batch_groups(self._h, 0, 0, None))
+            return
+        z = [int(v) for v in sizes]
+        arr = (C.c_int32 * len(z))(*z)
+        self.check(self.lib.hpe_set_batch_groups(self._h, sum(z), len(z), arr))
+
+    def batch_group_pick(self, d_states_ptr, B):
+        """The groups' pick on the B x 27 device rows at d_states_ptr (hpe_batch_group_pick),
+        asynchronous on the context stream: every group's rows become the group's best row."""
+        self.check(self.lib.hpe_batch_group_pick(self._h, int(B), C.c_void_p(int(d_states_ptr))))
+
+    def batch_group_rows(self, B):
+        """Every lane's own {bestp, cost} of the last grouped frame it tracked, (B, 27)
+        (hpe_batch_group_rows).  Synchronises."""
+        rows = np.zeros((int(B), 27))
+        self.check(self.lib.hpe_batch_group_rows(self._h, int(B), ptr(rows, C.c_double)))
+        return rows
 
     def lane_window_from_pose(self, lane, theta, focal=241.42, margin_xy=0.0, margin_z=0.0):
         """window_from_pose under lane `lane`'s hand (hpe_lane_window_from_pose): init[lane] of a

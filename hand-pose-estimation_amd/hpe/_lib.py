@@ -137,6 +137,10 @@ SIGNATURES = {
     "hpe_set_batch_hands": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(HandParams)]),
     "hpe_lane_window_from_pose": (C.c_int, [C.c_void_p, C.c_int, dp, C.c_double, C.c_double,
                                             C.c_double, C.POINTER(Window)]),
+    "hpe_set_batch_seeds": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "hpe_set_batch_groups": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ip]),
+    "hpe_batch_group_pick": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hpe_batch_group_rows": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "hpe_set_batch_pacing": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_batch_pending": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "hpe_pso_optimise_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, ip,

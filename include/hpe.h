@@ -632,6 +632,62 @@ int hpe_set_batch_hands(hpe_ctx *ctx, int B, const hpe_hand_params *hands);
 int hpe_lane_window_from_pose(hpe_ctx *ctx, int lane, const double theta[26], double focal,
                               double margin_xy, double margin_z, hpe_window *out);
 
+/* Lane seeds and groups: N subswarms per stream as lanes of the same launches, with the best of
+ * them carried to the next frame -- SURVEY 8e's independent subswarms and per-frame best-of-N
+ * (hpe_subswarm_init, hpe_pick_best) on one GPU, with no communicator and no extra process.
+ *
+ * hpe_set_batch_seeds: seeds is a host array of B entries, copied before return.  From the next
+ * hpe_track_batch_dev or hpe_track_raw_batch_dev call, or the next hpe_batch_pipeline_begin*, lane
+ * b's pso_evolve draws under seeds[b] -- the normals table, the link topology and its inbox
+ * counts, and the Philox key of the per-generation draws -- in both batch forms, at one and two
+ * waves per particle: lane b equals the single-sequence call on a context after
+ * hpe_set_seed(seeds[b]), bit for bit.  seeds == NULL (the default state): every lane uses the
+ * context's seed again; B is ignored.  Two lanes may hold the same seed.  The refine draws nothing
+ * and is untouched.  hpe_pso_optimise_batch and hpe_batch_pipeline_optimise keep the context's
+ * seed for every lane.  The seeds live in device tables built at the next batch call for its
+ * num_p and maxiter; new seeds between two calls of one shape rewrite the tables in place (the
+ * stream drained) and replay the tracking graphs -- nothing is captured -- unless the largest
+ * informant in-degree K over the seeds changes, which sizes the lanes' inboxes: then the graphs of
+ * the batch calls are captured again.
+ *
+ * hpe_set_batch_groups: sizes is a host array of n_groups positive entries summing to B; group g
+ * is the next sizes[g] consecutive lanes.  n_groups == 0 or sizes == NULL turns groups off (the
+ * default state).  With groups on, after every tracked frame of every group, in all three batch
+ * calls: lane b's own result {bestp, cost} is kept in an own-rows table of B x 27 doubles in
+ * device memory (hpe_batch_group_rows), and every row of the group in d_states -- and the lanes'
+ * d_hist rows of that frame -- becomes the group's best own row by hpe_pick_best's rule: the
+ * smallest cost wins, a NaN cost never wins, ties go to the lowest lane, and a group whose costs
+ * are all NaN takes its lowest lane's row.  The next frame's refine reads its lane's row of
+ * d_states as ever, so whatever writes rows between two calls keeps working
+ * (hpe_batch_pipeline_optimise, hpe_batch_pipeline_locate, a caller's own write ordered on the
+ * stream); reports carry the lane's row of d_states, the picked one; FOLLOW windows follow the
+ * picked pose.  No pick happens before a group's first frame: each lane starts from the row the
+ * caller gave it.  A group of one lane behaves bit for bit like no group.  The caller passes the
+ * same frames for every lane of a group; nothing checks that it does.
+ * Free pacing (HPE_PACING_FREE): a group advances as one.  In the begin and in every track call
+ * the entries of a group's lanes are all NULL or all non-NULL, else HPE_E_ARG and nothing
+ * changes; a group that idles in a call keeps its rows of d_states and its own rows bit for bit.
+ *
+ * hpe_batch_group_pick: the same pick on arbitrary rows, asynchronous on hpe_stream(ctx).
+ * d_states is device memory, B x 27; every group's rows are replaced by the group's best row.
+ * After hpe_batch_pipeline_optimise over a group it starts the group from its best
+ * initialisation.  It does not touch the own-rows table.
+ * hpe_batch_group_rows: synchronises and copies the own-rows table, B x 27, to host memory: each
+ * lane's own result of the last frame it tracked.
+ *
+ * Refused, and nothing changes: B outside 1..HPE_BATCH_MAX (with non-NULL seeds or sizes), sizes
+ * that are not positive or do not sum to B, a batch call or begin (or hpe_batch_group_pick,
+ * hpe_batch_group_rows) whose B differs from the B the seeds or groups were set for, null
+ * d_states or rows_out -- HPE_E_ARG; either setter while a live batch is in progress --
+ * HPE_E_STATE: the batch keeps what it began with, as it keeps its form, windows, hands and
+ * pacing; hpe_batch_group_pick with no groups set, hpe_batch_group_rows before any grouped frame
+ * was tracked since the groups were set -- HPE_E_STATE; a batch call under seeds of which one has
+ * an informant in-degree above the inbox bound (24) -- HPE_E_ARG, as for the context's seed. */
+int hpe_set_batch_seeds(hpe_ctx *ctx, int B, const uint64_t *seeds);
+int hpe_set_batch_groups(hpe_ctx *ctx, int B, int n_groups, const int32_t *sizes);
+int hpe_batch_group_pick(hpe_ctx *ctx, int B, double *d_states);
+int hpe_batch_group_rows(hpe_ctx *ctx, int B, double *rows_out);
+
 /* Lane pacing: whether the lanes of a live batch (hpe_batch_pipeline_begin /
  * hpe_track_batch_pipelined) advance in lockstep.  Cameras of a rig are not frame-locked: a 30 Hz
  * and a 60 Hz camera share it, a USB camera drops a frame, a person leaves one view.

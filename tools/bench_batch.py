@@ -63,7 +63,15 @@ frame back, and runs the lanes alone on its float conversion.  --host-reduce (wi
 application makes without views, cam[r0:r0+240K:K, c0:c0+320K:K], and fed to the plain u16 batch
 (with --in-place that copy goes straight into the lane's pinned buffer): the baseline a view batch
 is measured against.  All three runs track identical trajectories and print the same results_sha1.
+--seeds distinct (with any mode and form): a seed per lane (hpe_set_batch_seeds), lane b's 1000 + b;
+the default, shared, is every lane under the context's seed (the call is not made).  The check
+against the lanes alone runs before the seeds are set.
+--group N (with any mode and form; N divides every lane count): groups of N consecutive lanes over
+one stream (hpe_set_batch_groups) -- lane b is fed stream b // N, and after every frame the group's
+rows become its best own row.  Every line then carries "group", and "final_cost", the cost of
+every lane's row after the last frame.
 Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave] [--profile]
+                                             [--seeds shared|distinct] [--group N]
                                              [--window off|fixed|follow] [--hands shared|distinct]
                                              [--pacing lockstep|free] [--drop K]
                                              [--report DEPTH] [--consume sync|report]
@@ -369,7 +377,13 @@ def main():
     ap.add_argument("--host-reduce", action="store_true")
     ap.add_argument("--unit", type=float, default=None, metavar="MM")
     ap.add_argument("--in-place", action="store_true")
+    ap.add_argument("--seeds", choices=("shared", "distinct"), default="shared")
+    ap.add_argument("--group", type=int, default=0, metavar="N")
     a = ap.parse_args()
+    if a.group < 0 or any(int(x) % max(a.group, 1) for x in a.lanes.split(",")):
+        ap.error("--group N: N >= 1 divides every lane count")
+    if a.group and (a.hands != "shared" or a.drop):
+        ap.error("--group needs --hands shared and no --drop")
     quantised = a.input in ("u16", "view") or a.unit is not None
     cam_mode = a.input == "view" or a.host_reduce
     if a.host_reduce and a.input != "u16":
@@ -464,7 +478,8 @@ def main():
     if alone:
         alone.close()
     for B in counts:
-        slots = [b * n for b in range(B)]
+        of = [b // a.group if a.group else b for b in range(B)]  # lane b's stream
+        slots = [of[b] * n for b in range(B)]
         if a.hands == "distinct":
             # lane b's own hand: its frames rendered by, and its yardstick run on, a context
             # created with it (in the wave form where this line's check needs that)
@@ -505,7 +520,7 @@ def main():
             for h in own:
                 h.ctx.close()
         if a.raw:
-            ptrs = [r.data_ptr() for r in raws[:B]]
+            ptrs = [raws[of[b]].data_ptr() for b in range(B)]
 
         hist = torch.empty((B, n, 27), dtype=torch.float64, device="cuda:0") if a.raw else None
 
@@ -520,7 +535,8 @@ def main():
             elif a.live and a.drop:
                 tracked[0] = run_live_rebegin(ctx, torch, st, subs, host[:B], n, a.drop)
             elif a.live:
-                consumed[0] = run_live(ctx, st, feed[:B], n, a.consume, begin_kw, a.in_place, reduce)
+                consumed[0] = run_live(ctx, st, [feed[of[b]] for b in range(B)], n, a.consume,
+                                       begin_kw, a.in_place, reduce)
             elif a.raw:
                 ctx.track_raw_batch(P, 1, st.data_ptr(), ptrs, n, frames_per_graph=FPG,
                                     d_hist_ptr=hist.data_ptr())
@@ -534,6 +550,10 @@ def main():
         def results():
             return (hist if a.raw else st).cpu().numpy().copy()
 
+        if a.seeds == "distinct":  # (not called otherwise: an older build under A/B lacks it)
+            ctx.set_batch_seeds([1000 + b for b in range(B)])
+        if a.group:
+            ctx.set_batch_groups([a.group] * (B // a.group))
         off = None
         if a.window != "off":  # the same lanes without windows, then the windows for B lanes
             run()
@@ -595,6 +615,11 @@ def main():
             line["hands"] = "distinct"
             line["hand_scales"] = [round(s, 6) for s in scales]
             line["checked_against_own_hand_contexts"] = checked
+        if a.seeds == "distinct":
+            line["seeds"] = "distinct"
+        if a.group:
+            line["group"] = a.group
+            line["final_cost"] = [float(v) for v in st.cpu().numpy()[:, 26]]
         if off is not None:
             line["equals_off"] = bool(np.array_equal(results(), off))
         # the timed run's results (raw: the histories; else the final states), for an A/B of builds
@@ -608,6 +633,10 @@ def main():
             ctx.set_batch_window("off")
         if a.hands == "distinct":
             ctx.set_batch_hands(None)
+        if a.seeds == "distinct":
+            ctx.set_batch_seeds(None)
+        if a.group:
+            ctx.set_batch_groups(None)
     ctx.close()
     return 0
 
