@@ -156,6 +156,8 @@ struct GraphKey {
                 // device memory holds
     int groups; // lane groups are set (hpe_set_batch_groups): one more launch, k_group_pick; never
                 // a group, which device memory holds
+    int clean;  // lane cleaning is on (hpe_set_batch_clean): one more launch, k_clean_b, and the
+                // u16 preparation on the staging frames; never a parameter, which device memory holds
     double focal;
     const void *in;  // the raw frames' base
     double *state, *hist;  // a lane's or the batch's states; the history rows
@@ -164,7 +166,8 @@ struct GraphKey {
                filt == o.filt && parity == o.parity && tail_next == o.tail_next &&
                next == o.next && cur == o.cur && B == o.B && wave == o.wave && win == o.win &&
                hands == o.hands && pacing == o.pacing && report == o.report && u16 == o.u16 &&
-               view == o.view && seeds == o.seeds && groups == o.groups && to_cm == o.to_cm &&
+               view == o.view && seeds == o.seeds && groups == o.groups && clean == o.clean &&
+               to_cm == o.to_cm &&
                downsample == o.downsample && focal == o.focal && in == o.in &&
                state == o.state && hist == o.hist;
     }
@@ -243,6 +246,12 @@ struct LaneFrameIo {
     const float *unit = nullptr;
     // ... camera frames read through the lanes' views: unit then names the batch's ViewTab
     bool view = false;
+    // lane cleaning: k_clean_b on this table of the parity `prep` prepares (null: off), ahead of
+    // the refine launch; clean_view: the batch's ViewTab where the pinned buffers hold camera
+    // frames (prep then names the staging frames, and view is false: the u16 forms read them)
+    const CleanArgs *clean = nullptr;
+    const CleanTab *clean_par = nullptr;
+    const ViewTab *clean_view = nullptr;
 };
 
 }  // namespace
@@ -423,8 +432,40 @@ struct hpe_ctx {
         const float *unit_arg() const {  // the lane kernels' `unit` argument
             return view ? (const float *)d_view.get() : u16 ? d_unit.get() : nullptr;
         }
-        LaneSrc src() const { return view ? LANE_SRC_VIEW : u16 ? LANE_SRC_U16 : LANE_SRC_RING; }
+        // lane cleaning (hpe_set_batch_clean).  clean_B, clean_par: the setting the next u16 or
+        // view begin reads (0: off).  clean: the batch in progress began with cleaning on (it
+        // keeps that); cleaned_B: the lanes of the last cleaned begin (hpe_batch_clean_readback),
+        // 0: none yet.  d_stage holds the cleaned 240x320 frames by [parity][lane], d_cargs
+        // k_clean_b's table of {pinned buffer, staging frame}, d_cpar the lanes' parameters and
+        // d_ctab the PrepArgs table whose raw frames are the staging frames: allocated together
+        // by the first begin with cleaning on, never moved (the graphs hold their addresses).
+        int clean_B = 0;
+        hpe_clean clean_par[HPE_BATCH_MAX] = {};
+        bool clean = false;
+        int cleaned_B = 0;
+        DevBuf<unsigned short> d_stage;  // [2][HPE_BATCH_MAX][240 * 320]
+        DevBuf<CleanArgs> d_cargs;       // [2][HPE_BATCH_MAX]
+        DevBuf<CleanTab> d_cpar;
+        DevBuf<PrepArgs> d_ctab;         // [2][HPE_BATCH_MAX]
+        unsigned short *stage(int parity, int lane) const {
+            return d_stage.get() + ((size_t)parity * HPE_BATCH_MAX + lane) * HPE_IMG_H * HPE_IMG_W;
+        }
+        // what the preparation reads: a cleaned batch's staging frames in the u16 form -- also
+        // for a view batch, whose ViewTab has the unit at offset 0 -- else the pinned ring
+        const PrepArgs *prep_tab() const { return clean ? d_ctab.get() : d_tab.get(); }
+        LaneSrc src() const {
+            return clean ? LANE_SRC_U16 : view ? LANE_SRC_VIEW : u16 ? LANE_SRC_U16 : LANE_SRC_RING;
+        }
     } live;
+    // hpe_clean_depth_u16's own frames and tables (allocated by its first call; the source grows
+    // to the largest camera frame given)
+    struct CleanOne {
+        DevBuf<unsigned short> d_src, d_dst;
+        size_t src_pixels = 0;
+        DevBuf<CleanArgs> d_args;
+        DevBuf<CleanTab> d_par;
+        DevBuf<ViewTab> d_view;
+    } clean_one;
     // lane reports (hpe_set_batch_report): the setting the next begin reads (depth 0: off), and
     // what the rings hold -- the depth and lane count of the last batch begun with reports on
     // (ring_depth 0: nothing to read), per lane the reports enqueued since that begin.  The ring
@@ -2516,6 +2557,10 @@ static int track_lane_frame(hpe_ctx *c, int P, int refine, int B, double *d_stat
     if (f.win && io.follow)
         hipLaunchKernelGGL(lane_window_kernel(f), dim3(B), dim3(64), 0, c->stream,
                            (const double *)d_states, hand, (const WinPar *)c->win.d_par, io.win, act);
+    if (prep && io.clean)  // lane cleaning: the next frames, from the pinned ring to the staging
+        hipLaunchKernelGGL(io.clean_view ? k_clean_b<true> : k_clean_b<false>,
+                           dim3(CLEAN_TILES, B), dim3(CLEAN_NT), 0, c->stream, io.clean,
+                           io.clean_par, io.clean_view, act);
     if (prep || refine)
         launch(c, HPE_PROF_REFINE, kr, dim3(prep ? 1 + PREP_WG : 1, B), dim3(RF_NT), RF_DYN_LDS,
                d_states, obs, hand, c->d_bevals.get(), refine ? 1 : 0, io.prep, (const DevWindow *)io.win,
@@ -3232,6 +3277,9 @@ int hpe_track_raw_batch_dev(hpe_ctx *c, int P, int refine, int B, double *d_stat
     if ((rc = check_window_lanes(c, B)) || (rc = check_hand_lanes(c, B)) ||
         (rc = check_seed_group_lanes(c, B)))
         return rc;
+    if (c->live.clean_B)
+        return fail(c, HPE_E_STATE, "lane cleaning is set (hpe_set_batch_clean): it cleans a live "
+                    "batch's 16-bit frames, resident float sequences are refused (turn it off)");
     HIPCHK(c, hipSetDevice(c->device));
     to_cm = to_cm ? 1 : 0;
     if ((rc = ensure_raw_batch(c, B, to_cm, focal))) return rc;
@@ -3321,6 +3369,38 @@ static int ensure_live_batch(hpe_ctx *c, int B, size_t need_floats) {
     HIPCHK(c, hipMemcpy(lv.d_tab, tab.data(), sizeof(PrepArgs) * tab.size(), hipMemcpyHostToDevice));
     lv.tab_gen = c->rb.tab_gen;
     lv.tab_lanes = lv.lanes;
+    return HPE_OK;
+}
+
+// Lane cleaning's part of a begin with cleaning on (ensure_live_batch first; the stream has
+// drained): the staging frames and the three tables, allocated once, all or none, and never
+// moved; then the tables written -- the pinned buffers may have been replaced, rb's table
+// rewritten and the parameters set again since the last cleaned begin.
+static int ensure_clean(hpe_ctx *c) {
+    hpe_ctx::LiveBatch &lv = c->live;
+    const size_t M = HPE_BATCH_MAX, npix = (size_t)HPE_IMG_H * HPE_IMG_W;
+    if (!lv.d_stage) {
+        HIPCHK(c, alloc_all(lv.d_cargs, 2 * M, lv.d_cpar, 1, lv.d_ctab, 2 * M));
+        // the frames, the guard, moved in last and zeroed first (a lane that has had no frame yet
+        // reads back empty): a block that failed part way runs again in full -- the three tables
+        // may then still be allocated, and DevBuf::alloc releases what it holds before it allocates
+        DevBuf<unsigned short> stage;
+        HIPCHK(c, stage.alloc(2 * M * npix));
+        HIPCHK(c, hipMemset(stage, 0, sizeof(unsigned short) * 2 * M * npix));
+        lv.d_stage = std::move(stage);
+    }
+    std::vector<CleanArgs> args(2 * M, CleanArgs{nullptr, nullptr});
+    std::vector<PrepArgs> tab = c->rb.tab;
+    for (int p = 0; p < 2; ++p)
+        for (int b = 0; b < lv.lanes; ++b) {
+            args[p * M + b] = CleanArgs{(const unsigned short *)lv.h_raw[p][b].dev(), lv.stage(p, b)};
+            tab[p * M + b].raw = (const float *)lv.stage(p, b);
+        }
+    HIPCHK(c, hipMemcpy(lv.d_cargs, args.data(), sizeof(CleanArgs) * args.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(lv.d_ctab, tab.data(), sizeof(PrepArgs) * tab.size(), hipMemcpyHostToDevice));
+    CleanTab pt{};
+    std::memcpy(pt.par, lv.clean_par, sizeof(pt.par));
+    HIPCHK(c, hipMemcpy(lv.d_cpar, &pt, sizeof(pt), hipMemcpyHostToDevice));
     return HPE_OK;
 }
 
@@ -3549,6 +3629,14 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
         const size_t fl = ((size_t)views[b].pitch * (size_t)views[b].height + 1) / 2;
         if (fl > need_floats) need_floats = fl;
     }
+    // lane cleaning: the rule is defined on 16-bit values, and the parameters are the lanes'
+    const bool clean = c->live.clean_B != 0;
+    if (clean && !u16)
+        return fail(c, HPE_E_STATE, "lane cleaning is set (hpe_set_batch_clean): it cleans 16-bit "
+                    "frames, a float batch is refused (turn it off, or begin a u16 or view batch)");
+    if (clean && B != c->live.clean_B)
+        return fail(c, HPE_E_ARG, "%d lanes, the cleaning parameters were set for %d", B,
+                    c->live.clean_B);
     const bool paced = c->batch_pacing == HPE_PACING_FREE;
     if (!depth_mm || (!paced && lane_frames(depth_mm, B) != 1))
         return fail(c, HPE_E_ARG, "null frame array or lane frame");
@@ -3584,6 +3672,12 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
     int rc = ensure_batch_lanes(c);
     if (rc || (rc = ensure_raw_batch(c, B, to_cm, focal)) || (rc = ensure_live_batch(c, B, need_floats))) return rc;
     if ((rc = write_windows(c, focal, to_cm))) return rc;
+    lv.clean = false;
+    if (clean) {
+        if ((rc = ensure_clean(c))) return rc;
+        lv.clean = true;
+        lv.cleaned_B = B;
+    }
     lv.u16 = u16;
     lv.view = views != nullptr;
     if (views) {  // the unit and the views, one block (the stream has drained)
@@ -3613,8 +3707,14 @@ static int live_batch_begin(hpe_ctx *c, int B, const void *const *depth_mm, bool
     const bool win = c->win.mode != HPE_WINDOW_OFF;
     // paced: only the lanes given a frame prepare one; the others start empty
     if (paced) write_lane_act(c, B, 0, given);
+    if (lv.clean)  // cleaned first, from the pinned buffers to the staging frames of parity 0
+        hipLaunchKernelGGL(lv.view ? k_clean_b<true> : k_clean_b<false>, dim3(CLEAN_TILES, B),
+                           dim3(CLEAN_NT), 0, c->stream, (const CleanArgs *)lv.d_cargs,
+                           (const CleanTab *)lv.d_cpar,
+                           (const ViewTab *)(lv.view ? lv.d_view.get() : nullptr),
+                           (const int *)(paced ? lv.d_act : nullptr));
     hipLaunchKernelGGL(lane_prepare_kernel(lv.src(), win, paced),
-                       dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream, (const PrepArgs *)lv.d_tab,
+                       dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream, lv.prep_tab(),
                        (const DevWindow *)(win ? c->win.d_tab : nullptr),
                        (const int *)(paced ? lv.d_act : nullptr),
                        lv.unit_arg(), (const float *const *)nullptr,
@@ -3699,6 +3799,116 @@ int hpe_batch_views_readback(hpe_ctx *c, int B, hpe_view *out) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, (const char *)lv.d_view.get() + offsetof(ViewTab, view),
                         sizeof(hpe_view) * (size_t)B, hipMemcpyDeviceToHost));
+    return HPE_OK;
+}
+
+// ---------------------------------------------------------------- lane cleaning
+static_assert(offsetof(ViewTab, unit) == 0, "a cleaned view batch's u16 preparation reads the unit there");
+
+int hpe_clean_defaults(float unit_mm, hpe_clean *out) {
+    if (!out || !(std::isfinite(unit_mm) && unit_mm > 0)) return HPE_E_ARG;
+    const double e = std::nearbyint(15.0 / (double)unit_mm);
+    *out = hpe_clean{(uint16_t)(e < 1 ? 1 : e > 65535 ? 65535 : e), 3, HPE_CLEAN_MEDIAN, 0};
+    return HPE_OK;
+}
+
+// One lane's parameters against the refusals of include/hpe.h "Lane cleaning".
+static int check_clean(hpe_ctx *c, const hpe_clean &p, int lane) {
+    if (p.support > 8)
+        return fail(c, HPE_E_ARG, "lane %d: clean support %d above 8", lane, (int)p.support);
+    if ((p.flags & ~HPE_CLEAN_MEDIAN) || p.pad)
+        return fail(c, HPE_E_ARG, "lane %d: unknown clean flags 0x%x or non-zero pad %u", lane,
+                    (unsigned)p.flags, (unsigned)p.pad);
+    return HPE_OK;
+}
+
+int hpe_set_batch_clean(hpe_ctx *c, int B, const hpe_clean *params) {
+    if (!c) return HPE_E_ARG;
+    hpe_ctx::LiveBatch &lv = c->live;
+    if (params) {
+        if (B < 1 || B > HPE_BATCH_MAX)
+            return fail(c, HPE_E_ARG, "batch of %d lanes out of range [1, %d]", B, HPE_BATCH_MAX);
+        for (int b = 0; b < B; ++b)
+            if (int rc = check_clean(c, params[b], b)) return rc;
+    }
+    if (lv.cur >= 0) {  // a live batch keeps cleaning on or off, and its lanes
+        if ((params != nullptr) != lv.clean)
+            return fail(c, HPE_E_STATE, "a live batch is in progress: it keeps lane cleaning %s, as "
+                        "it began (end it first)", lv.clean ? "on" : "off");
+        if (params && B != lv.B)
+            return fail(c, HPE_E_STATE, "a live batch of %d lanes is in progress: cleaning "
+                        "parameters for %d lanes (end it first)", lv.B, B);
+    }
+    if (!params) {
+        lv.clean_B = 0;
+        return HPE_OK;
+    }
+    if (lv.cur >= 0) {  // the table, once nothing in flight reads it: from the next frame cleaned
+        CleanTab pt{};
+        std::memcpy(pt.par, params, sizeof(hpe_clean) * (size_t)B);
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(lv.d_cpar, &pt, sizeof(pt), hipMemcpyHostToDevice));
+    }
+    std::memset(lv.clean_par, 0, sizeof(lv.clean_par));
+    std::memcpy(lv.clean_par, params, sizeof(hpe_clean) * (size_t)B);
+    lv.clean_B = B;
+    return HPE_OK;
+}
+
+int hpe_clean_depth_u16(hpe_ctx *c, const uint16_t *frame, const hpe_view *view,
+                        const hpe_clean *params, uint16_t *out) {
+    if (!c) return HPE_E_ARG;
+    if (!frame || !params || !out) return fail(c, HPE_E_ARG, "null frame, parameters or result");
+    if (int rc = check_clean(c, *params, 0)) return rc;
+    if (view)
+        if (int rc = check_view(c, *view, 0)) return rc;
+    const size_t npix = (size_t)HPE_IMG_H * HPE_IMG_W;
+    const size_t src_pixels = view ? (size_t)view->pitch * (size_t)view->height : npix;
+    HIPCHK(c, hipSetDevice(c->device));
+    hpe_ctx::CleanOne &o = c->clean_one;
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier call's kernel may still read the buffers
+    if (!o.d_dst) {
+        HIPCHK(c, alloc_all(o.d_args, 1, o.d_par, 1, o.d_view, 1, o.d_dst, npix));
+        o.src_pixels = 0;
+    }
+    if (src_pixels > o.src_pixels) {
+        o.src_pixels = 0;
+        HIPCHK(c, o.d_src.alloc(src_pixels));
+        o.src_pixels = src_pixels;
+    }
+    const CleanArgs args{o.d_src.get(), o.d_dst.get()};
+    CleanTab pt{};
+    pt.par[0] = *params;
+    ViewTab vt{};
+    if (view) vt.view[0] = *view;
+    HIPCHK(c, hipMemcpy(o.d_src, frame, sizeof(uint16_t) * src_pixels, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(o.d_args, &args, sizeof(args), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(o.d_par, &pt, sizeof(pt), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(o.d_view, &vt, sizeof(vt), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(view ? k_clean_b<true> : k_clean_b<false>, dim3(CLEAN_TILES, 1),
+                       dim3(CLEAN_NT), 0, c->stream, (const CleanArgs *)o.d_args,
+                       (const CleanTab *)o.d_par, (const ViewTab *)(view ? o.d_view.get() : nullptr),
+                       (const int *)nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, o.d_dst, sizeof(uint16_t) * npix, hipMemcpyDeviceToHost));
+    return HPE_OK;
+}
+
+int hpe_batch_clean_readback(hpe_ctx *c, int parity, int lane, uint16_t *out) {
+    if (!c) return HPE_E_ARG;
+    if (!out) return fail(c, HPE_E_ARG, "null frame");
+    hpe_ctx::LiveBatch &lv = c->live;
+    if (!lv.cleaned_B)
+        return fail(c, HPE_E_STATE, "no cleaned batch has begun (hpe_set_batch_clean before the begin)");
+    if (parity < 0 || parity > 1) return fail(c, HPE_E_ARG, "buffer parity %d", parity);
+    if (lane < 0 || lane >= lv.cleaned_B)
+        return fail(c, HPE_E_ARG, "lane %d outside the cleaned batch's %d lanes", lane, lv.cleaned_B);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, lv.stage(parity, lane), sizeof(uint16_t) * (size_t)HPE_IMG_H * HPE_IMG_W,
+                        hipMemcpyDeviceToHost));
     return HPE_OK;
 }
 
@@ -3789,13 +3999,19 @@ static int live_batch_track(hpe_ctx *c, int P, int refine, int B, double *d_stat
     // next frames read from the pinned buffers of parity nxt), no history or cursor, and the final
     // launch that publishes the batch's frame number
     LaneFrameIo io{c->rb.d_obs + cur * HPE_BATCH_MAX, false, nullptr, nullptr, nullptr};
-    if (next) io.prep = lv.d_tab + nxt * HPE_BATCH_MAX;
+    if (next) io.prep = lv.prep_tab() + nxt * HPE_BATCH_MAX;
     if (c->win.mode != HPE_WINDOW_OFF) io.win = c->win.d_tab + nxt * HPE_BATCH_MAX;
     io.follow = c->win.mode == HPE_WINDOW_FOLLOW;
     io.seq = lv.d_seq;
     io.done_host = lv.h_done.dev();
     io.unit = lv.unit_arg();
-    io.view = lv.view;
+    io.view = lv.view && !lv.clean;
+    key.clean = lv.clean ? 1 : 0;  // ... nor whether it is cleaned (never a parameter)
+    if (lv.clean) {  // k_clean_b ahead of the refine launch, then the u16 forms on the staging
+        io.clean = lv.d_cargs + nxt * HPE_BATCH_MAX;
+        io.clean_par = lv.d_cpar;
+        if (lv.view) io.clean_view = lv.d_view;
+    }
     if (paced) {
         write_lane_act(c, B, lv.pending, given);
         io.act = lv.d_act;
@@ -4086,10 +4302,11 @@ int hpe_batch_pipeline_locate(hpe_ctx *c, int B, double *d_states, uint32_t lane
     const int cur = lv.cur, M = HPE_BATCH_MAX;
     // the lanes' current raw frames: the pinned buffers of the parity the next track call tracks
     for (int b = 0; b < B; ++b)
-        if (lanes >> b & 1) ln.raw[b] = lv.h_raw[cur][b].dev();
+        if (lanes >> b & 1)  // (a cleaned batch: the lane's cleaned frame, a 240x320 u16 frame)
+            ln.raw[b] = lv.clean ? (const void *)lv.stage(cur, b) : (const void *)lv.h_raw[cur][b].dev();
     DevWindow *const wcur = c->win.d_tab + cur * M;
     DevWindow *const woth = c->win.mode == HPE_WINDOW_FIXED ? c->win.d_tab + (cur ^ 1) * M : nullptr;
-    if (lv.view) {  // the lanes' camera frames, read through their views
+    if (lv.view && !lv.clean) {  // the lanes' camera frames, read through their views
         std::memcpy(ln.view, lv.views, sizeof(ln.view));
         hipLaunchKernelGGL((k_locate_b<true, true>), dim3(B), dim3(LOC_NT), 0, c->stream, ln,
                            (unsigned)lanes, lv.unit_mm, lv.to_cm, lv.focal, wcur, woth, lo.d_act.get(),
@@ -4112,7 +4329,7 @@ int hpe_batch_pipeline_locate(hpe_ctx *c, int B, double *d_states, uint32_t lane
     // kernel in its windowed, idle-aware form, gated by the table the locate kernel filled
     hipLaunchKernelGGL(lane_prepare_kernel(lv.src(), true, true),
                        dim3(PREP_WG, B), dim3(PREP_NT), 0, c->stream,
-                       (const PrepArgs *)lv.d_tab + cur * M, (const DevWindow *)wcur,
+                       lv.prep_tab() + cur * M, (const DevWindow *)wcur,
                        (const int *)lo.d_act, lv.unit_arg(),
                        (const float *const *)nullptr, (const int *)nullptr);
     LocTmpl tp{};

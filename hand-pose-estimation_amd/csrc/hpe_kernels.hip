@@ -1995,6 +1995,9 @@ __global__ __launch_bounds__(64) void k_lane_joints_b(const double *__restrict__
 // ------------------------------------------------------------------ lane location
 #include "hpe_locate.hpp"
 
+// ------------------------------------------------------------------ lane cleaning
+#include "hpe_clean.hpp"
+
 #include "hpe_optimise.hpp"
 
 // ------------------------------------------------------------------ synthetic frames

@@ -14,7 +14,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _lib, group, locate, report, view, window
+from . import _lib, clean, group, locate, report, view, window
 from ._lib import HpeError, ptr
 
 __all__ = ["handmodel", "observedmodel", "costfunc", "PSO", "reference_hand", "scaled_hand",
@@ -608,6 +608,50 @@ class Context:
         out = (_lib.View * int(B))()
         self.check(self.lib.hpe_batch_views_readback(self._h, int(B), out))
         return [view.as_view(v) for v in out]
+
+    @staticmethod
+    def _clean_par(p):
+        p = clean.as_clean(p)
+        return _lib.CleanPar(*[getattr(p, f) for f in clean.FIELDS])
+
+    def set_batch_clean(self, params=None):
+        """Lane cleaning from the next u16 or view begin on (hpe_set_batch_clean): params[b]
+        (hpe.clean.Clean or anything as_clean takes) are lane b's; None turns it off.  During a
+        cleaned live batch, parameters for the same lanes apply from the next frame cleaned."""
+        if params is None:
+            self.check(self.lib.hpe_set_batch_clean(self._h, 0, None))
+            return
+        tab = (_lib.CleanPar * max(len(params), 1))(*[self._clean_par(p) for p in params])
+        self.check(self.lib.hpe_set_batch_clean(self._h, len(params), tab))
+
+    def clean_depth_u16(self, frame_u16, params, view_=None):
+        """The cleaning rule on one host frame by the batch's kernel (hpe_clean_depth_u16;
+        synchronises): frame_u16 is a 240x320 uint16 frame, or with view_ the view's
+        (height, pitch) camera frame; returns the cleaned 240x320 uint16 frame, equal to
+        hpe.clean.clean on the (reduced) frame."""
+        f = np.asarray(frame_u16)
+        if f.dtype != np.uint16:
+            raise TypeError(f"clean_depth_u16 takes uint16 frames, got {f.dtype}")
+        f = np.ascontiguousarray(f)
+        v = None if view_ is None else view.as_view(view_)
+        need = IMG_H * IMG_W if v is None else v.pitch * v.height
+        if f.size != need:
+            raise ValueError(f"a frame of {f.size} pixels, {need} expected")
+        vs = None if v is None else _lib.View(*[getattr(v, k) for k in view.FIELDS])
+        par = self._clean_par(params)
+        out = np.empty((IMG_H, IMG_W), dtype=np.uint16)
+        self.check(self.lib.hpe_clean_depth_u16(
+            self._h, C.c_void_p(f.ctypes.data), None if vs is None else C.byref(vs),
+            C.byref(par), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def batch_clean_readback(self, parity, lane):
+        """Lane `lane`'s cleaned 240x320 uint16 frame of buffer parity `parity`
+        (hpe_batch_clean_readback; synchronises)."""
+        out = np.empty((IMG_H, IMG_W), dtype=np.uint16)
+        self.check(self.lib.hpe_batch_clean_readback(self._h, int(parity), int(lane),
+                                                     C.c_void_p(out.ctypes.data)))
+        return out
 
     def batch_wave_wpp(self, num_p, B) -> int:
         """Waves per particle (1 or 2) of a wave-form batch of B lanes of num_p particles: the

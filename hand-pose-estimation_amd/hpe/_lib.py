@@ -55,6 +55,15 @@ class View(C.Structure):
                 ("flags", C.c_uint32), ("pad", C.c_int32)]
 
 
+CLEAN_MEDIAN = 1  # HPE_CLEAN_MEDIAN
+
+
+class CleanPar(C.Structure):
+    """hpe_clean: 8 bytes (hpe/clean.py is the rule in numpy)."""
+    _fields_ = [("edge", C.c_uint16), ("support", C.c_uint8), ("flags", C.c_uint8),
+                ("pad", C.c_uint32)]
+
+
 REPORT_TRACK, REPORT_INIT = 1, 2  # HPE_REPORT_* kinds
 REPORT_F_NAN, REPORT_F_EMPTY, REPORT_F_SUSPECT, REPORT_F_LOST = 1, 2, 4, 8  # HPE_REPORT_F_*
 
@@ -127,6 +136,11 @@ SIGNATURES = {
     "hpe_view_fit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                C.c_int, C.c_uint32, C.POINTER(View), dp, dp]),
     "hpe_batch_views_readback": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(View)]),
+    "hpe_clean_defaults": (C.c_int, [C.c_float, C.POINTER(CleanPar)]),
+    "hpe_set_batch_clean": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(CleanPar)]),
+    "hpe_clean_depth_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(View),
+                                      C.POINTER(CleanPar), C.c_void_p]),
+    "hpe_batch_clean_readback": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hpe_set_batch_form": (C.c_int, [C.c_void_p, C.c_int]),
     "hpe_batch_wave_wpp": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hpe_set_batch_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Window),

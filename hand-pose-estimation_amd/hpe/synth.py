@@ -41,6 +41,49 @@ def load_sequence(ctx: Context, n_frames: int, seed: int = 0, downsample: bool =
     return poses, sizes
 
 
+def _grow(mask: np.ndarray, k: int) -> np.ndarray:
+    """The mask dilated k times by the 3x3 square."""
+    m = mask.copy()
+    for _ in range(k):
+        p = np.zeros((m.shape[0] + 2, m.shape[1] + 2), dtype=bool)
+        p[1:-1, 1:-1] = m
+        m = np.zeros_like(m)
+        for dr in range(3):
+            for dc in range(3):
+                m |= p[dr:dr + mask.shape[0], dc:dc + mask.shape[1]]
+    return m
+
+
+def camera_noise(frame_u16, seed, background: int = 800, flying: float = 0.3,
+                 speckle: int = 40, ring: int = 10, jitter: int = 30) -> np.ndarray:
+    """What a time-of-flight or structured-light camera makes of a rendered uint16 frame (0: no
+    depth), seeded and deterministic; a new array.
+    Flying pixels: the share `flying` of the silhouette pixels -- hand pixels with a hole among
+    their eight neighbours -- takes a depth between its own and `background` (raw units, behind
+    the hand), 20 % to 80 % of the way.
+    Speckle: `speckle` single pixels scattered over the holes that lie 2 .. `ring` pixels from the
+    hand, at the hand's median depth +- `jitter`: inside any window that holds the hand."""
+    f = np.asarray(frame_u16)
+    if f.dtype != np.uint16 or f.ndim != 2:
+        raise TypeError(f"camera_noise takes 2-D uint16 frames, got {f.dtype}")
+    rng = np.random.default_rng(seed)
+    out = f.copy()
+    on = f > 0
+    if not on.any():
+        return out
+    edge = np.flatnonzero(on & _grow(~on, 1))
+    pick = edge[rng.random(edge.size) < flying]
+    z = f.ravel()[pick].astype(np.int64)
+    t = rng.uniform(0.2, 0.8, size=pick.size)
+    out.ravel()[pick] = np.clip(z + np.rint(t * (int(background) - z)), 1, 65535).astype(np.uint16)
+    free = np.flatnonzero(_grow(on, int(ring)) & ~_grow(on, 1))
+    spots = rng.choice(free, size=min(int(speckle), free.size), replace=False)
+    mid = int(np.median(f[on]))
+    out.ravel()[spots] = np.clip(mid + rng.integers(-int(jitter), int(jitter) + 1, size=spots.size),
+                                 1, 65535).astype(np.uint16)
+    return out
+
+
 def rig_scene(hand_mm, wrist_cm, focal: float = 241.42, wall_mm: float = 800.0,
               arm_behind_cm: float = 1.0, arm_half_cm: float = 2.5, speckle: int = 15,
               speckle_mm: float = 150.0, seed: int = 0) -> np.ndarray:

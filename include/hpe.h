@@ -448,7 +448,8 @@ int hpe_batch_frame_buffer(hpe_ctx *ctx, int lane, void **buf_out, size_t *bytes
  * ("no depth", like any other hole).  This is a pick (nearest-neighbour decimation), the usual
  * reduction for depth: averaging would invent surfaces across depth edges.  A hole at the picked
  * pixel stays a hole, whatever its camera neighbours hold; block rules (min-non-zero, median) are
- * not offered.  The flip tracks a left hand, or a camera that faces the user, with the right-hand
+ * not offered in the pick ("Lane cleaning" below runs a neighbourhood rule on the picked image).
+ * The flip tracks a left hand, or a camera that faces the user, with the right-hand
  * model.  The picked value follows the u16 batch's rule unchanged: rv = (float)u * unit_mm.
  *
  * hpe_batch_pipeline_begin_view is hpe_batch_pipeline_begin_u16 with views[b] (host, B entries,
@@ -509,6 +510,71 @@ int hpe_batch_pipeline_begin_view(hpe_ctx *ctx, int B, const uint16_t *const *fr
 int hpe_view_fit(int width, int height, int pitch, double fx, double cx, double cy, int step,
                  uint32_t flags, hpe_view *out, double *focal_out, double residual_px[2]);
 int hpe_batch_views_readback(hpe_ctx *ctx, int B, hpe_view *out);
+
+/* Lane cleaning: a live batch's 16-bit frames cleaned on the device, per lane, ahead of the
+ * preparation.  A real depth camera delivers flying pixels at the hand's silhouette, at depths
+ * between the hand and the background, which pass a window's depth range and enter the point
+ * cloud, and isolated speckle, which the distance transform's mask takes for hand.  The rule is
+ * on integers, so it is bit-exact.  F is the lane's 240x320 model image of 16-bit values -- for a
+ * view lane the pick the view defines, so neighbours are MODEL-image neighbours -- and the eight
+ * neighbours q of pixel p read 0 where they fall outside the image.  With u = F[p],
+ *   near(q)  <=>  F[q] != 0 && |F[q] - u| <= edge      (the difference in 32-bit integers)
+ *   s = the number of near neighbours
+ *   out[p] = 0                       if u == 0       (a hole stays a hole: nothing is invented)
+ *          = 0                       if s < support  (the flying pixel, the speckle)
+ *          = sorted(C)[s / 2]        with HPE_CLEAN_MEDIAN, C = {u} + {F[q] : near(q)}, s + 1
+ *                                    values ascending: the median, the lower one of an even count
+ *          = u                       otherwise
+ * Every output depends on the input image alone: one pass, never in place.  support = 0 without
+ * the flag is the identity.  edge is in the frame's raw units.  hpe/clean.py is the rule in numpy.
+ *
+ * hpe_set_batch_clean gives lane b the parameters params[b] (host, B entries, read before return)
+ * from the next hpe_batch_pipeline_begin_u16 / _begin_view on; params == NULL turns cleaning off
+ * (the default; B is then ignored).  A cleaned batch runs one more launch per frame, k_clean_b,
+ * directly ahead of the launch that prepares the lanes' next frames (at a begin, ahead of the
+ * preparation): it reads each lane's pinned buffer -- every pixel once per workgroup that needs
+ * it, so the rows either side of an 8-row tile's border twice, 1.25 reads per pixel in all --
+ * through the lane's view on a view batch, and writes the cleaned 240x320 frame to device memory, from where the u16 preparation reads it.
+ * Everything downstream -- windows, lane hands, both pacings, both batch forms, reports, seeds and
+ * groups, hpe_batch_pipeline_optimise -- works unchanged, hpe_batch_frame_buffer keeps its
+ * contract, and hpe_batch_pipeline_locate reads the lane's cleaned current frame.  Lane b equals,
+ * bit for bit after every frame, hpe_pipeline_begin + hpe_track_pipelined on the stream cleaned on
+ * the host by the rule above (after the view's reduction) and converted by the u16 rule.  The
+ * parameters live in a device table, never a captured argument: other parameters replay the same
+ * graphs.  While a live batch that began with cleaning on is in progress, non-NULL params of the
+ * same B are accepted: the call drains the stream, rewrites the table, and the new parameters
+ * apply from the next frame cleaned (the next frames of the following track call).  With cleaning
+ * off a batch launches exactly what it launches without this section.
+ *
+ * hpe_clean_defaults (host only, no context) fills {edge = lrint(15 / unit_mm) (at least 1, at
+ * most 65535), support = 3, HPE_CLEAN_MEDIAN} for frames of unit_mm millimetres per count:
+ * untuned, tried on rendered scenes with synthetic camera noise only (hpe/synth.py camera_noise).
+ * hpe_clean_depth_u16 applies the rule to one host frame by the same kernel, through a staging
+ * buffer, and synchronises: frame is 240x320, or with a view a pitch x height camera frame; out
+ * receives 240x320 values.  hpe_batch_clean_readback synchronises and copies lane `lane`'s cleaned
+ * frame of buffer parity `parity` (0: the begin's frames, then alternating).
+ *
+ * Refused with HPE_E_ARG, nothing changed: B outside 1..HPE_BATCH_MAX, support > 8, an unknown
+ * flag bit, non-zero pad; a u16 or view begin whose B differs from the B the parameters were set
+ * for; null frame, params or out, an invalid view, a unit_mm that is not finite and positive;
+ * parity outside 0..1, a lane outside the cleaned batch.  HPE_E_STATE: turning cleaning on or off,
+ * or other parameters for another B, while a live batch is in progress; hpe_batch_pipeline_begin
+ * (float frames) and hpe_track_raw_batch_dev while cleaning is set -- the rule is defined on
+ * 16-bit values, and it is refused, never run another way; hpe_batch_clean_readback without a
+ * cleaned batch begun on the context.  hpe_track_batch_dev prepares nothing and ignores the
+ * setting, as it ignores windows. */
+#define HPE_CLEAN_MEDIAN 1u
+typedef struct hpe_clean {   /* 8 bytes */
+    uint16_t edge;           /* raw units: a neighbour within this of the pixel is near */
+    uint8_t support;         /* 0..8: near neighbours a pixel needs to stay */
+    uint8_t flags;           /* HPE_CLEAN_MEDIAN or 0 */
+    uint32_t pad;            /* 0 */
+} hpe_clean;
+int hpe_clean_defaults(float unit_mm, hpe_clean *out);
+int hpe_set_batch_clean(hpe_ctx *ctx, int B, const hpe_clean *params);
+int hpe_clean_depth_u16(hpe_ctx *ctx, const uint16_t *frame, const hpe_view *view,
+                        const hpe_clean *params, uint16_t *out);
+int hpe_batch_clean_readback(hpe_ctx *ctx, int parity, int lane, uint16_t *out);
 
 /* The form of pso_evolve in the three batch calls above (hpe_track_batch_dev,
  * hpe_track_raw_batch_dev, hpe_batch_pipeline_begin / hpe_track_batch_pipelined).

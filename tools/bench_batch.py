@@ -63,6 +63,10 @@ frame back, and runs the lanes alone on its float conversion.  --host-reduce (wi
 application makes without views, cam[r0:r0+240K:K, c0:c0+320K:K], and fed to the plain u16 batch
 (with --in-place that copy goes straight into the lane's pinned buffer): the baseline a view batch
 is measured against.  All three runs track identical trajectories and print the same results_sha1.
+--clean (with --live --input u16|view): lane cleaning on (hpe_set_batch_clean) with the default
+parameters of the run's unit in every lane, set after the check; the line carries "clean": true
+and prices the cleaning launch per frame against a run without it (the frames are the noise-free
+renders: the median still moves silhouette values, so results_sha1 differs from the run without).
 --seeds distinct (with any mode and form): a seed per lane (hpe_set_batch_seeds), lane b's 1000 + b;
 the default, shared, is every lane under the context's seed (the call is not made).  The check
 against the lanes alone runs before the seeds are set.
@@ -76,7 +80,7 @@ Usage (GPU box): python tools/bench_batch.py [--raw | --live] [--form auto|wave]
                                              [--pacing lockstep|free] [--drop K]
                                              [--report DEPTH] [--consume sync|report]
                                              [--input f32|u16|view] [--unit MM] [--in-place]
-                                             [--cam WxH] [--step K] [--host-reduce]
+                                             [--cam WxH] [--step K] [--host-reduce] [--clean]
                                              [--lanes 1,2,4,8,16] [--frames 48] [--reps 3]
 """
 import argparse
@@ -379,7 +383,10 @@ def main():
     ap.add_argument("--in-place", action="store_true")
     ap.add_argument("--seeds", choices=("shared", "distinct"), default="shared")
     ap.add_argument("--group", type=int, default=0, metavar="N")
+    ap.add_argument("--clean", action="store_true")
     a = ap.parse_args()
+    if a.clean and (not a.live or a.drop or a.input not in ("u16", "view")):
+        ap.error("--clean cleans a live batch's 16-bit frames: --live --input u16|view, no --drop")
     if a.group < 0 or any(int(x) % max(a.group, 1) for x in a.lanes.split(",")):
         ap.error("--group N: N >= 1 divides every lane count")
     if a.group and (a.hands != "shared" or a.drop):
@@ -554,6 +561,8 @@ def main():
             ctx.set_batch_seeds([1000 + b for b in range(B)])
         if a.group:
             ctx.set_batch_groups([a.group] * (B // a.group))
+        if a.clean:  # after the check, which runs the lanes uncleaned
+            ctx.set_batch_clean([hpe.clean.defaults(float(unit))] * B)
         off = None
         if a.window != "off":  # the same lanes without windows, then the windows for B lanes
             run()
@@ -595,6 +604,8 @@ def main():
                 line["cam"] = "%dx%d" % (view.width, view.height)
                 line["step"] = view.step
                 line["host_reduce"] = a.host_reduce
+        if a.clean:
+            line["clean"] = True
         if a.report:
             line["report_depth"] = a.report
         if a.consume:
@@ -637,6 +648,8 @@ def main():
             ctx.set_batch_seeds(None)
         if a.group:
             ctx.set_batch_groups(None)
+        if a.clean:
+            ctx.set_batch_clean(None)
     ctx.close()
     return 0
 
